@@ -8,11 +8,18 @@ set -euo pipefail
 here="$(cd "$(dirname "$0")" && pwd)"
 ref="${TD_REFERENCE_ROOT:-/root/reference}"
 out="$here/_ref"
+pcre="$(ls /usr/lib/x86_64-linux-gnu/libpcre2-8.so.0 2>/dev/null || true)"
+# PCRE2's interpreter behind the reference's split loop (oracle/pcre2_interp.c): the oracle of the random-pattern tests.  Needs
+# the PCRE2 runtime only, not the reference checkout.
+if [ -n "$pcre" ]; then
+    mkdir -p "$out"
+    gcc -O1 -fPIC -shared -I"$here/shim" "$here/pcre2_interp.c" "$pcre" -o "$out/libpcre2interp.so"
+    echo "built $out/libpcre2interp.so"
+fi
 if [ ! -f "$ref/src/tiktoken/tiktoken.cpp" ]; then
     echo "build_ref: $ref/src/tiktoken/tiktoken.cpp not present; keeping prebuilt $out (if any)" >&2
     exit 0
 fi
-pcre="$(ls /usr/lib/x86_64-linux-gnu/libpcre2-8.so.0 2>/dev/null || true)"
 if [ -z "$pcre" ]; then echo "build_ref: libpcre2-8.so.0 not found" >&2; exit 1; fi
 mkdir -p "$out"
 g++ -std=c++17 -O2 -fPIC -w -pthread -shared \
@@ -20,9 +27,6 @@ g++ -std=c++17 -O2 -fPIC -w -pthread -shared \
     "$ref/src/tiktoken/tiktoken.cpp" "$here/ref_driver.cpp" \
     "$pcre" -o "$out/libtdref.so"
 echo "built $out/libtdref.so"
-# PCRE2's interpreter behind the reference's split loop (oracle/pcre2_interp.c): the oracle of the random-pattern tests
-gcc -O1 -fPIC -shared -I"$here/shim" "$here/pcre2_interp.c" "$pcre" -o "$out/libpcre2interp.so"
-echo "built $out/libpcre2interp.so"
 # The reference's own Python extension (src/py_binding.cpp, unmodified, compiled where it lies) for the cpu_baseline leg that
 # follows the reference's benchmark METHOD (Tokenizer.encode_batch: Python threads over the pybind CoreBPE.encode,
 # tests/throughput_test.py:413-422).  extern/pybind11 is an empty submodule in the checkout: the installed pybind11 headers
