@@ -188,6 +188,48 @@ int td_encode_device_with_special(td_tokenizer* t, const void* d_text, int64_t n
                                   const int32_t* allowed_ids, int64_t n_allowed, void* d_out_tokens, int64_t out_capacity,
                                   void* d_out_offsets, void* hip_stream);
 
+/* ---- per-token start offsets (td_offsets.hip) ----------------------------------------------------------------------------
+ * The START of a token is where its text begins in its own document:
+ *   TD_UNIT_BYTES  the offset of its first byte in the document's UTF-8 bytes;
+ *   TD_UNIT_CHARS  tiktoken's decode_with_offsets rule in code points: with chars(b) = the bytes of doc[0, b) that are not
+ *                  continuation bytes (0x80..0xBF), start = max(0, chars(b) - (doc[b] is a continuation byte)) — a token that
+ *                  begins inside a character points at that character; for text that is valid UTF-8 the index into the
+ *                  decoded string.
+ * The end of a token in bytes is start + its byte length (td_token_bytes).  Starts are computed on the device: a segmented
+ * scan of per-id byte lengths or character counts (a per-id table built at td_create, special tokens included); a generic
+ * pattern that skips text maps the documents where it did through a bitmap of the bytes it covered.  Errors are reported
+ * like the other entry points': an id outside the vocabulary is TD_E_BAD_TOKEN with its index, a too small output
+ * TD_E_CAPACITY. */
+#define TD_UNIT_BYTES 0
+#define TD_UNIT_CHARS 1
+
+/* Starts from ids alone, by the covered rule (every document's bytes are its tokens' bytes concatenated): the offsets of
+ * decode_with_offsets, and the encode offsets of any pattern that skips no text.  tokens[n_tokens] holds the ids of all
+ * documents concatenated, tok_offsets[n_docs+1] the first id of every document; out_starts has room for n_tokens starts
+ * (tok_offsets[n_docs] > n_tokens: TD_E_CAPACITY).  Synchronous. */
+int td_token_starts(td_tokenizer* t, const int32_t* tokens, int64_t n_tokens, const int64_t* tok_offsets, int64_t n_docs, int unit,
+                    int64_t* out_starts);
+/* The same on device buffers, asynchronously on hip_stream; errors surface through td_device_status. */
+int td_token_starts_device(td_tokenizer* t, const void* d_tokens, int64_t n_tokens, const void* d_tok_offsets, int64_t n_docs, int unit,
+                           void* d_out_starts, void* hip_stream);
+
+/* td_encode_batch_with_special_strs (mode TD_MODE_ENCODE) / td_encode_batch (n_allowed == 0) that also returns the start of
+ * every id: out_starts (int64, room for out_capacity) in `unit`.  The ids equal those of the entry points it stands for.
+ * Every pattern kind: the family's, generic patterns (also where they skip text) and allowed special tokens (a special's
+ * start is where its literal stands; the starts of the text between two specials are shifted by where it stands).
+ * TD_MODE_ORDINARY takes no allowed set (TD_E_INVALID).  Synchronous; it takes the copy-and-synchronise path at every size
+ * (not the one-launch, mid-size or pipelined forms of td_encode_batch).  TD_UNIT_CHARS: less than 4 GiB of text a call. */
+int td_encode_batch_with_starts(td_tokenizer* t, const uint8_t* text, const int64_t* doc_offsets, int64_t n_docs, int mode,
+                                const uint8_t* allowed_bytes, const int64_t* allowed_offsets, int64_t n_allowed, int unit,
+                                int32_t* out_tokens, int64_t out_capacity, int64_t* out_offsets, int64_t* out_starts, int64_t* n_tokens);
+
+/* td_encode_device that also writes d_out_starts (int64, room for out_capacity): device-resident and asynchronous like
+ * td_encode_device, every pattern kind, no special tokens.  The starts are launched behind the encode on the same stream
+ * (a generic pattern's skipped text is read from the workspace of this very call).  TD_UNIT_CHARS: n_bytes below 4 GiB. */
+int td_encode_device_with_starts(td_tokenizer* t, const void* d_text, int64_t n_bytes, const void* d_doc_offsets, int64_t n_docs, int mode,
+                                 int unit, void* d_out_tokens, int64_t out_capacity, void* d_out_offsets, void* d_out_starts,
+                                 void* hip_stream);
+
 /* Options. */
 #define TD_OPT_LONG_POOL_BYTES 1 /* scratch for pieces longer than 64 bytes (default max(64 MiB, 2 x input)) */
 #define TD_OPT_PROFILE 2         /* 1: bracket the kernels of every td_encode_device call with HIP events on the

@@ -18,6 +18,9 @@ TD_OK = 0
 TD_E_CAPACITY = 5
 TD_MODE_ENCODE = 0
 TD_MODE_ORDINARY = 1
+TD_E_INVALID = 1
+TD_E_BAD_TOKEN = 8
+TD_UNIT_BYTES, TD_UNIT_CHARS = 0, 1
 TD_INFO_N_PAIRS, TD_INFO_MERGE_CLOSED, TD_INFO_MAX_ID, TD_INFO_TILE_BYTES = 1, 2, 3, 4
 TD_INFO_WORKSPACE_BYTES, TD_INFO_N_SPECIAL, TD_INFO_LONG_PIECES, TD_INFO_FAR_PIECES = 5, 6, 7, 8
 TD_OPT_LONG_POOL_BYTES = 1
@@ -49,7 +52,8 @@ EXPORTS = [
     "td_create_from_vocab", "td_token_bytes", "td_single_token", "td_decode_device", "td_decode_batch", "td_encode_batch_with_special",
     "td_encode_with_special_strs", "td_encode_batch_with_special_strs", "td_profile_read_ex", "td_profile_segment_name",
     "td_comm_unique_id", "td_comm_create", "td_comm_destroy", "td_comm_gather_counts", "td_comm_bases", "td_comm_gather_tokens",
-    "td_comm_last_error", "td_encode_device_with_special",
+    "td_comm_last_error", "td_encode_device_with_special", "td_token_starts", "td_token_starts_device", "td_encode_batch_with_starts",
+    "td_encode_device_with_starts",
 ]
 
 
@@ -98,6 +102,14 @@ def load_library():
     vp, i64, i32 = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int
     lib.td_encode_device_with_special.restype = i32
     lib.td_encode_device_with_special.argtypes = [vp, vp, i64, vp, i64, vp, i64, vp, i64, vp, vp]
+    lib.td_token_starts.restype = i32
+    lib.td_token_starts.argtypes = [vp, vp, i64, vp, i64, i32, vp]
+    lib.td_token_starts_device.restype = i32
+    lib.td_token_starts_device.argtypes = [vp, vp, i64, vp, i64, i32, vp, vp]
+    lib.td_encode_batch_with_starts.restype = i32
+    lib.td_encode_batch_with_starts.argtypes = [vp, vp, vp, i64, i32, vp, vp, i64, i32, vp, i64, vp, vp, ctypes.POINTER(i64)]
+    lib.td_encode_device_with_starts.restype = i32
+    lib.td_encode_device_with_starts.argtypes = [vp, vp, i64, vp, i64, i32, i32, vp, i64, vp, vp, vp]
     lib.td_comm_unique_id.restype = i32
     lib.td_comm_unique_id.argtypes = [vp]
     lib.td_comm_create.restype = i32
@@ -410,6 +422,49 @@ class HipTokenizer:
                                                          out_offs.ctypes.data, ctypes.byref(ntok))
         self._check(rc)
         return toks[:ntok.value].copy(), out_offs
+
+    # ---- start offsets (TD_UNIT_BYTES / TD_UNIT_CHARS) ---------------------------------------
+    def token_starts(self, tokens, tok_offsets=None, unit: int = TD_UNIT_BYTES, n_tokens: int | None = None) -> np.ndarray:
+        """td_token_starts: ids (all documents concatenated) + int64 tok_offsets (default: one document) -> int64 starts."""
+        t = np.ascontiguousarray(tokens, dtype=np.int32)
+        o = np.ascontiguousarray([0, len(t)] if tok_offsets is None else tok_offsets, dtype=np.int64)
+        n = len(t) if n_tokens is None else n_tokens
+        out = np.empty(max(n, 1), dtype=np.int64)
+        self._check(self._lib.td_token_starts(self._h, t.ctypes.data if len(t) else None, n, o.ctypes.data, len(o) - 1, unit,
+                                              out.ctypes.data))
+        return out[:int(o[-1])]
+
+    def token_starts_device(self, d_tokens: int, n_tokens: int, d_tok_offsets: int, n_docs: int, d_out_starts: int, unit: int = TD_UNIT_BYTES,
+                            stream: int = 0):
+        """Asynchronous on `stream`; check with device_status(stream)."""
+        self._check(self._lib.td_token_starts_device(self._h, d_tokens, n_tokens, d_tok_offsets, n_docs, unit, d_out_starts, stream or None))
+
+    def encode_batch_with_starts(self, text, doc_offsets, mode: int = TD_MODE_ENCODE, allowed=(), unit: int = TD_UNIT_BYTES,
+                                 capacity: int | None = None):
+        """td_encode_batch_with_starts: -> (tokens int32[total], offsets int64[n_docs+1], starts int64[total]).
+        allowed: special-token strings that are cut out."""
+        buf = _as_u8(text)
+        offs = np.ascontiguousarray(doc_offsets, dtype=np.int64)
+        ab, ao = self._pack_strs(list(allowed))
+        n_docs = len(offs) - 1
+        n = int(offs[-1]) if len(offs) else 0
+        cap = capacity if capacity is not None else n + 16
+        out_offs = np.empty(n_docs + 1, dtype=np.int64)
+        toks = np.empty(max(cap, 1), dtype=np.int32)
+        starts = np.empty(max(cap, 1), dtype=np.int64)
+        ntok = ctypes.c_int64(0)
+        rc = self._lib.td_encode_batch_with_starts(self._h, buf.ctypes.data if n else None, offs.ctypes.data, n_docs, mode, ab.ctypes.data,
+                                                   ao.ctypes.data, len(ao) - 1, unit, toks.ctypes.data, cap, out_offs.ctypes.data,
+                                                   starts.ctypes.data, ctypes.byref(ntok))
+        self._check(rc)
+        return toks[:ntok.value].copy(), out_offs, starts[:ntok.value].copy()
+
+    def encode_device_with_starts(self, d_text: int, n_bytes: int, d_doc_offsets: int, n_docs: int, d_out_tokens: int, out_capacity: int,
+                                  d_out_offsets: int, d_out_starts: int, unit: int = TD_UNIT_BYTES, stream: int = 0,
+                                  mode: int = TD_MODE_ENCODE):
+        """td_encode_device + the starts (int64, room for out_capacity), asynchronous on `stream`."""
+        self._check(self._lib.td_encode_device_with_starts(self._h, d_text, n_bytes, d_doc_offsets, n_docs, mode, unit, d_out_tokens,
+                                                           out_capacity, d_out_offsets, d_out_starts, stream or None))
 
     def decode_bytes(self, tokens) -> bytes:
         t = np.ascontiguousarray(tokens, dtype=np.int32)

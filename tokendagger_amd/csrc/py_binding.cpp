@@ -487,6 +487,58 @@ public:
         return py::make_tuple(toks, toffs);
     }
 
+    // ---- start offsets (td_encode_batch_with_starts, td_token_starts) --------------------------------------------------------
+    // concatenated UTF-8 + int64 offsets in, (int32 ids, int64 token offsets, int64 starts in `unit`) out; allowed: special strings
+    py::tuple starts_batch(const uint8_t* tp, const int64_t* op, int64_t n_docs, int mode, const std::set<std::string>& allowed, int unit) {
+        std::vector<uint8_t> ab;
+        std::vector<int64_t> ao;
+        pack_allowed(allowed, ab, ao);
+        const int64_t nbytes = op[n_docs];
+        int64_t cap = nbytes + 16;  // (at most one id per byte, and one per special)
+        py::array_t<int32_t> toks(cap);
+        py::array_t<int64_t> toffs(n_docs + 1), starts(cap);
+        int64_t n = 0;
+        int rc;
+        {
+            int32_t* outp = toks.mutable_data();
+            int64_t* top = toffs.mutable_data();
+            int64_t* sp = starts.mutable_data();
+            py::gil_scoped_release rel;
+            rc = td_encode_batch_with_starts(h_, tp, op, n_docs, mode, ab.data(), ao.data(), (int64_t)ao.size() - 1, unit, outp, cap, top, sp, &n);
+        }
+        if (rc != TD_OK) fail();
+        toks.resize({(py::ssize_t)n}, false);
+        starts.resize({(py::ssize_t)n}, false);
+        return py::make_tuple(toks, toffs, starts);
+    }
+    py::tuple encode_batch_numpy_with_starts(py::array_t<uint8_t, py::array::c_style | py::array::forcecast> text,
+                                             py::array_t<int64_t, py::array::c_style | py::array::forcecast> offsets, int mode, int unit) {
+        const int64_t n_docs = (int64_t)offsets.size() - 1;
+        if (n_docs < 0) throw TiktokenError("offsets must have n_docs+1 entries");
+        if (offsets.data()[n_docs] > (int64_t)text.size()) throw TiktokenError("offsets exceed the text buffer");
+        return starts_batch(text.data(), offsets.data(), n_docs, mode, {}, unit);
+    }
+    // -> (list[int] ids, list[int] starts)
+    py::tuple encode_with_starts(const std::string& text, const std::set<std::string>& allowed, int unit) {
+        const int64_t offs[2] = {0, (int64_t)text.size()};
+        py::tuple r = starts_batch((const uint8_t*)text.data(), offs, 1, TD_MODE_ENCODE, allowed, unit);
+        return py::make_tuple(r[0].attr("tolist")(), r[2].attr("tolist")());
+    }
+    py::array_t<int64_t> token_starts(py::array_t<int32_t, py::array::c_style | py::array::forcecast> ids, int unit) {
+        const int64_t n = (int64_t)ids.size();
+        const int64_t offs[2] = {0, n};
+        py::array_t<int64_t> starts(n);
+        int rc;
+        {
+            int64_t* sp = starts.mutable_data();
+            const int32_t* ip = ids.data();
+            py::gil_scoped_release rel;
+            rc = td_token_starts(h_, ip, n, offs, 1, unit, sp);
+        }
+        if (rc != TD_OK) fail();
+        return starts;
+    }
+
     // list[str] in, list[list[int]] out through ONE device batch (PackedTexts / IntCache above)
     py::list encode_batch(const py::sequence& texts, int mode) {
         PackedTexts in(texts);
@@ -638,6 +690,10 @@ PYBIND11_MODULE(_tokendagger_core, m) {
         .def("encode_batch", &CoreBPE::encode_batch, py::arg("texts"), py::arg("mode") = TD_MODE_ENCODE)
         .def("encode_batch_numpy", &CoreBPE::encode_batch_numpy, py::arg("text"), py::arg("offsets"), py::arg("mode") = TD_MODE_ENCODE)
         .def("decode_to_bytes", &CoreBPE::decode_to_bytes, py::arg("tokens"))
+        .def("encode_with_starts", &CoreBPE::encode_with_starts, py::arg("text"), py::arg("allowed_special"), py::arg("unit"))
+        .def("encode_batch_numpy_with_starts", &CoreBPE::encode_batch_numpy_with_starts, py::arg("text"), py::arg("offsets"),
+             py::arg("mode") = TD_MODE_ENCODE, py::arg("unit") = TD_UNIT_BYTES)
+        .def("token_starts", &CoreBPE::token_starts, py::arg("ids"), py::arg("unit"))
         .def("decode_batch", &CoreBPE::decode_batch, py::arg("docs"))
         .def("encode_batch_special", &CoreBPE::encode_batch_special, py::arg("texts"), py::arg("allowed_special"))
         .def("token_bytes", &CoreBPE::token_bytes, py::arg("id"))

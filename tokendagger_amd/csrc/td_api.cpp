@@ -17,6 +17,7 @@
 
 #include "../../include/tokendagger_hip.h"
 #include "td_kernels.h"
+#include "td_offsets.h"
 #include "td_regex.h"
 #include "td_tables.h"
 #include "td_vocab.h"
@@ -187,6 +188,9 @@ struct td_tokenizer {
     DevBuf dd_table, rest_mask, coll_ctr, tile_state, slab, docbits, startbits, slow_list, tile_flag, tile_carry, stage, stage2, tile_count, tile_extra, miss_list, flagged_list, deferred_list, gap_list, gapbits, gx_exit, gx_state, tile_base, doc_slot, long_list, pool, ctl, tile_first_doc, chunk_pref;
     DevBuf h2d_text, h2d_offs, d_tokens, d_offsets;  // host-API staging
     DevBuf dec_tokens, dec_off, dec_out;
+    // per-token starts (td_offsets.hip): the per-id character table (td_create, shared like the other tables) and the scratch
+    const uint32_t* d_ctab = nullptr;
+    DevBuf off_heads, off_chunks, off_docs, off_rank, off_starts;
     int64_t pool_bytes_opt = 0;
     bool profile = false;
     int stop_after = 0;
@@ -740,6 +744,71 @@ int absorb_ctl(td_tokenizer* t, Ctl c, hipStream_t stream, int64_t* err_pos) {
     return TD_OK;
 }
 
+// ---- per-token starts (td_offsets.hip) -------------------------------------------------------------------------------------
+int starts_args(td_tokenizer* t, StartsArgs& a, const void* tokens, const void* tok_off, int64_t n_docs, int64_t n_bound, int kind,
+                void* out) {
+    int rc;
+    const int64_t nch = n_bound / OFF_CHUNK + 2;
+    if ((rc = ensure(t, t->off_heads, (size_t)(n_bound / 32 + 2) * 4))) return rc;
+    if ((rc = ensure(t, t->off_chunks, (size_t)nch * 12))) return rc;
+    memset(&a, 0, sizeof a);
+    a.tokens = (const int32_t*)tokens;
+    a.tok_off = (const int64_t*)tok_off;
+    a.n_docs = n_docs;
+    a.n_bound = n_bound;
+    a.len_off = t->dT.tok_off;
+    a.ctab = t->d_ctab;
+    a.max_id = t->H.max_id;
+    a.kind = kind;
+    a.out = (int64_t*)out;
+    a.heads = (uint32_t*)t->off_heads.p;
+    a.chunk_sum = (unsigned long long*)t->off_chunks.p;
+    a.chunk_head = (uint32_t*)(a.chunk_sum + nch);
+    Ctl* ctl = (Ctl*)t->ctl.p;
+    a.err = &ctl->err;
+    a.err_pos = &ctl->err_pos;
+    return TD_OK;
+}
+
+int token_starts_locked(td_tokenizer* t, const void* d_tokens, int64_t n_tokens, const void* d_tok_off, int64_t n_docs, int unit, void* d_out,
+                        hipStream_t stream) {
+    int rc;
+    if ((rc = order_before(t, stream))) return rc;
+    StartsArgs a;
+    if ((rc = starts_args(t, a, d_tokens, d_tok_off, n_docs, n_tokens, unit == TD_UNIT_CHARS ? OFF_CHARS : OFF_BYTES, d_out))) return rc;
+    HIP_TRY(t, launch_token_starts(a, stream));
+    return order_after(t, stream);
+}
+
+// Behind encode_device_locked, on the same stream: the generic engine's bitmaps in the workspace are still those of this call.
+// Starts by the covered rule (chars: bytes and characters packed, every document checked against its length), then the documents
+// with skipped text through the covered-byte bitmap.
+int encode_starts_locked(td_tokenizer* t, const void* d_text, int64_t n, const void* d_offs, int64_t n_docs, const void* d_tokens,
+                         int64_t cap, const void* d_out_offs, int unit, void* d_starts, hipStream_t stream) {
+    const int64_t bound = std::min(cap, n);
+    if (bound <= 0 || n_docs <= 0) return TD_OK;  // (no ids; a capacity too small for the ids is the encode's error)
+    const bool chars = unit == TD_UNIT_CHARS, generic = t->H.pattern_kind == PATTERN_GENERIC;
+    int rc;
+    StartsArgs a;
+    if ((rc = starts_args(t, a, d_tokens, d_out_offs, n_docs, bound, chars ? OFF_PAIR : OFF_BYTES, d_starts))) return rc;
+    if ((rc = ensure(t, t->off_docs, (size_t)n_docs + 16))) return rc;
+    a.text = (const uint8_t*)d_text;
+    a.n = n;
+    a.doc_off = (const int64_t*)d_offs;
+    a.doc_gap = (uint8_t*)t->off_docs.p;
+    a.generic = generic ? 1 : 0;
+    a.chars = chars ? 1 : 0;
+    if (generic) {
+        if ((rc = ensure(t, t->off_rank, off_rank_bytes(n)))) return rc;
+        off_rank_layout(a, t->off_rank.p, n);
+        a.startbits = (const uint32_t*)t->startbits.p;
+        a.gapbits = (const uint32_t*)t->gapbits.p;
+    }
+    HIP_TRY(t, launch_token_starts(a, stream));
+    HIP_TRY(t, launch_encode_starts(a, stream));
+    return order_after(t, stream);
+}
+
 }  // namespace
 
 extern "C" {
@@ -841,6 +910,19 @@ int td_create(const char* pat_str, int64_t n_vocab, const uint8_t* token_bytes, 
         if ((rc = upload(t, s1, n1, &t->d_rx_s1))) return fail(rc);
         if ((rc = upload(t, s2, n2, &t->d_rx_s2))) return fail(rc);
     }
+    {
+        // per id (specials included): characters = bytes that are not continuation bytes, << 1 | the first byte is one.  Not a
+        // member of Tables (its argument footprint is tuned): the starts kernels take it as an argument of their own.
+        std::vector<uint32_t> ctab((size_t)H.max_id + 1, 0);
+        for (int32_t id = 0; id <= H.max_id; ++id) {
+            const uint32_t lo = H.tok_off[(size_t)id], hi = H.tok_off[(size_t)id + 1];
+            if (hi == lo) continue;
+            uint32_t c = 0;
+            for (uint32_t q = lo; q < hi; ++q) c += (H.tok_bytes[q] & 0xC0u) != 0x80u;
+            ctab[(size_t)id] = c << 1 | ((H.tok_bytes[lo] & 0xC0u) == 0x80u ? 1u : 0u);
+        }
+        if ((rc = upload(t, ctab.data(), ctab.size(), &t->d_ctab))) return fail(rc);
+    }
     t->dT = d;
     if ((rc = upload(t, &t->dT, 1, &t->dTp))) return fail(rc);
     if ((rc = ensure(t, t->ctl, CTL_BYTES + TD_GP_SCRATCH_BYTES))) return fail(rc);
@@ -858,7 +940,7 @@ int td_clone(td_tokenizer* src, td_tokenizer** out) {
         std::lock_guard<std::mutex> g(src->mu);  // (its options are read)
         t = new td_tokenizer(src->shared);
         t->dT = src->dT; t->dTp = src->dTp; t->device = src->device;
-        t->d_rx = src->d_rx; t->d_rx_s1 = src->d_rx_s1; t->d_rx_s2 = src->d_rx_s2;
+        t->d_rx = src->d_rx; t->d_rx_s1 = src->d_rx_s1; t->d_rx_s2 = src->d_rx_s2; t->d_ctab = src->d_ctab;
         t->pool_bytes_opt = src->pool_bytes_opt; t->graphs = src->graphs; t->fused = src->fused; t->direct = src->direct; t->pack_split = src->pack_split; t->dedupe = src->dedupe; t->overlap = src->overlap; t->sparse_opt = src->sparse_opt; t->gp_coop_min = src->gp_coop_min; t->dd_entries_opt = src->dd_entries_opt; t->dd_minlen = src->dd_minlen; t->dd_replicas = src->dd_replicas; t->coll_shrink = src->coll_shrink;
         t->device_specials = src->device_specials; t->small_enabled = src->small_enabled; t->mid_enabled = src->mid_enabled; t->small_resident = src->small_resident; t->small_idle_ticks = src->small_idle_ticks;
         t->pipe_chunk_bytes = src->pipe_chunk_bytes; t->pipe_threads = src->pipe_threads;
@@ -903,7 +985,7 @@ void td_destroy(td_tokenizer* t) {
         if (t->small_out) (void)hipHostFree(t->small_out);
         DevBuf* bufs[] = {&t->dd_table, &t->rest_mask, &t->coll_ctr, &t->gx_prefix, &t->tile_state, &t->slab, &t->docbits, &t->startbits, &t->slow_list, &t->tile_flag, &t->tile_carry, &t->stage, &t->stage2, &t->tile_count, &t->tile_extra, &t->miss_list, &t->flagged_list, &t->deferred_list, &t->gap_list, &t->gapbits, &t->gx_exit, &t->gx_state, &t->sp_bytes, &t->sp_off, &t->sp_len, &t->sp_id, &t->sp_parent, &t->sp_first2, &t->sp_hit, &t->sp_acc, &t->sp_cpos, &t->sp_clit, &t->sp_ccount, &t->tile_base, &t->doc_slot, &t->long_list,
                           &t->pool, &t->ctl, &t->tile_first_doc, &t->chunk_pref, &t->h2d_text, &t->h2d_offs, &t->d_tokens, &t->d_offsets, &t->dec_tokens,
-                          &t->dec_off, &t->dec_out};
+                          &t->dec_off, &t->dec_out, &t->off_heads, &t->off_chunks, &t->off_docs, &t->off_rank, &t->off_starts};
         for (DevBuf* b : bufs)
             if (b->p) (void)hipFree(b->p);
     }
@@ -1427,19 +1509,22 @@ int encode_batch_mid(td_tokenizer* t, const uint8_t* text, const int64_t* doc_of
     return TD_OK;
 }
 
+// out_starts (optional, capacity out_capacity): the start of every id in its document in `unit` (td_encode_batch_with_starts); such
+// calls take the plain path below whatever the size
 int encode_batch_locked(td_tokenizer* t, const uint8_t* text, const int64_t* doc_offsets, int64_t n_docs, int mode,
-                        int32_t* out_tokens, int64_t out_capacity, int64_t* out_offsets, int64_t* n_tokens) {
+                        int32_t* out_tokens, int64_t out_capacity, int64_t* out_offsets, int64_t* n_tokens, int unit = TD_UNIT_BYTES,
+                        int64_t* out_starts = nullptr) {
     int rc;
     if ((rc = check_offsets(t, "doc_offsets", doc_offsets, n_docs, text))) return rc;
     const int64_t n = doc_offsets[n_docs];
-    const bool with_prefix = t->gx_prefix_host != nullptr;  // (generic pattern: the plain path below, whatever the size)
-    if (n > 0 && n <= SMALL_MAX_BYTES && n_docs <= SMALL_MAX_DOCS && t->small_enabled && t->H.pattern_kind != PATTERN_GENERIC) {  // (the one-launch kernel knows the family's scanners only)
+    const bool plain = t->gx_prefix_host != nullptr || out_starts;  // (context prefixes of a generic pattern, starts: the plain path below, whatever the size)
+    if (n > 0 && n <= SMALL_MAX_BYTES && n_docs <= SMALL_MAX_DOCS && t->small_enabled && t->H.pattern_kind != PATTERN_GENERIC && !out_starts) {  // (the one-launch kernel knows the family's scanners only)
         rc = encode_batch_small(t, text, doc_offsets, n_docs, mode, out_tokens, out_capacity, out_offsets, n_tokens);
         if (rc != -1) return rc;  // (-1: a piece above 64 bytes; the general path below handles it)
     }
-    if (n > 0 && n <= MID_MAX_BYTES && n_docs <= MID_MAX_DOCS && t->mid_enabled && !with_prefix)
+    if (n > 0 && n <= MID_MAX_BYTES && n_docs <= MID_MAX_DOCS && t->mid_enabled && !plain)
         return encode_batch_mid(t, text, doc_offsets, n_docs, mode, out_tokens, out_capacity, out_offsets, n_tokens);
-    if (n >= t->pipe_chunk_bytes / 2 && out_tokens && !with_prefix)  // (default: from 32 MiB on)
+    if (n >= t->pipe_chunk_bytes / 2 && out_tokens && !plain)  // (default: from 32 MiB on)
         return encode_batch_pipelined(t, text, doc_offsets, n_docs, mode, out_tokens, out_capacity, out_offsets, n_tokens);
     if ((rc = ensure(t, t->h2d_text, (size_t)n + 64))) return rc;
     if ((rc = ensure(t, t->h2d_offs, (size_t)(n_docs + 1) * 8))) return rc;
@@ -1452,7 +1537,7 @@ int encode_batch_locked(td_tokenizer* t, const uint8_t* text, const int64_t* doc
     if ((rc = order_before(t, s))) return rc;
     if (n > 0) HIP_TRY(t, hipMemcpyAsync(t->h2d_text.p, text, (size_t)n, hipMemcpyHostToDevice, s));
     HIP_TRY(t, hipMemcpyAsync(t->h2d_offs.p, doc_offsets, (size_t)(n_docs + 1) * 8, hipMemcpyHostToDevice, s));
-    if (with_prefix) {
+    if (t->gx_prefix_host) {
         if ((rc = ensure(t, t->gx_prefix, (size_t)n_docs + 16))) return rc;
         HIP_TRY(t, hipMemcpyAsync(t->gx_prefix.p, t->gx_prefix_host, (size_t)n_docs, hipMemcpyHostToDevice, s));
         t->gx_prefix_dev = (const uint8_t*)t->gx_prefix.p;
@@ -1460,6 +1545,11 @@ int encode_batch_locked(td_tokenizer* t, const uint8_t* text, const int64_t* doc
     rc = encode_device_locked(t, t->h2d_text.p, n, t->h2d_offs.p, n_docs, mode, t->d_tokens.p, dev_cap, t->d_offsets.p, s);
     t->gx_prefix_dev = nullptr;
     if (rc) return rc;
+    if (out_starts) {
+        if ((rc = ensure(t, t->off_starts, (size_t)dev_cap * 8))) return rc;
+        if ((rc = encode_starts_locked(t, t->h2d_text.p, n, t->h2d_offs.p, n_docs, t->d_tokens.p, dev_cap, t->d_offsets.p, unit, t->off_starts.p, s)))
+            return rc;
+    }
     rc = device_status_locked(t, s, nullptr);
     if (rc) return rc;
     if ((rc = copy_wait(t, out_offsets, t->d_offsets.p, (size_t)(n_docs + 1) * 8, hipMemcpyDeviceToHost, s))) return rc;
@@ -1472,6 +1562,7 @@ int encode_batch_locked(td_tokenizer* t, const uint8_t* text, const int64_t* doc
     if (total > 0) {
         if (!out_tokens) { t->err = "null out_tokens"; return TD_E_INVALID; }
         if ((rc = copy_wait(t, out_tokens, t->d_tokens.p, (size_t)total * 4, hipMemcpyDeviceToHost, s))) return rc;
+        if (out_starts && (rc = copy_wait(t, out_starts, t->off_starts.p, (size_t)total * 8, hipMemcpyDeviceToHost, s))) return rc;
     }
     return TD_OK;
 }
@@ -1773,23 +1864,62 @@ void segment_document(const SpecialIndex& ix, const uint8_t* text, int64_t lo, i
     starts.push_back(start); ends.push_back(hi); seg_special.push_back(-1);
 }
 
+// Document-relative byte starts (host) -> characters, by rank over the documents' text on the device (td_encode_batch_with_starts
+// behind allowed special tokens: segments are encoded in bytes, stitched on the host, then converted here).
+int chars_by_rank_locked(td_tokenizer* t, const uint8_t* text, const int64_t* doc_offsets, int64_t n_docs, const int64_t* tok_offsets,
+                         int64_t* starts, int64_t n_tok) {
+    const int64_t n = doc_offsets[n_docs];
+    if (n_tok <= 0 || n <= 0) return TD_OK;
+    int rc;
+    if ((rc = ensure(t, t->h2d_text, (size_t)n + 64))) return rc;
+    if ((rc = ensure(t, t->h2d_offs, (size_t)(n_docs + 1) * 8))) return rc;
+    if ((rc = ensure(t, t->d_offsets, (size_t)(n_docs + 1) * 8))) return rc;
+    if ((rc = ensure(t, t->off_starts, (size_t)n_tok * 8))) return rc;
+    if ((rc = ensure(t, t->off_rank, off_rank_bytes(n)))) return rc;
+    if ((rc = own_streams(t))) return rc;
+    hipStream_t s = t->s_own;
+    if ((rc = order_before(t, s))) return rc;
+    HIP_TRY(t, hipMemcpyAsync(t->h2d_text.p, text, (size_t)n, hipMemcpyHostToDevice, s));
+    HIP_TRY(t, hipMemcpyAsync(t->h2d_offs.p, doc_offsets, (size_t)(n_docs + 1) * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(t, hipMemcpyAsync(t->d_offsets.p, tok_offsets, (size_t)(n_docs + 1) * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(t, hipMemcpyAsync(t->off_starts.p, starts, (size_t)n_tok * 8, hipMemcpyHostToDevice, s));
+    StartsArgs a;
+    memset(&a, 0, sizeof a);
+    a.tok_off = (const int64_t*)t->d_offsets.p;
+    a.n_docs = n_docs;
+    a.n_bound = n_tok;
+    a.out = (int64_t*)t->off_starts.p;
+    a.text = (const uint8_t*)t->h2d_text.p;
+    a.n = n;
+    a.doc_off = (const int64_t*)t->h2d_offs.p;
+    a.chars = 1;
+    off_rank_layout(a, t->off_rank.p, n);
+    Ctl* ctl = (Ctl*)t->ctl.p;
+    a.err = &ctl->err;
+    a.err_pos = &ctl->err_pos;
+    HIP_TRY(t, launch_chars_by_rank(a, s));
+    if ((rc = order_after(t, s))) return rc;
+    if ((rc = device_status_locked(t, s, nullptr))) return rc;
+    return copy_wait(t, starts, t->off_starts.p, (size_t)n_tok * 8, hipMemcpyDeviceToHost, s);
+}
+
 // Shared body of the two *_with_special entry points (handle locked by the caller).
 int encode_special_locked(td_tokenizer* t, const uint8_t* text, const int64_t* doc_offsets, int64_t n_docs,
                           const uint8_t* allowed_bytes, const int64_t* allowed_offsets, const int32_t* allowed_ids, int64_t n_allowed,
                           int32_t* out_tokens, int64_t out_capacity, int64_t* out_offsets, int64_t* n_tokens,
-                          int64_t* last_seg_lo, int64_t* last_seg_hi) {
+                          int64_t* last_seg_lo, int64_t* last_seg_hi, int unit = TD_UNIT_BYTES, int64_t* out_starts = nullptr) {
     int rc;
     if ((rc = check_offsets(t, "doc_offsets", doc_offsets, n_docs, text))) return rc;
     if (n_allowed == 0) {  // nothing to cut out: the documents are the segments
         if (last_seg_lo) { *last_seg_lo = n_docs ? doc_offsets[n_docs - 1] : 0; *last_seg_hi = doc_offsets[n_docs]; }
-        return encode_batch_locked(t, text, doc_offsets, n_docs, TD_MODE_ENCODE, out_tokens, out_capacity, out_offsets, n_tokens);
+        return encode_batch_locked(t, text, doc_offsets, n_docs, TD_MODE_ENCODE, out_tokens, out_capacity, out_offsets, n_tokens, unit, out_starts);
     }
     SpecialIndex ix;
     if ((rc = build_special_index(t, allowed_bytes, allowed_offsets, allowed_ids, n_allowed, ix))) return rc;
     // Batches of a MiB and more: the search runs on the device (td_special.hip; the same cuts, td_encode_device_with_special)
     // when the allowed set can be named by ids (no other special string shares an allowed one's id) and the caller does not
     // ask for the last segment (the single-string entry points do, for last_piece_token_len).
-    if (t->device_specials && !last_seg_lo && doc_offsets[n_docs] >= (1ll << 20) && t->H.pattern_kind != PATTERN_GENERIC && ix.count > 0) {
+    if (t->device_specials && !last_seg_lo && !out_starts && doc_offsets[n_docs] >= (1ll << 20) && t->H.pattern_kind != PATTERN_GENERIC && ix.count > 0) {
         std::vector<int32_t> ids;
         bool nameable = true;
         for (const auto& e : ix.ents) {
@@ -1891,7 +2021,7 @@ int encode_special_locked(td_tokenizer* t, const uint8_t* text, const int64_t* d
     std::vector<int64_t> toffs((size_t)nseg + 1);
     int64_t ntok = 0;
     if (n_special == 0) {
-        rc = encode_batch_locked(t, text, doc_offsets, n_docs, TD_MODE_ENCODE, out_tokens, out_capacity, out_offsets, &ntok);
+        rc = encode_batch_locked(t, text, doc_offsets, n_docs, TD_MODE_ENCODE, out_tokens, out_capacity, out_offsets, &ntok, unit, out_starts);
         if (n_tokens) *n_tokens = ntok;
         return rc;
     }
@@ -1924,8 +2054,10 @@ int encode_special_locked(td_tokenizer* t, const uint8_t* text, const int64_t* d
         }
     }
     std::vector<int32_t> toks((size_t)std::max<int64_t>(seg_offs[(size_t)nseg], 1));
+    std::vector<int64_t> seg_starts(out_starts ? toks.size() : 0);  // (segment-relative, in bytes: shifted and converted below)
     if (ctx) t->gx_prefix_host = prefix.data();
-    rc = encode_batch_locked(t, seg_text.data(), seg_offs.data(), nseg, TD_MODE_ENCODE, toks.data(), (int64_t)toks.size(), toffs.data(), &ntok);
+    rc = encode_batch_locked(t, seg_text.data(), seg_offs.data(), nseg, TD_MODE_ENCODE, toks.data(), (int64_t)toks.size(), toffs.data(), &ntok,
+                             TD_UNIT_BYTES, out_starts ? seg_starts.data() : nullptr);
     t->gx_prefix_host = nullptr;
     if (rc) return rc;
     // 3. stitch: offsets first (they do not need the capacity), then the ids
@@ -1945,6 +2077,16 @@ int encode_special_locked(td_tokenizer* t, const uint8_t* text, const int64_t* d
         if (cnt) memcpy(out_tokens + k, toks.data() + toffs[(size_t)sg], (size_t)cnt * 4);
         k += cnt;
         if (seg_special[(size_t)sg] >= 0) out_tokens[k++] = seg_special[(size_t)sg];
+    }
+    if (out_starts) {  // the same stitching for the starts: a segment's are shifted by where it stands in its document (its context in front of it)
+        k = 0;
+        for (int64_t d = 0; d < n_docs; ++d)
+            for (int64_t sg = doc_seg[(size_t)d]; sg < doc_seg[(size_t)d + 1]; ++sg) {
+                const int64_t shift = starts[(size_t)sg] - (ctx ? prefix[(size_t)sg] : 0) - doc_offsets[d];
+                for (int64_t j = toffs[(size_t)sg]; j < toffs[(size_t)sg + 1]; ++j) out_starts[k++] = seg_starts[(size_t)j] + shift;
+                if (seg_special[(size_t)sg] >= 0) out_starts[k++] = ends[(size_t)sg] - doc_offsets[d];
+            }
+        if (unit == TD_UNIT_CHARS) return chars_by_rank_locked(t, text, doc_offsets, n_docs, out_offsets, out_starts, need);
     }
     return TD_OK;
 }
@@ -2063,6 +2205,72 @@ int td_encode_with_special_strs(td_tokenizer* t, const uint8_t* text, int64_t n_
                                              out_tokens, out_capacity, offs, n_tokens, &lo, &hi);
         if (rc == TD_OK && last_piece_token_len) *last_piece_token_len = last_piece_token_len_host(t, text, lo, hi);
         return rc;
+    });
+}
+
+int td_token_starts(td_tokenizer* t, const int32_t* tokens, int64_t n_tokens, const int64_t* tok_offsets, int64_t n_docs, int unit,
+                    int64_t* out_starts) {
+    if (!t || n_tokens < 0 || (n_tokens > 0 && (!tokens || !out_starts)) || !tok_offsets || n_docs < 0 ||
+        (unit != TD_UNIT_BYTES && unit != TD_UNIT_CHARS))
+        return TD_E_INVALID;
+    return locked(t, [&] {
+        int rc;
+        if ((rc = check_offsets(t, "tok_offsets", tok_offsets, n_docs, tokens))) return rc;
+        const int64_t total = tok_offsets[n_docs];
+        if (total > n_tokens) { t->err = "output capacity too small: " + std::to_string(total) + " starts needed"; return (int)TD_E_CAPACITY; }
+        if (total == 0) return (int)TD_OK;
+        if ((rc = ensure(t, t->dec_tokens, (size_t)total * 4))) return rc;
+        if ((rc = ensure(t, t->d_offsets, (size_t)(n_docs + 1) * 8))) return rc;
+        if ((rc = ensure(t, t->off_starts, (size_t)total * 8))) return rc;
+        if ((rc = own_streams(t))) return rc;
+        hipStream_t s = t->s_own;
+        if ((rc = order_before(t, s))) return rc;
+        HIP_TRY(t, hipMemcpyAsync(t->dec_tokens.p, tokens, (size_t)total * 4, hipMemcpyHostToDevice, s));
+        HIP_TRY(t, hipMemcpyAsync(t->d_offsets.p, tok_offsets, (size_t)(n_docs + 1) * 8, hipMemcpyHostToDevice, s));
+        if ((rc = token_starts_locked(t, t->dec_tokens.p, total, t->d_offsets.p, n_docs, unit, t->off_starts.p, s))) return rc;
+        if ((rc = device_status_locked(t, s, nullptr))) return rc;
+        return copy_wait(t, out_starts, t->off_starts.p, (size_t)total * 8, hipMemcpyDeviceToHost, s);
+    });
+}
+
+int td_token_starts_device(td_tokenizer* t, const void* d_tokens, int64_t n_tokens, const void* d_tok_offsets, int64_t n_docs, int unit,
+                           void* d_out_starts, void* hip_stream) {
+    if (!t || n_tokens < 0 || (n_tokens > 0 && (!d_tokens || !d_out_starts)) || !d_tok_offsets || n_docs < 0 ||
+        (unit != TD_UNIT_BYTES && unit != TD_UNIT_CHARS))
+        return TD_E_INVALID;
+    return locked(t, [&] {
+        return token_starts_locked(t, d_tokens, n_tokens, d_tok_offsets, n_docs, unit, d_out_starts, (hipStream_t)hip_stream);
+    });
+}
+
+int td_encode_batch_with_starts(td_tokenizer* t, const uint8_t* text, const int64_t* doc_offsets, int64_t n_docs, int mode,
+                                const uint8_t* allowed_bytes, const int64_t* allowed_offsets, int64_t n_allowed, int unit,
+                                int32_t* out_tokens, int64_t out_capacity, int64_t* out_offsets, int64_t* out_starts, int64_t* n_tokens) {
+    if (!t || !doc_offsets || n_docs < 0 || n_allowed < 0 || (n_allowed > 0 && (!allowed_bytes || !allowed_offsets)) || !out_offsets ||
+        out_capacity < 0 || (out_capacity > 0 && !out_starts) || (unit != TD_UNIT_BYTES && unit != TD_UNIT_CHARS) ||
+        (mode != TD_MODE_ENCODE && mode != TD_MODE_ORDINARY) || (mode == TD_MODE_ORDINARY && n_allowed > 0))
+        return TD_E_INVALID;
+    if (unit == TD_UNIT_CHARS && doc_offsets[n_docs] >= (1ll << 32))
+        return fail_unlocked(t, TD_E_INVALID, "td_encode_batch_with_starts: character starts need less than 4 GiB of text a call");
+    return locked(t, [&] {
+        if (n_allowed == 0)
+            return encode_batch_locked(t, text, doc_offsets, n_docs, mode, out_tokens, out_capacity, out_offsets, n_tokens, unit, out_starts);
+        return encode_special_locked(t, text, doc_offsets, n_docs, allowed_bytes, allowed_offsets, nullptr, n_allowed, out_tokens,
+                                     out_capacity, out_offsets, n_tokens, nullptr, nullptr, unit, out_starts);
+    });
+}
+
+int td_encode_device_with_starts(td_tokenizer* t, const void* d_text, int64_t n_bytes, const void* d_doc_offsets, int64_t n_docs, int mode,
+                                 int unit, void* d_out_tokens, int64_t out_capacity, void* d_out_offsets, void* d_out_starts,
+                                 void* hip_stream) {
+    if (!t || (unit != TD_UNIT_BYTES && unit != TD_UNIT_CHARS) || (n_bytes > 0 && out_capacity > 0 && !d_out_starts)) return TD_E_INVALID;
+    if (unit == TD_UNIT_CHARS && n_bytes >= (1ll << 32))
+        return fail_unlocked(t, TD_E_INVALID, "td_encode_device_with_starts: character starts need less than 4 GiB of text a call");
+    return locked(t, [&] {
+        const hipStream_t s = (hipStream_t)hip_stream;
+        int rc = encode_device_locked(t, d_text, n_bytes, d_doc_offsets, n_docs, mode, d_out_tokens, out_capacity, d_out_offsets, s);
+        if (rc) return rc;
+        return encode_starts_locked(t, d_text, n_bytes, d_doc_offsets, n_docs, d_out_tokens, out_capacity, d_out_offsets, unit, d_out_starts, s);
     });
 }
 

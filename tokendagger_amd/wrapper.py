@@ -21,6 +21,7 @@ _capi.load_library()  # (first: it makes the HIP runtime of this process the one
 from . import _tokendagger_core as _core  # noqa: E402
 
 MODE_ENCODE, MODE_ORDINARY = 0, 1
+_UNITS = {"bytes": 0, "chars": 1}  # TD_UNIT_BYTES, TD_UNIT_CHARS
 
 
 class TokenDaggerError(Exception):
@@ -212,6 +213,56 @@ class Tokenizer:
                                                      MODE_ORDINARY if ordinary else MODE_ENCODE)
         except Exception as e:
             raise TokenDaggerError(f"Encoding failed: {e}")
+
+    # ------------------------------------------------------------------ offsets ----------------
+    # The start of a token is where its text begins in its document: in "bytes", the offset of its first UTF-8 byte; in "chars",
+    # tiktoken's decode_with_offsets rule (code points; a token that begins inside a character points at that character), which
+    # for a str is the index into that str.  Computed on the GPU (include/tokendagger_hip.h, TD_UNIT_*); the end of a token in
+    # bytes is its start + len(decode_single_token_bytes(token)).
+    @staticmethod
+    def _unit(unit: str) -> int:
+        if unit not in _UNITS:
+            raise ValueError(f"unit must be 'bytes' or 'chars', not {unit!r}")
+        return _UNITS[unit]
+
+    def encode_with_offsets(
+        self,
+        text: str | bytes,
+        *,
+        allowed_special: Literal["all"] | AbstractSet[str] = set(),
+        disallowed_special: Literal["all"] | Collection[str] = set(),
+        unit: str | None = None,
+    ) -> tuple[list[int], list[int]]:
+        """encode() and the start of every token: chars by default for a str, bytes for bytes."""
+        is_str = isinstance(text, str)
+        u = self._unit(unit or ("chars" if is_str else "bytes"))
+        allowed, disallowed = self._special_sets(allowed_special, disallowed_special)
+        self._check_disallowed(text if is_str else bytes(text).decode("utf-8", "replace"), disallowed)
+        try:
+            return self._core_bpe.encode_with_starts(text if is_str else bytes(text), allowed, u)
+        except Exception as e:
+            raise TokenDaggerError(f"Encoding failed: {e}")
+
+    def encode_batch_to_numpy_with_offsets(self, text: np.ndarray | bytes, offsets: np.ndarray, *, ordinary: bool = False,
+                                           unit: str = "bytes"):
+        """encode_batch_to_numpy and the start of every token in its document: -> (int32 ids, int64 token offsets, int64 starts)."""
+        u = self._unit(unit)
+        buf = np.frombuffer(text, dtype=np.uint8) if isinstance(text, (bytes, bytearray)) else text
+        try:
+            return self._core_bpe.encode_batch_numpy_with_starts(buf, np.asarray(offsets, dtype=np.int64),
+                                                                 MODE_ORDINARY if ordinary else MODE_ENCODE, u)
+        except Exception as e:
+            raise TokenDaggerError(f"Encoding failed: {e}")
+
+    def decode_with_offsets(self, tokens: Sequence[int]) -> tuple[str, list[int]]:
+        """tiktoken's Encoding.decode_with_offsets: the text (decoded strictly) and the char offset of every token in it."""
+        ids = np.asarray(list(tokens), dtype=np.int32)
+        try:
+            data = self._core_bpe.decode_to_bytes(ids)
+            starts = self._core_bpe.token_starts(ids, _UNITS["chars"]).tolist()
+        except Exception as e:
+            raise TokenDaggerError(f"Decoding failed: {e}")
+        return data.decode("utf-8", errors="strict"), starts
 
     # ------------------------------------------------------------------ decoding ---------------
     def decode_bytes(self, tokens: Sequence[int]) -> bytes:
