@@ -230,6 +230,60 @@ int td_encode_device_with_starts(td_tokenizer* t, const void* d_text, int64_t n_
                                  int unit, void* d_out_tokens, int64_t out_capacity, void* d_out_offsets, void* d_out_starts,
                                  void* hip_stream);
 
+/* ---- training rows (td_rows.hip) -----------------------------------------------------------------------------------------
+ * Encoded documents -> rows of a fixed length S.  Input: ids[n_tokens] (int32) and tok_offsets[n_docs+1] (int64), what
+ * td_encode_batch / td_encode_device produce; L_d = tok_offsets[d+1] - tok_offsets[d].  b = (bos_id >= 0), e = (eos_id >= 0).
+ *
+ * TD_ROWS_CONCAT  every document becomes [BOS] ids... [EOS], n_d = b + L_d + e slots (an empty document without BOS and EOS: 0
+ *   slots), concatenated in document order into a stream of T = tok_offsets[n_docs] + n_docs * (b + e) slots; document d starts
+ *   at base_d = tok_offsets[d] + d * (b + e).  The stream is cut into rows of S: rows = ceil(T / S), the tail padded with pad_id;
+ *   with TD_ROWS_DROP_LAST rows = floor(T / S) and the partial row is dropped.  R = min(T, rows * S) slots are real.
+ *     positions[rows * S]  a slot's index inside its SEGMENT; segments are the pieces of [0, R) cut at every document start and
+ *                          every row start; pad slots are 0.
+ *     aux = cu_seqlens     the sorted segment boundaries 0 ... R without duplicates (n_seg + 1 entries, never a zero-length
+ *                          segment): the cu_seqlens of variable-length attention over the flattened [rows * S] batch.
+ * TD_ROWS_PAD  one row per document (rows = n_docs): [BOS] body [EOS] then pad_id, the body truncated to min(L_d, S - b - e)
+ *   ids (S < b + e: TD_E_INVALID), so a truncated document still ends with EOS (Hugging Face's truncation with special tokens).
+ *     positions            0 .. len - 1, pad slots 0.
+ *     aux = lengths        [n_docs] the real slots of every row (int32).
+ *   Not allowed with TD_ROWS_DROP_LAST.
+ * counts[4] (int64) = {rows, R (real slots), n_seg (PAD: rows with at least one slot), documents truncated (PAD)}.
+ * bos_id / eos_id: -1 for none, otherwise an id of the vocabulary, ordinary or special (else TD_E_BAD_TOKEN); pad_id: any int32.
+ * seq_len: 1 .. 2^31 - 1.  With cu_seqlens requested, rows_capacity * seq_len must stay below 2^31 (its entries are int32). */
+#define TD_ROWS_CONCAT 0
+#define TD_ROWS_PAD 1
+#define TD_ROWS_DROP_LAST 1 /* flags */
+typedef struct td_rows_spec {
+    int64_t layout;  /* TD_ROWS_CONCAT / TD_ROWS_PAD */
+    int64_t seq_len; /* S */
+    int64_t bos_id;  /* -1: none */
+    int64_t eos_id;  /* -1: none */
+    int64_t pad_id;
+    int64_t flags;   /* TD_ROWS_DROP_LAST (CONCAT only) */
+} td_rows_spec;
+
+/* Rows from DEVICE buffers, asynchronously on hip_stream.  d_out_ids has room for rows_capacity rows of S; d_positions (same
+ * size) and d_aux (CONCAT: cu_seqlens, room for n_docs + rows_capacity + 1 entries; PAD: lengths, n_docs entries) may be NULL;
+ * d_counts (4 int64) is required.  The host does not know T, so the kernels check the capacity: more rows than rows_capacity
+ * raise TD_E_CAPACITY with err_pos (td_device_status) = the rows needed and counts[0] = the same, and nothing is written into
+ * the outputs.  tok_offsets[n_docs] > n_tokens is TD_E_INVALID on the device too; tok_offsets must start at 0 and not decrease
+ * (the host form checks that; here no id outside [0, n_tokens) is read whatever they hold). */
+int td_make_rows_device(td_tokenizer* t, const void* d_ids, int64_t n_tokens, const void* d_tok_offsets, int64_t n_docs,
+                        const td_rows_spec* spec, void* d_out_ids, int64_t rows_capacity, void* d_positions, void* d_aux,
+                        void* d_counts, void* hip_stream);
+/* The same on host buffers, synchronously.  tok_offsets is checked like every host entry point's offsets.  The rows are known
+ * on the host: a capacity below them fails before any launch with TD_E_CAPACITY and counts[0] = the rows needed. */
+int td_make_rows(td_tokenizer* t, const int32_t* ids, int64_t n_tokens, const int64_t* tok_offsets, int64_t n_docs,
+                 const td_rows_spec* spec, int32_t* out_ids, int64_t rows_capacity, int32_t* out_positions, int32_t* out_aux,
+                 int64_t* counts);
+/* td_encode_batch (mode TD_MODE_ENCODE / TD_MODE_ORDINARY, no allowed special tokens) and td_make_rows in one call: the ids stay
+ * in the handle's workspace between the two.  Synchronous; it takes the copy-and-synchronise path at every size (not the
+ * one-launch, mid-size or pipelined forms of td_encode_batch).  Callers that need allowed specials encode first
+ * (td_encode_batch_with_special_strs) and call td_make_rows. */
+int td_encode_batch_rows(td_tokenizer* t, const uint8_t* text, const int64_t* doc_offsets, int64_t n_docs, int mode,
+                         const td_rows_spec* spec, int32_t* out_ids, int64_t rows_capacity, int32_t* out_positions, int32_t* out_aux,
+                         int64_t* counts);
+
 /* Options. */
 #define TD_OPT_LONG_POOL_BYTES 1 /* scratch for pieces longer than 64 bytes (default max(64 MiB, 2 x input)) */
 #define TD_OPT_PROFILE 2         /* 1: bracket the kernels of every td_encode_device call with HIP events on the

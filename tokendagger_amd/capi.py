@@ -21,6 +21,8 @@ TD_MODE_ORDINARY = 1
 TD_E_INVALID = 1
 TD_E_BAD_TOKEN = 8
 TD_UNIT_BYTES, TD_UNIT_CHARS = 0, 1
+TD_ROWS_CONCAT, TD_ROWS_PAD = 0, 1
+TD_ROWS_DROP_LAST = 1
 TD_INFO_N_PAIRS, TD_INFO_MERGE_CLOSED, TD_INFO_MAX_ID, TD_INFO_TILE_BYTES = 1, 2, 3, 4
 TD_INFO_WORKSPACE_BYTES, TD_INFO_N_SPECIAL, TD_INFO_LONG_PIECES, TD_INFO_FAR_PIECES = 5, 6, 7, 8
 TD_OPT_LONG_POOL_BYTES = 1
@@ -53,7 +55,7 @@ EXPORTS = [
     "td_encode_with_special_strs", "td_encode_batch_with_special_strs", "td_profile_read_ex", "td_profile_segment_name",
     "td_comm_unique_id", "td_comm_create", "td_comm_destroy", "td_comm_gather_counts", "td_comm_bases", "td_comm_gather_tokens",
     "td_comm_last_error", "td_encode_device_with_special", "td_token_starts", "td_token_starts_device", "td_encode_batch_with_starts",
-    "td_encode_device_with_starts",
+    "td_encode_device_with_starts", "td_make_rows_device", "td_make_rows", "td_encode_batch_rows",
 ]
 
 
@@ -110,6 +112,12 @@ def load_library():
     lib.td_encode_batch_with_starts.argtypes = [vp, vp, vp, i64, i32, vp, vp, i64, i32, vp, i64, vp, vp, ctypes.POINTER(i64)]
     lib.td_encode_device_with_starts.restype = i32
     lib.td_encode_device_with_starts.argtypes = [vp, vp, i64, vp, i64, i32, i32, vp, i64, vp, vp, vp]
+    lib.td_make_rows_device.restype = i32
+    lib.td_make_rows_device.argtypes = [vp, vp, i64, vp, i64, vp, vp, i64, vp, vp, vp, vp]
+    lib.td_make_rows.restype = i32
+    lib.td_make_rows.argtypes = [vp, vp, i64, vp, i64, vp, vp, i64, vp, vp, vp]
+    lib.td_encode_batch_rows.restype = i32
+    lib.td_encode_batch_rows.argtypes = [vp, vp, vp, i64, i32, vp, vp, i64, vp, vp, vp]
     lib.td_comm_unique_id.restype = i32
     lib.td_comm_unique_id.argtypes = [vp]
     lib.td_comm_create.restype = i32
@@ -198,6 +206,24 @@ def _pack(items: list[tuple[bytes, int]]):
         np.cumsum([len(b) for b, _ in items], out=offs[1:])
     blob = np.frombuffer(b"".join(b for b, _ in items) or b"\0", dtype=np.uint8).copy()
     return blob, offs, ranks
+
+
+class RowsSpec(ctypes.Structure):
+    """td_rows_spec (include/tokendagger_hip.h): -1 for no BOS / EOS."""
+    _fields_ = [("layout", ctypes.c_int64), ("seq_len", ctypes.c_int64), ("bos_id", ctypes.c_int64), ("eos_id", ctypes.c_int64),
+                ("pad_id", ctypes.c_int64), ("flags", ctypes.c_int64)]
+
+
+def rows_spec(seq_len: int, layout: int = TD_ROWS_CONCAT, bos: int = -1, eos: int = -1, pad: int = 0, drop_last: bool = False) -> RowsSpec:
+    return RowsSpec(layout, seq_len, bos, eos, pad, TD_ROWS_DROP_LAST if drop_last else 0)
+
+
+def rows_capacity_of(spec: RowsSpec, n_ids: int, n_docs: int) -> int:
+    """The rows td_make_rows writes for n_ids ids in n_docs documents."""
+    if spec.layout == TD_ROWS_PAD:
+        return n_docs
+    t = n_ids + n_docs * ((spec.bos_id >= 0) + (spec.eos_id >= 0))
+    return t // spec.seq_len if spec.flags & TD_ROWS_DROP_LAST else -(-t // spec.seq_len)
 
 
 def _as_u8(data) -> np.ndarray:
@@ -433,6 +459,65 @@ class HipTokenizer:
         self._check(self._lib.td_token_starts(self._h, t.ctypes.data if len(t) else None, n, o.ctypes.data, len(o) - 1, unit,
                                               out.ctypes.data))
         return out[:int(o[-1])]
+
+    # ---- training rows (TD_ROWS_*) ------------------------------------------------------------------
+    def make_rows(self, ids, tok_offsets, spec: RowsSpec, positions: bool = False, aux: bool = True, rows_capacity: int | None = None):
+        """td_make_rows -> (ids int32[rows, S], positions int32[rows, S] or None, aux or None, counts int64[4]).
+        aux: cu_seqlens (CONCAT, int32[n_seg + 1]) or lengths (PAD, int32[n_docs])."""
+        t = np.ascontiguousarray(ids, dtype=np.int32)
+        o = np.ascontiguousarray(tok_offsets, dtype=np.int64)
+        n_docs = len(o) - 1
+        rows = rows_capacity if rows_capacity is not None else rows_capacity_of(spec, int(o[-1]) if len(o) else 0, n_docs)
+        S = spec.seq_len
+        out = np.empty(max(rows * S, 1), dtype=np.int32)
+        pos = np.empty(max(rows * S, 1), dtype=np.int32) if positions else None
+        concat = spec.layout == TD_ROWS_CONCAT
+        ax = np.empty(max(n_docs + rows + 1 if concat else n_docs, 1), dtype=np.int32) if aux else None
+        counts = np.zeros(4, dtype=np.int64)
+        self._check(self._lib.td_make_rows(self._h, t.ctypes.data if len(t) else None, len(t), o.ctypes.data, n_docs, ctypes.byref(spec),
+                                           out.ctypes.data, rows, pos.ctypes.data if pos is not None else None,
+                                           ax.ctypes.data if ax is not None else None, counts.ctypes.data))
+        return self._rows_result(spec, out, pos, ax, counts, n_docs)
+
+    @staticmethod
+    def _rows_result(spec, out, pos, ax, counts, n_docs):
+        r, S = int(counts[0]), spec.seq_len
+        ids = out[:r * S].reshape(r, S).copy()
+        p = pos[:r * S].reshape(r, S).copy() if pos is not None else None
+        if ax is not None:
+            ax = ax[:int(counts[2]) + 1].copy() if spec.layout == TD_ROWS_CONCAT else ax[:n_docs].copy()
+        return ids, p, ax, counts
+
+    def make_rows_device(self, d_ids: int, n_tokens: int, d_tok_offsets: int, n_docs: int, spec: RowsSpec, d_out_ids: int,
+                         rows_capacity: int, d_positions: int = 0, d_aux: int = 0, d_counts: int = 0, stream: int = 0):
+        """td_make_rows_device: raw device pointers, asynchronous on `stream`; check with device_status(stream)."""
+        self._check(self._lib.td_make_rows_device(self._h, d_ids or None, n_tokens, d_tok_offsets, n_docs, ctypes.byref(spec), d_out_ids or None,
+                                                  rows_capacity, d_positions or None, d_aux or None, d_counts or None, stream or None))
+
+    def encode_batch_rows(self, text, doc_offsets, spec: RowsSpec, mode: int = TD_MODE_ENCODE, positions: bool = False, aux: bool = True,
+                          rows_capacity: int | None = None):
+        """td_encode_batch_rows: encode + td_make_rows in one call; same result tuple as make_rows.  The default capacity is
+        the most rows the text can need (one id per byte)."""
+        buf = _as_u8(text)
+        offs = np.ascontiguousarray(doc_offsets, dtype=np.int64)
+        n_docs = len(offs) - 1
+        rows = rows_capacity if rows_capacity is not None else rows_capacity_of(spec, int(offs[-1]) if len(offs) else 0, n_docs)
+        S = spec.seq_len
+        out = np.empty(max(rows * S, 1), dtype=np.int32)
+        pos = np.empty(max(rows * S, 1), dtype=np.int32) if positions else None
+        concat = spec.layout == TD_ROWS_CONCAT
+        ax = np.empty(max(n_docs + rows + 1 if concat else n_docs, 1), dtype=np.int32) if aux else None
+        counts = np.zeros(4, dtype=np.int64)
+        self._check(self._lib.td_encode_batch_rows(self._h, buf.ctypes.data if len(buf) else None, offs.ctypes.data, n_docs, mode,
+                                                   ctypes.byref(spec), out.ctypes.data, rows, pos.ctypes.data if pos is not None else None,
+                                                   ax.ctypes.data if ax is not None else None, counts.ctypes.data))
+        return self._rows_result(spec, out, pos, ax, counts, n_docs)
+
+    def device_status_pos(self, stream: int = 0) -> tuple[int, int]:
+        """td_device_status without raising: (code, err_pos)."""
+        pos = ctypes.c_int64(0)
+        rc = self._lib.td_device_status(self._h, stream or None, ctypes.byref(pos))
+        return int(rc), int(pos.value)
 
     def token_starts_device(self, d_tokens: int, n_tokens: int, d_tok_offsets: int, n_docs: int, d_out_starts: int, unit: int = TD_UNIT_BYTES,
                             stream: int = 0):

@@ -539,6 +539,76 @@ public:
         return starts;
     }
 
+    // ---- training rows (td_make_rows, td_encode_batch_rows) -------------------------------------------------------------------
+    // -> (ids int32[rows, S], positions int32[rows, S] or None, cu_seqlens (CONCAT) / lengths (PAD) int32 or None, counts int64[4])
+    static td_rows_spec rows_spec(int64_t seq_len, int layout, int64_t bos, int64_t eos, int64_t pad, bool drop_last) {
+        td_rows_spec sp{layout, seq_len, bos, eos, pad, drop_last ? TD_ROWS_DROP_LAST : 0};
+        return sp;
+    }
+    static int64_t rows_for(const td_rows_spec& sp, int64_t n_ids, int64_t n_docs) {
+        if (sp.layout == TD_ROWS_PAD) return n_docs;
+        if (sp.seq_len < 1) return 0;  // (the library rejects the spec)
+        const int64_t t = n_ids + n_docs * ((sp.bos_id >= 0) + (sp.eos_id >= 0));
+        return (sp.flags & TD_ROWS_DROP_LAST) ? t / sp.seq_len : (t + sp.seq_len - 1) / sp.seq_len;
+    }
+    template <class F>
+    py::tuple rows_call(const td_rows_spec& sp, int64_t rows_cap, int64_t n_docs, bool positions, bool aux, F&& call) {
+        const int64_t S = sp.seq_len > 0 ? sp.seq_len : 1, slots = std::max<int64_t>(rows_cap * S, 1);
+        const bool concat = sp.layout == TD_ROWS_CONCAT;
+        py::array_t<int32_t> ids(slots), pos(positions ? slots : 0), ax(aux ? std::max<int64_t>(concat ? n_docs + rows_cap + 1 : n_docs, 1) : 0);
+        py::array_t<int64_t> counts(4);
+        int rc;
+        {
+            int32_t* ip = ids.mutable_data();
+            int32_t* pp = positions ? pos.mutable_data() : nullptr;
+            int32_t* ap = aux ? ax.mutable_data() : nullptr;
+            int64_t* cp = counts.mutable_data();
+            py::gil_scoped_release rel;
+            rc = call(ip, pp, ap, cp);
+        }
+        if (rc != TD_OK) fail();
+        const int64_t rows = counts.data()[0];
+        ids.resize({(py::ssize_t)(rows * S)}, false);
+        py::object p = py::none(), a = py::none();
+        if (positions) {
+            pos.resize({(py::ssize_t)(rows * S)}, false);
+            p = pos.attr("reshape")(rows, S);
+        }
+        if (aux) {
+            ax.resize({(py::ssize_t)(concat ? counts.data()[2] + 1 : n_docs)}, false);
+            a = ax;
+        }
+        return py::make_tuple(ids.attr("reshape")(rows, S), p, a, counts);
+    }
+    py::tuple encode_batch_numpy_rows(py::array_t<uint8_t, py::array::c_style | py::array::forcecast> text,
+                                      py::array_t<int64_t, py::array::c_style | py::array::forcecast> offsets, int64_t seq_len, int layout,
+                                      int64_t bos, int64_t eos, int64_t pad, bool drop_last, bool positions, bool aux, int mode) {
+        const int64_t n_docs = (int64_t)offsets.size() - 1;
+        if (n_docs < 0) throw TiktokenError("offsets must have n_docs+1 entries");
+        if (offsets.data()[n_docs] > (int64_t)text.size()) throw TiktokenError("offsets exceed the text buffer");
+        const td_rows_spec sp = rows_spec(seq_len, layout, bos, eos, pad, drop_last);
+        const int64_t cap = rows_for(sp, offsets.data()[n_docs], n_docs);  // (at most one id per byte)
+        const uint8_t* tp = text.data();
+        const int64_t* op = offsets.data();
+        return rows_call(sp, cap, n_docs, positions, aux, [&](int32_t* ip, int32_t* pp, int32_t* ap, int64_t* cp) {
+            return td_encode_batch_rows(h_, tp, op, n_docs, mode, &sp, ip, cap, pp, ap, cp);
+        });
+    }
+    py::tuple ids_to_rows(py::array_t<int32_t, py::array::c_style | py::array::forcecast> ids,
+                          py::array_t<int64_t, py::array::c_style | py::array::forcecast> tok_offsets, int64_t seq_len, int layout, int64_t bos,
+                          int64_t eos, int64_t pad, bool drop_last, bool positions, bool aux) {
+        const int64_t n_docs = (int64_t)tok_offsets.size() - 1;
+        if (n_docs < 0) throw TiktokenError("tok_offsets must have n_docs+1 entries");
+        const td_rows_spec sp = rows_spec(seq_len, layout, bos, eos, pad, drop_last);
+        const int64_t n = (int64_t)ids.size();
+        const int64_t cap = rows_for(sp, std::min<int64_t>(tok_offsets.data()[n_docs], n), n_docs);
+        const int32_t* tp = ids.data();
+        const int64_t* op = tok_offsets.data();
+        return rows_call(sp, cap, n_docs, positions, aux, [&](int32_t* ip, int32_t* pp, int32_t* ap, int64_t* cp) {
+            return td_make_rows(h_, tp, n, op, n_docs, &sp, ip, cap, pp, ap, cp);
+        });
+    }
+
     // list[str] in, list[list[int]] out through ONE device batch (PackedTexts / IntCache above)
     py::list encode_batch(const py::sequence& texts, int mode) {
         PackedTexts in(texts);
@@ -694,6 +764,12 @@ PYBIND11_MODULE(_tokendagger_core, m) {
         .def("encode_batch_numpy_with_starts", &CoreBPE::encode_batch_numpy_with_starts, py::arg("text"), py::arg("offsets"),
              py::arg("mode") = TD_MODE_ENCODE, py::arg("unit") = TD_UNIT_BYTES)
         .def("token_starts", &CoreBPE::token_starts, py::arg("ids"), py::arg("unit"))
+        .def("encode_batch_numpy_rows", &CoreBPE::encode_batch_numpy_rows, py::arg("text"), py::arg("offsets"), py::arg("seq_len"),
+             py::arg("layout") = TD_ROWS_CONCAT, py::arg("bos") = -1, py::arg("eos") = -1, py::arg("pad") = 0, py::arg("drop_last") = false,
+             py::arg("positions") = false, py::arg("aux") = true, py::arg("mode") = TD_MODE_ENCODE)
+        .def("ids_to_rows", &CoreBPE::ids_to_rows, py::arg("ids"), py::arg("tok_offsets"), py::arg("seq_len"), py::arg("layout") = TD_ROWS_CONCAT,
+             py::arg("bos") = -1, py::arg("eos") = -1, py::arg("pad") = 0, py::arg("drop_last") = false, py::arg("positions") = false,
+             py::arg("aux") = true)
         .def("decode_batch", &CoreBPE::decode_batch, py::arg("docs"))
         .def("encode_batch_special", &CoreBPE::encode_batch_special, py::arg("texts"), py::arg("allowed_special"))
         .def("token_bytes", &CoreBPE::token_bytes, py::arg("id"))

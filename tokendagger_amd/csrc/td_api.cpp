@@ -18,6 +18,7 @@
 #include "../../include/tokendagger_hip.h"
 #include "td_kernels.h"
 #include "td_offsets.h"
+#include "td_rows.h"
 #include "td_regex.h"
 #include "td_tables.h"
 #include "td_vocab.h"
@@ -191,6 +192,9 @@ struct td_tokenizer {
     // per-token starts (td_offsets.hip): the per-id character table (td_create, shared like the other tables) and the scratch
     const uint32_t* d_ctab = nullptr;
     DevBuf off_heads, off_chunks, off_docs, off_rank, off_starts;
+    // training rows (td_rows.hip): the cu_seqlens scan's status words, the host entry points' outputs on the device
+    DevBuf rows_scan, rows_out, rows_pos, rows_aux, rows_counts;
+    bool rows_last = false;  // the last call launched the rows kernels (the unit of a TD_E_CAPACITY position)
     int64_t pool_bytes_opt = 0;
     bool profile = false;
     int stop_after = 0;
@@ -358,6 +362,7 @@ int fail_unlocked(td_tokenizer* t, int rc, const std::string& msg) {  // argumen
 // Stream order across calls: the per-handle workspace and control block are reused by every call, so a call on a
 // stream other than the previous call's waits for that call's last kernel (device-side wait, no host stall).
 int order_before(td_tokenizer* t, hipStream_t stream) {
+    t->rows_last = false;
     if (t->has_last && stream != t->last_stream) HIP_TRY(t, hipStreamWaitEvent(stream, t->last_done, 0));
     return TD_OK;
 }
@@ -727,7 +732,7 @@ int absorb_ctl(td_tokenizer* t, Ctl c, hipStream_t stream, int64_t* err_pos) {
                 t->err = "No value found for piece at byte offset " + std::to_string(c.err_pos) + ": byte sequence is not in the vocabulary";
                 break;
             case TD_E_CAPACITY:
-                t->err = "output capacity too small: " + std::to_string(c.err_pos) + " tokens needed";
+                t->err = "output capacity too small: " + std::to_string(c.err_pos) + (t->rows_last ? " rows needed" : " tokens needed");
                 break;
             case TD_E_BAD_TOKEN:
                 t->err = "Invalid token for decoding at index " + std::to_string(c.err_pos);
@@ -807,6 +812,116 @@ int encode_starts_locked(td_tokenizer* t, const void* d_text, int64_t n, const v
     HIP_TRY(t, launch_token_starts(a, stream));
     HIP_TRY(t, launch_encode_starts(a, stream));
     return order_after(t, stream);
+}
+
+// ---- training rows (td_rows.hip) -------------------------------------------------------------------------------------------
+// The checks of a spec that need no handle (nullptr: fine).  want_cu: CONCAT with cu_seqlens requested.
+const char* rows_spec_error(const td_rows_spec* sp, int64_t rows_capacity, bool want_cu) {
+    if (!sp) return "null td_rows_spec";
+    if (sp->layout != TD_ROWS_CONCAT && sp->layout != TD_ROWS_PAD) return "layout must be TD_ROWS_CONCAT or TD_ROWS_PAD";
+    if (sp->seq_len < 1 || sp->seq_len > INT32_MAX) return "seq_len must be in 1 .. 2^31 - 1";
+    if (sp->flags & ~(int64_t)TD_ROWS_DROP_LAST) return "unknown td_rows_spec flags";
+    if ((sp->flags & TD_ROWS_DROP_LAST) && sp->layout != TD_ROWS_CONCAT) return "TD_ROWS_DROP_LAST is for TD_ROWS_CONCAT only";
+    if (sp->pad_id < INT32_MIN || sp->pad_id > INT32_MAX) return "pad_id must be an int32";
+    const int64_t k = (sp->bos_id >= 0) + (sp->eos_id >= 0);
+    if (sp->layout == TD_ROWS_PAD && sp->seq_len < k) return "TD_ROWS_PAD needs seq_len >= the BOS and EOS slots";
+    if (rows_capacity < 0) return "rows_capacity must be >= 0";
+    if (rows_capacity > ((int64_t)1 << 62) / sp->seq_len) return "rows_capacity * seq_len is too large";
+    if (want_cu && rows_capacity * sp->seq_len >= ((int64_t)1 << 31))
+        return "cu_seqlens entries are int32: rows_capacity * seq_len must stay below 2^31";
+    return nullptr;
+}
+
+// bos_id / eos_id: -1, or an id of the vocabulary (ordinary or special)
+int rows_check_ids(td_tokenizer* t, const td_rows_spec* sp) {
+    for (const int64_t id : {sp->bos_id, sp->eos_id}) {
+        if (id == -1) continue;
+        if (id < 0 || id > INT32_MAX || td_token_bytes(t, (int32_t)id, nullptr, nullptr) != TD_OK)
+            return fail_unlocked(t, TD_E_BAD_TOKEN, "td_rows_spec: bos_id / eos_id " + std::to_string(id) + " is not in the vocabulary");
+    }
+    return TD_OK;
+}
+
+int64_t rows_needed(const td_rows_spec* sp, int64_t n_ids, int64_t n_docs) {
+    if (sp->layout == TD_ROWS_PAD) return n_docs;
+    const int64_t T = n_ids + n_docs * ((sp->bos_id >= 0) + (sp->eos_id >= 0));
+    return (sp->flags & TD_ROWS_DROP_LAST) ? T / sp->seq_len : (T + sp->seq_len - 1) / sp->seq_len;
+}
+
+int rows_funnel_src() {  // TD_ROWS_FUNNEL=1 in the environment: misaligned ids read as aligned int4 and a funnel (A/B)
+    static const int v = getenv("TD_ROWS_FUNNEL") && atoi(getenv("TD_ROWS_FUNNEL")) == 1;
+    return v;
+}
+
+int rows_launch_locked(td_tokenizer* t, const void* d_ids, int64_t n_tokens, const void* d_toff, int64_t n_docs, const td_rows_spec* sp,
+                       void* d_out, int64_t cap, void* d_pos, void* d_aux, void* d_counts, hipStream_t s) {
+    int rc;
+    if ((rc = order_before(t, s))) return rc;
+    t->rows_last = true;
+    RowsArgs a;
+    memset(&a, 0, sizeof a);
+    a.ids = (const int32_t*)d_ids;
+    a.n_tokens = n_tokens;
+    a.tok_off = (const int64_t*)d_toff;
+    a.n_docs = n_docs;
+    a.layout = (int)sp->layout;
+    a.drop_last = (sp->flags & TD_ROWS_DROP_LAST) ? 1 : 0;
+    a.S = sp->seq_len;
+    a.s_magic = ~0ull / (unsigned long long)sp->seq_len;
+    a.b = sp->bos_id >= 0;
+    a.e = sp->eos_id >= 0;
+    a.bos = a.b ? (int32_t)sp->bos_id : 0;
+    a.eos = a.e ? (int32_t)sp->eos_id : 0;
+    a.pad = (int32_t)sp->pad_id;
+    a.funnel_src = rows_funnel_src();
+    a.out = (int32_t*)d_out;
+    a.rows_cap = cap;
+    a.pos = (int32_t*)d_pos;
+    a.aux = (int32_t*)d_aux;
+    a.aux_cap = sp->layout == TD_ROWS_CONCAT ? n_docs + cap + 1 : n_docs;
+    a.counts = (long long*)d_counts;
+    if (d_aux && sp->layout == TD_ROWS_CONCAT) {
+        const size_t bytes = (size_t)rows_scan_words(n_docs) * 8;
+        if ((rc = ensure(t, t->rows_scan, bytes))) return rc;
+        a.scan = (unsigned long long*)t->rows_scan.p;
+        HIP_TRY(t, hipMemsetAsync(a.scan, 0, bytes, s));
+    }
+    HIP_TRY(t, hipMemsetAsync(d_counts, 0, 4 * sizeof(int64_t), s));
+    Ctl* ctl = (Ctl*)t->ctl.p;
+    a.err = &ctl->err;
+    a.err_pos = &ctl->err_pos;
+    HIP_TRY(t, launch_rows(a, s));
+    return order_after(t, s);
+}
+
+// Host entry points: rows (known on the host, checked against the capacity by the caller) from ids already on the device, into
+// the handle's buffers, then to the caller's.
+int rows_to_host(td_tokenizer* t, const void* d_ids, int64_t n_ids, const void* d_toff, int64_t n_docs, const td_rows_spec* sp, int64_t rows,
+                 int32_t* out_ids, int32_t* out_pos, int32_t* out_aux, int64_t* counts, hipStream_t s) {
+    int rc;
+    const bool concat = sp->layout == TD_ROWS_CONCAT;
+    const int64_t slots = rows * sp->seq_len, aux_n = concat ? n_docs + rows + 1 : n_docs;
+    if ((rc = ensure(t, t->rows_out, (size_t)std::max<int64_t>(slots, 1) * 4))) return rc;
+    if (out_pos && (rc = ensure(t, t->rows_pos, (size_t)std::max<int64_t>(slots, 1) * 4))) return rc;
+    if (out_aux && (rc = ensure(t, t->rows_aux, (size_t)std::max<int64_t>(aux_n, 1) * 4))) return rc;
+    if ((rc = ensure(t, t->rows_counts, 4 * sizeof(int64_t)))) return rc;
+    if ((rc = rows_launch_locked(t, d_ids, n_ids, d_toff, n_docs, sp, t->rows_out.p, rows, out_pos ? t->rows_pos.p : nullptr,
+                                 out_aux ? t->rows_aux.p : nullptr, t->rows_counts.p, s)))
+        return rc;
+    if ((rc = device_status_locked(t, s, nullptr))) return rc;
+    if ((rc = copy_wait(t, counts, t->rows_counts.p, 4 * sizeof(int64_t), hipMemcpyDeviceToHost, s))) return rc;
+    if ((rc = copy_wait(t, out_ids, t->rows_out.p, (size_t)slots * 4, hipMemcpyDeviceToHost, s))) return rc;
+    if (out_pos && (rc = copy_wait(t, out_pos, t->rows_pos.p, (size_t)slots * 4, hipMemcpyDeviceToHost, s))) return rc;
+    if (out_aux && (rc = copy_wait(t, out_aux, t->rows_aux.p, (size_t)(concat ? counts[2] + 1 : n_docs) * 4, hipMemcpyDeviceToHost, s)))
+        return rc;
+    return TD_OK;
+}
+
+int rows_capacity_fail(td_tokenizer* t, int64_t rows, int64_t* counts) {
+    counts[0] = rows;
+    counts[1] = counts[2] = counts[3] = 0;
+    t->err = "output capacity too small: " + std::to_string(rows) + " rows needed";
+    return TD_E_CAPACITY;
 }
 
 }  // namespace
@@ -985,7 +1100,8 @@ void td_destroy(td_tokenizer* t) {
         if (t->small_out) (void)hipHostFree(t->small_out);
         DevBuf* bufs[] = {&t->dd_table, &t->rest_mask, &t->coll_ctr, &t->gx_prefix, &t->tile_state, &t->slab, &t->docbits, &t->startbits, &t->slow_list, &t->tile_flag, &t->tile_carry, &t->stage, &t->stage2, &t->tile_count, &t->tile_extra, &t->miss_list, &t->flagged_list, &t->deferred_list, &t->gap_list, &t->gapbits, &t->gx_exit, &t->gx_state, &t->sp_bytes, &t->sp_off, &t->sp_len, &t->sp_id, &t->sp_parent, &t->sp_first2, &t->sp_hit, &t->sp_acc, &t->sp_cpos, &t->sp_clit, &t->sp_ccount, &t->tile_base, &t->doc_slot, &t->long_list,
                           &t->pool, &t->ctl, &t->tile_first_doc, &t->chunk_pref, &t->h2d_text, &t->h2d_offs, &t->d_tokens, &t->d_offsets, &t->dec_tokens,
-                          &t->dec_off, &t->dec_out, &t->off_heads, &t->off_chunks, &t->off_docs, &t->off_rank, &t->off_starts};
+                          &t->dec_off, &t->dec_out, &t->off_heads, &t->off_chunks, &t->off_docs, &t->off_rank, &t->off_starts, &t->rows_scan, &t->rows_out, &t->rows_pos,
+                          &t->rows_aux, &t->rows_counts};
         for (DevBuf* b : bufs)
             if (b->p) (void)hipFree(b->p);
     }
@@ -2271,6 +2387,87 @@ int td_encode_device_with_starts(td_tokenizer* t, const void* d_text, int64_t n_
         int rc = encode_device_locked(t, d_text, n_bytes, d_doc_offsets, n_docs, mode, d_out_tokens, out_capacity, d_out_offsets, s);
         if (rc) return rc;
         return encode_starts_locked(t, d_text, n_bytes, d_doc_offsets, n_docs, d_out_tokens, out_capacity, d_out_offsets, unit, d_out_starts, s);
+    });
+}
+
+int td_make_rows_device(td_tokenizer* t, const void* d_ids, int64_t n_tokens, const void* d_tok_offsets, int64_t n_docs,
+                        const td_rows_spec* spec, void* d_out_ids, int64_t rows_capacity, void* d_positions, void* d_aux,
+                        void* d_counts, void* hip_stream) {
+    if (!t || !spec || n_tokens < 0 || n_docs < 0 || !d_tok_offsets || (n_tokens > 0 && !d_ids) || !d_counts ||
+        (rows_capacity > 0 && !d_out_ids))
+        return TD_E_INVALID;
+    if (const char* m = rows_spec_error(spec, rows_capacity, spec->layout == TD_ROWS_CONCAT && d_aux))
+        return fail_unlocked(t, TD_E_INVALID, std::string("td_make_rows_device: ") + m);
+    int rc;
+    if ((rc = rows_check_ids(t, spec))) return rc;
+    return locked(t, [&] {
+        return rows_launch_locked(t, d_ids, n_tokens, d_tok_offsets, n_docs, spec, d_out_ids, rows_capacity, d_positions, d_aux, d_counts,
+                                  (hipStream_t)hip_stream);
+    });
+}
+
+int td_make_rows(td_tokenizer* t, const int32_t* ids, int64_t n_tokens, const int64_t* tok_offsets, int64_t n_docs,
+                 const td_rows_spec* spec, int32_t* out_ids, int64_t rows_capacity, int32_t* out_positions, int32_t* out_aux,
+                 int64_t* counts) {
+    if (!t || !spec || n_tokens < 0 || n_docs < 0 || !tok_offsets || !counts || (rows_capacity > 0 && !out_ids)) return TD_E_INVALID;
+    if (const char* m = rows_spec_error(spec, rows_capacity, spec->layout == TD_ROWS_CONCAT && out_aux))
+        return fail_unlocked(t, TD_E_INVALID, std::string("td_make_rows: ") + m);
+    int rc;
+    if ((rc = rows_check_ids(t, spec))) return rc;
+    return locked(t, [&] {
+        int rc2;
+        if ((rc2 = check_offsets(t, "tok_offsets", tok_offsets, n_docs, ids))) return rc2;
+        const int64_t total = tok_offsets[n_docs];
+        if (total > n_tokens) { t->err = "tok_offsets[n_docs] exceeds n_tokens"; return (int)TD_E_INVALID; }
+        const int64_t rows = rows_needed(spec, total, n_docs);
+        if (rows > rows_capacity) return rows_capacity_fail(t, rows, counts);
+        if ((rc2 = ensure(t, t->dec_tokens, (size_t)std::max<int64_t>(total, 1) * 4))) return rc2;
+        if ((rc2 = ensure(t, t->d_offsets, (size_t)(n_docs + 1) * 8))) return rc2;
+        if ((rc2 = own_streams(t))) return rc2;
+        hipStream_t s = t->s_own;
+        if ((rc2 = order_before(t, s))) return rc2;
+        if (total > 0) HIP_TRY(t, hipMemcpyAsync(t->dec_tokens.p, ids, (size_t)total * 4, hipMemcpyHostToDevice, s));
+        HIP_TRY(t, hipMemcpyAsync(t->d_offsets.p, tok_offsets, (size_t)(n_docs + 1) * 8, hipMemcpyHostToDevice, s));
+        return rows_to_host(t, t->dec_tokens.p, total, t->d_offsets.p, n_docs, spec, rows, out_ids, out_positions, out_aux, counts, s);
+    });
+}
+
+int td_encode_batch_rows(td_tokenizer* t, const uint8_t* text, const int64_t* doc_offsets, int64_t n_docs, int mode,
+                         const td_rows_spec* spec, int32_t* out_ids, int64_t rows_capacity, int32_t* out_positions, int32_t* out_aux,
+                         int64_t* counts) {
+    if (!t || !spec || !doc_offsets || n_docs < 0 || !counts || (rows_capacity > 0 && !out_ids) ||
+        (mode != TD_MODE_ENCODE && mode != TD_MODE_ORDINARY))
+        return TD_E_INVALID;
+    if (const char* m = rows_spec_error(spec, rows_capacity, spec->layout == TD_ROWS_CONCAT && out_aux))
+        return fail_unlocked(t, TD_E_INVALID, std::string("td_encode_batch_rows: ") + m);
+    int rc;
+    if ((rc = rows_check_ids(t, spec))) return rc;
+    return locked(t, [&] {
+        int rc2;
+        if ((rc2 = check_offsets(t, "doc_offsets", doc_offsets, n_docs, text))) return rc2;
+        const int64_t n = doc_offsets[n_docs];
+        const int64_t dev_cap = std::max<int64_t>(n, 1);  // (at most one id per byte)
+        if ((rc2 = ensure(t, t->h2d_text, (size_t)n + 64))) return rc2;
+        if ((rc2 = ensure(t, t->h2d_offs, (size_t)(n_docs + 1) * 8))) return rc2;
+        if ((rc2 = ensure(t, t->d_offsets, (size_t)(n_docs + 1) * 8))) return rc2;
+        if ((rc2 = ensure(t, t->d_tokens, (size_t)dev_cap * 4))) return rc2;
+        if ((rc2 = own_streams(t))) return rc2;
+        hipStream_t s = t->s_own;
+        if ((rc2 = order_before(t, s))) return rc2;
+        if (n > 0) {
+            HIP_TRY(t, hipMemcpyAsync(t->h2d_text.p, text, (size_t)n, hipMemcpyHostToDevice, s));
+            HIP_TRY(t, hipMemcpyAsync(t->h2d_offs.p, doc_offsets, (size_t)(n_docs + 1) * 8, hipMemcpyHostToDevice, s));
+            if ((rc2 = encode_device_locked(t, t->h2d_text.p, n, t->h2d_offs.p, n_docs, mode, t->d_tokens.p, dev_cap, t->d_offsets.p, s)))
+                return rc2;
+        } else {  // (nothing but empty documents: no encode)
+            HIP_TRY(t, hipMemsetAsync(t->d_offsets.p, 0, (size_t)(n_docs + 1) * 8, s));
+        }
+        if ((rc2 = device_status_locked(t, s, nullptr))) return rc2;  // (the encode's errors as such, before the rows read its ids)
+        int64_t total = 0;
+        if ((rc2 = copy_wait(t, &total, (const int64_t*)t->d_offsets.p + n_docs, 8, hipMemcpyDeviceToHost, s))) return rc2;
+        const int64_t rows = rows_needed(spec, total, n_docs);
+        if (rows > rows_capacity) return rows_capacity_fail(t, rows, counts);
+        return rows_to_host(t, t->d_tokens.p, dev_cap, t->d_offsets.p, n_docs, spec, rows, out_ids, out_positions, out_aux, counts, s);
     });
 }
 

@@ -11,7 +11,7 @@ from __future__ import annotations
 
 import json
 from pathlib import Path
-from typing import AbstractSet, Collection, Literal, Sequence
+from typing import AbstractSet, Collection, Literal, NamedTuple, Sequence
 
 import numpy as np
 
@@ -22,6 +22,16 @@ from . import _tokendagger_core as _core  # noqa: E402
 
 MODE_ENCODE, MODE_ORDINARY = 0, 1
 _UNITS = {"bytes": 0, "chars": 1}  # TD_UNIT_BYTES, TD_UNIT_CHARS
+_LAYOUTS = {"concat": 0, "pad": 1}  # TD_ROWS_CONCAT, TD_ROWS_PAD
+
+
+class Rows(NamedTuple):
+    """Training rows (Tokenizer.encode_batch_to_rows / ids_to_rows; the contract: include/tokendagger_hip.h, td_make_rows)."""
+    ids: np.ndarray                 # int32 [rows, seq_len]
+    positions: np.ndarray | None    # int32 [rows, seq_len]: the index inside the segment (concat) / row (pad); pad slots 0
+    cu_seqlens: np.ndarray | None   # int32 [n_seg + 1]: "concat" segment boundaries 0 .. real slots
+    lengths: np.ndarray | None      # int32 [n_docs]: "pad" real slots of every row
+    counts: np.ndarray              # int64 [4]: rows, real slots, segments, truncated documents
 
 
 class TokenDaggerError(Exception):
@@ -263,6 +273,55 @@ class Tokenizer:
         except Exception as e:
             raise TokenDaggerError(f"Decoding failed: {e}")
         return data.decode("utf-8", errors="strict"), starts
+
+    # ------------------------------------------------------------------ training rows ----------
+    # Documents -> rows of seq_len ids on the GPU: "concat" packs [BOS] ids [EOS] of every document into one stream cut into rows
+    # (cu_seqlens and positions restart at every document and row start), "pad" gives every document a row of its own,
+    # truncated to seq_len with its EOS kept.  bos / eos: an id or a special-token string; pad=None: eos, and an error if
+    # padding is needed and there is no eos.
+    def _rows_args(self, seq_len: int, layout: str, bos, eos, pad):
+        if layout not in _LAYOUTS:
+            raise ValueError(f"layout must be 'concat' or 'pad', not {layout!r}")
+
+        def tid(x):
+            if x is None:
+                return -1
+            if isinstance(x, (str, bytes)):
+                return self.encode_single_token(x)
+            return int(x)
+        b, e = tid(bos), tid(eos)
+        return _LAYOUTS[layout], b, e, (int(pad) if pad is not None else (e if e >= 0 else 0)), pad is None and e < 0
+
+    @staticmethod
+    def _rows(r, layout: int, seq_len: int, no_pad: bool) -> Rows:
+        ids, pos, aux, counts = r
+        if no_pad and int(counts[1]) < int(counts[0]) * seq_len:
+            raise ValueError("the rows need padding: pass pad=, or eos= to pad with it")
+        return Rows(ids, pos, aux if layout == 0 else None, aux if layout == 1 else None, counts)
+
+    def encode_batch_to_rows(self, text: np.ndarray | bytes, offsets: np.ndarray, seq_len: int, *, layout: str = "concat", bos=None,
+                             eos=None, pad=None, drop_last: bool = False, positions: bool = False, cu_seqlens: bool = True,
+                             ordinary: bool = False) -> Rows:
+        """encode_batch_to_numpy straight into training rows (one call; the ids never leave the device)."""
+        lay, b, e, p, no_pad = self._rows_args(seq_len, layout, bos, eos, pad)
+        buf = np.frombuffer(text, dtype=np.uint8) if isinstance(text, (bytes, bytearray)) else text
+        try:
+            r = self._core_bpe.encode_batch_numpy_rows(buf, np.asarray(offsets, dtype=np.int64), seq_len, lay, b, e, p, drop_last, positions,
+                                                       cu_seqlens or lay == 1, MODE_ORDINARY if ordinary else MODE_ENCODE)
+        except Exception as ex:
+            raise TokenDaggerError(f"Encoding failed: {ex}")
+        return self._rows(r, lay, seq_len, no_pad)
+
+    def ids_to_rows(self, ids: np.ndarray, tok_offsets: np.ndarray, seq_len: int, *, layout: str = "concat", bos=None, eos=None, pad=None,
+                    drop_last: bool = False, positions: bool = False, cu_seqlens: bool = True) -> Rows:
+        """Rows from ids already encoded (int32 ids + int64 per-document token offsets, what encode_batch_to_numpy returns)."""
+        lay, b, e, p, no_pad = self._rows_args(seq_len, layout, bos, eos, pad)
+        try:
+            r = self._core_bpe.ids_to_rows(np.asarray(ids, dtype=np.int32), np.asarray(tok_offsets, dtype=np.int64), seq_len, lay, b, e, p,
+                                           drop_last, positions, cu_seqlens or lay == 1)
+        except Exception as ex:
+            raise TokenDaggerError(f"Making rows failed: {ex}")
+        return self._rows(r, lay, seq_len, no_pad)
 
     # ------------------------------------------------------------------ decoding ---------------
     def decode_bytes(self, tokens: Sequence[int]) -> bytes:
