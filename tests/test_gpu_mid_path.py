@@ -81,3 +81,31 @@ def test_mid_size_errors_and_capacity():
         assert np.array_equal(ids, ids2)
     finally:
         tok.close()
+
+
+def test_closed_handles_give_their_device_memory_back():
+    """td_destroy frees every buffer a handle grew: a handle that took the mid path, the one-launch path and the small decode gives all
+    its device memory back when it is closed (the mid path's device staging buffer, ~4 MiB for a 3.5 MiB call, once outlived it)."""
+    import torch
+    pat, mr, special = H.llama4()
+    mid, mid_offs = td_corpus.english(7 << 19, seed=41)  # 3.5 MiB: the mid path
+    small = b"Hello, world! It's a small call. " * 20    # under 4 KiB: the one-launch path
+    small_offs = np.asarray([0, len(small)], dtype=np.int64)
+
+    def one_handle():
+        tok = capi.HipTokenizer(pat, mr, special, device=0)
+        try:
+            ids, offs = tok.encode_batch(mid.tobytes(), mid_offs)
+            assert offs[-1] == len(ids) > 0
+            sids, _ = tok.encode_batch(small, small_offs)
+            assert small.startswith(tok.decode_bytes(sids[:8]))
+        finally:
+            tok.close()
+
+    one_handle()  # (warm-up: the runtime's own first allocations)
+    free0 = torch.cuda.mem_get_info(0)[0]
+    rounds, limit = 16, 16 << 20  # (a leak of the staging buffer: 16 x ~4 MiB, four times the limit)
+    for _ in range(rounds):
+        one_handle()
+    lost = free0 - torch.cuda.mem_get_info(0)[0]
+    assert lost < limit, f"{lost / 2**20:.1f} MiB of device memory not given back after {rounds} handles were closed"

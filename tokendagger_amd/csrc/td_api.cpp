@@ -61,10 +61,53 @@ struct DeviceGuard {
         }                                                                                     \
     } while (0)
 
-struct DevBuf {
+// Owners of the handle's HIP resources: each releases what it holds when it is destroyed or assigned another (move-only).
+// A handle's members are therefore freed by `delete`; td_destroy makes that safe (see there).
+template <hipError_t (*Free)(void*)>
+struct Buf {  // device (DevBuf) or pinned host (PinnedBuf) memory of `cap` bytes
     void* p = nullptr;
     size_t cap = 0;
+    Buf() = default;
+    Buf(Buf&& o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
+    Buf& operator=(Buf&& o) noexcept { std::swap(p, o.p); std::swap(cap, o.cap); return *this; }  // (o frees the old one)
+    ~Buf() { if (p) (void)Free(p); }
 };
+using DevBuf = Buf<hipFree>;
+using PinnedBuf = Buf<hipHostFree>;
+
+template <class T, hipError_t (*Destroy)(T)>
+struct Owned {  // a stream, an event or an executable graph
+    T h = nullptr;
+    Owned() = default;
+    explicit Owned(T x) : h(x) {}
+    Owned(Owned&& o) noexcept : h(o.h) { o.h = nullptr; }
+    Owned& operator=(Owned&& o) noexcept { std::swap(h, o.h); return *this; }
+    ~Owned() { if (h) (void)Destroy(h); }
+    operator T() const { return h; }
+};
+using Stream = Owned<hipStream_t, hipStreamDestroy>;
+using Event = Owned<hipEvent_t, hipEventDestroy>;
+using GraphExec = Owned<hipGraphExec_t, hipGraphExecDestroy>;
+
+// (each changes its owner only when it succeeds)
+hipError_t make_stream(Stream& s) {
+    hipStream_t h = nullptr;
+    const hipError_t e = hipStreamCreateWithFlags(&h, hipStreamNonBlocking);
+    if (e == hipSuccess) s = Stream(h);
+    return e;
+}
+hipError_t make_event(Event& ev) {
+    hipEvent_t h = nullptr;
+    const hipError_t e = hipEventCreateWithFlags(&h, hipEventDisableTiming);
+    if (e == hipSuccess) ev = Event(h);
+    return e;
+}
+hipError_t make_pinned(PinnedBuf& b, size_t bytes) {
+    void* p = nullptr;
+    const hipError_t e = hipHostMalloc(&p, bytes, hipHostMallocDefault);
+    if (e == hipSuccess) { PinnedBuf n; n.p = p; n.cap = bytes; b = std::move(n); }
+    return e;
+}
 
 }  // namespace
 
@@ -174,6 +217,56 @@ struct SharedTables {
     }
 };
 
+namespace {
+
+// The tunables: td_create reads them from the environment (from_env), td_set_option changes most of them, td_clone copies them all.
+struct Options {
+    bool fused = true;            // pre-tokenizer and lookup in one pass over the text (TD_OPT_FUSED; TD_FUSED=0 turns it off)
+    bool graphs = false;          // the last step as a hipGraph (encode_device_locked): opt-in (TD_OPT_GRAPH, TD_GRAPH=1)
+    bool direct = false;          // the fused loop places a tile's ids itself when their output base is known in time (TD_OPT_DIRECT; TD_DIRECT)
+    bool pack_split = true;       // td_pack_plain + td_pack_rest instead of td_pack_tokens (TD_OPT_PACK_SPLIT; TD_PACK_SPLIT=0 turns it off)
+    bool dedupe = true;           // a missed piece whose bytes another one of the call has is merged once (TD_OPT_DEDUPE; TD_DEDUPE=0 turns it off)
+    bool overlap = true;          // TD_OPT_OVERLAP (TD_OVERLAP=0 turns it off)
+    bool mid_enabled = true;      // (TD_MID_PATH=0: the copies-and-synchronise path of rounds 1-5, A/B)
+    bool small_enabled = true;    // TD_OPT_SMALL_PATH
+    bool small_resident = false;  // (TD_SMALL_RESIDENT=1.  Built for VERDICT r5 item 5a, measured, OFF: 14.1 us against 13.6 for a one-byte call —
+                                  // what a small call costs is the body's PCIe round trips and barriers, not the launch; tests/test_gpu_small_resident.py keeps it right)
+    unsigned long long small_idle_ticks = 20000;  // (TD_SMALL_IDLE_US, default 200 us: 100 MHz ticks the resident kernel waits for the next request)
+    int sparse_opt = -1;          // TD_OPT_SPARSE / TD_SPARSE: 1 = always the sparse sequence, 0 = never, -1 = by the last counters
+    uint32_t gp_coop_min = 16384; // TD_OPT_GIANT_COOP_MIN (TD_GP_COOP_MIN): pieces above this many bytes get all workgroups of td_giant_pieces
+    uint32_t dd_replicas = 4;     // (TD_DD_REPLICAS, tuning: a power of two)
+    uint32_t dd_minlen = 2;       // (TD_DD_MINLEN, tuning: pieces below this many bytes are merged without a look at the table)
+    uint32_t dd_entries_opt = 0;  // (TD_DD_ENTRIES=<power of two>, tests: seats of the table of distinct missed pieces)
+    int coll_shrink = 1;          // (TD_COLL_SHRINK=<k>, tests: td_collect_misses' lists 1/k of their size)
+    bool device_specials = true;  // host-buffer batches of a MiB and more search on the device (TD_OPT_DEVICE_SPECIALS)
+    int64_t pool_bytes_opt = 0;   // TD_OPT_LONG_POOL_BYTES
+    int64_t pipe_chunk_bytes = 64ll << 20;  // TD_OPT_PIPE_CHUNK_BYTES (a GiB of English host to host: 16 MiB chunks 33 GB/s, 32 MiB 39, 64 MiB 40.5, profiles/r5_bench/e2e_sweep.txt)
+    int pipe_threads = 16;        // TD_OPT_PIPE_THREADS
+    static Options from_env();
+};
+
+Options Options::from_env() {
+    Options o;
+    if (const char* e = getenv("TD_FUSED")) o.fused = atoi(e) != 0;
+    if (const char* e = getenv("TD_GRAPH")) o.graphs = atoi(e) != 0;
+    if (const char* e = getenv("TD_DIRECT")) o.direct = atoi(e) != 0;
+    if (const char* e = getenv("TD_PACK_SPLIT")) o.pack_split = atoi(e) != 0;
+    if (const char* e = getenv("TD_DEDUPE")) o.dedupe = atoi(e) != 0;
+    if (const char* e = getenv("TD_OVERLAP")) o.overlap = atoi(e) != 0;
+    if (const char* e = getenv("TD_MID_PATH")) o.mid_enabled = atoi(e) != 0;
+    if (const char* e = getenv("TD_SMALL_RESIDENT")) o.small_resident = atoi(e) != 0;
+    if (const char* e = getenv("TD_SMALL_IDLE_US")) { const long v = atol(e); if (v >= 1 && v <= 1000000) o.small_idle_ticks = (unsigned long long)v * 100ull; }
+    if (const char* e = getenv("TD_SPARSE")) { const int v = atoi(e); if (v >= -1 && v <= 1) o.sparse_opt = v; }
+    if (const char* e = getenv("TD_GP_COOP_MIN")) { if (atol(e) >= 1024) o.gp_coop_min = (uint32_t)std::min<long>(atol(e), 0x7FFFFFFF); }
+    if (const char* e = getenv("TD_DD_REPLICAS")) { const int v = atoi(e); if (v >= 1 && v <= 16 && !(v & (v - 1))) o.dd_replicas = (uint32_t)v; }
+    if (const char* e = getenv("TD_DD_MINLEN")) o.dd_minlen = (uint32_t)std::max(2, atoi(e));
+    if (const char* e = getenv("TD_DD_ENTRIES")) { const long v = atol(e); if (v >= 2 && v <= (1l << 24) && !(v & (v - 1))) o.dd_entries_opt = (uint32_t)v; }
+    if (const char* e = getenv("TD_COLL_SHRINK")) o.coll_shrink = std::max(1, atoi(e));
+    return o;
+}
+
+}  // namespace
+
 struct td_tokenizer {
     std::shared_ptr<SharedTables> shared;
     HostTables& H;                           // = shared->H
@@ -185,6 +278,9 @@ struct td_tokenizer {
         : shared(std::move(s)), H(shared->H), table_allocs(shared->table_allocs) {}
     std::string err;
     std::mutex mu;
+    Options opt;
+    bool profile = false;   // (TD_OPT_PROFILE; neither it nor stop_after is handed on by td_clone)
+    int stop_after = 0;
     // workspace (grown on demand)
     DevBuf dd_table, rest_mask, coll_ctr, tile_state, slab, docbits, startbits, slow_list, tile_flag, tile_carry, stage, stage2, tile_count, tile_extra, miss_list, flagged_list, deferred_list, gap_list, gapbits, gx_exit, gx_state, tile_base, doc_slot, long_list, pool, ctl, tile_first_doc, chunk_pref;
     DevBuf h2d_text, h2d_offs, d_tokens, d_offsets;  // host-API staging
@@ -195,24 +291,18 @@ struct td_tokenizer {
     // training rows (td_rows.hip): the cu_seqlens scan's status words, the host entry points' outputs on the device
     DevBuf rows_scan, rows_out, rows_pos, rows_aux, rows_counts;
     bool rows_last = false;  // the last call launched the rows kernels (the unit of a TD_E_CAPACITY position)
-    int64_t pool_bytes_opt = 0;
-    bool profile = false;
-    int stop_after = 0;
     // The library never touches the legacy (null) stream on its own: a legacy-stream operation is illegal while ANY thread of
     // the process captures a blocking stream, and synchronises with every blocking stream of every other thread.  Copies the
     // host waits for, table uploads and the host-buffer entry points run on `s_own` (non-blocking, private to the handle);
     // small results come back through `h_ctl` (pinned).
-    hipStream_t s_own = nullptr;
-    hipStream_t s_aux = nullptr;       // the long pieces beside the short ones (LaunchAux, td_kernels.h); with its two events
-    hipEvent_t e_fork = nullptr, e_join = nullptr;
-    bool overlap = true;               // TD_OPT_OVERLAP (TD_OVERLAP=0 at td_create time turns it off)
-    uint32_t gp_coop_min = 16384;      // TD_OPT_GIANT_COOP_MIN (TD_GP_COOP_MIN at td_create time): pieces above this many bytes get all workgroups of td_giant_pieces
-    hipStream_t s_cap = nullptr;       // hipGraph capture only (non-blocking: the CALLER's stream is never put into capture)
-    void* h_ctl = nullptr;             // pinned, 256 B: the control block / an 8-byte total on their way to the host
-    // the last step as a hipGraph (encode_device_locked): opt-in (TD_OPT_GRAPH, TD_GRAPH=1)
-    bool graphs = false;
+    Stream s_own;
+    Stream s_aux;                      // the long pieces beside the short ones (LaunchAux, td_kernels.h); with its two events
+    Event e_fork, e_join;
+    Stream s_cap;                      // hipGraph capture only (non-blocking: the CALLER's stream is never put into capture)
+    PinnedBuf h_ctl;                   // 256 B: the control block / an 8-byte total on their way to the host
+    // the last step as a hipGraph (encode_device_locked): opt-in (Options::graphs)
     int graph_failures = 0;
-    hipGraphExec_t graph_exec = nullptr;
+    GraphExec graph_exec;
     EncodeArgs graph_key, last_key;
     hipStream_t graph_stream = nullptr, last_key_stream = nullptr;
     bool has_last_key = false;
@@ -220,90 +310,69 @@ struct td_tokenizer {
     std::vector<int32_t> sp_key;     // the allowed ids it was built for (sorted, unique)
     DevBuf sp_bytes, sp_off, sp_len, sp_id, sp_parent, sp_first2, sp_hit, sp_acc, sp_cpos, sp_clit, sp_ccount;
     uint32_t sp_n = 0, sp_maxlen = 0;
-    bool device_specials = true;     // host-buffer batches of a MiB and more search on the device (TD_OPT_DEVICE_SPECIALS)
     bool sp_active = false;          // this call cuts allowed specials (set around encode_device_locked)
-    uint32_t dd_replicas = 4;     // (TD_DD_REPLICAS at td_create time, tuning: a power of two)
-    uint32_t dd_minlen = 2;       // (TD_DD_MINLEN at td_create time, tuning: pieces below this many bytes are merged without a look at the table)
-    uint32_t dd_entries_opt = 0;  // (TD_DD_ENTRIES=<power of two> at td_create time, tests: seats of the table of distinct missed pieces)
-    bool dedupe = true;       // a missed piece whose bytes another one of the call has is merged once (TD_OPT_DEDUPE; TD_DEDUPE=0 at td_create time turns it off)
-    bool pack_split = true;   // td_pack_plain + td_pack_rest instead of td_pack_tokens (TD_OPT_PACK_SPLIT; TD_PACK_SPLIT=0 at td_create time turns it off)
-    int coll_shrink = 1;      // (TD_COLL_SHRINK=<k> at td_create time, tests: td_collect_misses' lists 1/k of their size)
     // generic patterns with left-context assertions behind special cuts: per document of the NEXT host batch, the bytes at its
     // start that are context only (set around encode_batch_locked by encode_special_locked)
     const uint8_t* gx_prefix_host = nullptr;
     DevBuf gx_prefix;
     const uint8_t* gx_prefix_dev = nullptr;
-    bool direct = false; // the fused loop places a tile's ids itself when their output base is known in time (TD_OPT_DIRECT; TD_DIRECT=0 turns it off)
-    bool fused = true;  // pre-tokenizer and lookup in one pass over the text (TD_OPT_FUSED; TD_FUSED=0 in the environment turns it off)
-    struct Ev3 { hipEvent_t e[TD_PROF_EVENTS]; };
+    struct Ev3 {  // the profiling events of one step (owned: hipEventDestroy when it goes)
+        hipEvent_t e[TD_PROF_EVENTS] = {};
+        Ev3() = default;
+        Ev3(Ev3&& o) noexcept { std::swap(e, o.e); }
+        Ev3& operator=(Ev3&& o) noexcept { std::swap(e, o.e); return *this; }
+        ~Ev3() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); }
+    };
     std::vector<Ev3> ev_pending, ev_free;
     int64_t last_repeats = 0, last_listed = 0;
     int64_t last_long = 0, last_far = 0, last_deferred = 0, last_flagged = 0, last_direct = 0, last_timeouts = 0;
     int64_t last_giant = 0;
     bool seen_counters = false;   // td_device_status / a host-buffer entry point has read a call's counters (what the launch sequence is chosen by)
     bool last_sparse = false;     // (TD_INFO_SPARSE)
-    int sparse_opt = -1;          // TD_OPT_SPARSE / TD_SPARSE at td_create time: 1 = always the sparse sequence, 0 = never, -1 = by the last counters
     const RxProgram* d_rx = nullptr;      // generic split pattern: the compiled program and its tables in HBM
     const uint16_t* d_rx_s1 = nullptr;
     const uint8_t* d_rx_s2 = nullptr;
     size_t ws_bytes = 0;
     // One workspace per handle: work of this handle may be in flight on one stream at a time.  A call on another
     // stream first waits (on the device, not the host) for the previous call's last kernel.
-    hipEvent_t last_done = nullptr;
+    Event last_done;
     hipStream_t last_stream = nullptr;
     bool has_last = false;
-    std::vector<void*> graveyard;  // workspace buffers replaced by larger ones; freed at the next synchronisation point
+    std::vector<DevBuf> graveyard;  // workspace buffers replaced by larger ones; freed at the next synchronisation point
     // host-buffer pipeline (td_encode_batch on large inputs): four slots of pinned bounce buffers + device buffers, three
     // streams (H2D, kernels, D2H)
     struct PipeSlot {
-        void* h_text = nullptr; size_t h_text_cap = 0;   // pinned
-        void* h_offs = nullptr; size_t h_offs_cap = 0;   // pinned: rebased document offsets in, token offsets out
-        void* h_tok = nullptr; size_t h_tok_cap = 0;     // pinned
+        PinnedBuf h_text, h_offs, h_tok;   // h_offs: rebased document offsets in, token offsets out
         DevBuf d_text, d_offs, d_tok, d_toff;
-        hipEvent_t ev_h2d = nullptr, ev_k = nullptr, ev_off = nullptr, ev_tok = nullptr;
-        Ctl* h_ctl = nullptr;                            // pinned copy of the device control block after the chunk's kernels
+        Event ev_h2d, ev_k, ev_off, ev_tok;
+        PinnedBuf h_ctl;                   // copy of the device control block after the chunk's kernels
     };
     static constexpr int PIPE_SLOTS = 4;
     PipeSlot pipe[PIPE_SLOTS];
-    hipStream_t s_h2d = nullptr, s_k = nullptr, s_d2h = nullptr;
-    int64_t pipe_chunk_bytes = 64ll << 20;  // (a GiB of English host to host: 16 MiB chunks 33 GB/s, 32 MiB 39, 64 MiB 40.5, profiles/r5_bench/e2e_sweep.txt)
-    int pipe_threads = 16;
+    Stream s_h2d, s_k, s_d2h;
     std::unique_ptr<CopyPool> pool_threads;
     // one-launch path for inputs of at most 4 KiB: pinned host buffers the kernel reads and writes directly
-    void* small_in = nullptr;
-    void* small_out = nullptr;
-    void* small_dec_in = nullptr;   // td_small_decode: ids in, status + bytes out
-    void* small_dec_out = nullptr;
+    PinnedBuf small_in, small_out;
+    PinnedBuf small_dec_in, small_dec_out;  // td_small_decode: ids in, status + bytes out
     unsigned long long small_seq = 0;
     // the resident form of the one-launch kernel (td_small_resident): its own stream, the generation of the last launch
-    hipStream_t s_res = nullptr;
+    Stream s_res;
     unsigned long long res_gen = 0;
-    bool small_resident = false;  // (TD_SMALL_RESIDENT=1 at td_create time.  Built for VERDICT r5 item 5a, measured, OFF: 14.1 us against 13.6 for a one-byte call —
-                                  // what a small call costs is the body's PCIe round trips and barriers, not the launch; tests/test_gpu_small_resident.py keeps it right)
-    unsigned long long small_idle_ticks = 20000;  // (TD_SMALL_IDLE_US at td_create time, default 200 us: 100 MHz ticks the kernel waits for the next request)
     // host batches between the one-launch path and the pipeline (td_encode_batch, 4 KiB .. 4 MiB): pinned in / out buffers
-    void* mid_in = nullptr; size_t mid_in_cap = 0;
-    void* mid_out = nullptr; size_t mid_out_cap = 0;
+    PinnedBuf mid_in, mid_out;
     DevBuf mid_dev;               // [offsets | text] on the device
     unsigned long long mid_seq = 0;
-    bool mid_enabled = true;      // (TD_MID_PATH=0 at td_create time: the copies-and-synchronise path of rounds 1-5, A/B)
-    bool small_enabled = true;
 };
 
 namespace {
 
-void drop_graph(td_tokenizer* t) {
-    if (t->graph_exec) (void)hipGraphExecDestroy(t->graph_exec);
-    t->graph_exec = nullptr;
-}
+void drop_graph(td_tokenizer* t) { t->graph_exec = GraphExec(); }
 
 int ensure(td_tokenizer* t, DevBuf& b, size_t bytes) {
     if (b.cap >= bytes && b.p) return TD_OK;
     if (b.p) {  // kernels of an earlier call may still read it: park it until the next synchronisation point
-        t->graveyard.push_back(b.p);
         t->ws_bytes -= b.cap;
-        b.p = nullptr;
-        b.cap = 0;
+        t->graveyard.push_back(std::move(b));
     }
     size_t want = bytes + bytes / 8 + 256;
     HIP_TRY(t, hipMalloc(&b.p, want));
@@ -312,14 +381,9 @@ int ensure(td_tokenizer* t, DevBuf& b, size_t bytes) {
     return TD_OK;
 }
 
-void bury(td_tokenizer* t) {  // caller has synchronised every stream this handle was used on
-    for (void* p : t->graveyard) (void)hipFree(p);
-    t->graveyard.clear();
-}
-
 int own_streams(td_tokenizer* t) {
-    if (!t->s_own) HIP_TRY(t, hipStreamCreateWithFlags(&t->s_own, hipStreamNonBlocking));
-    if (!t->h_ctl) HIP_TRY(t, hipHostMalloc(&t->h_ctl, 256, hipHostMallocDefault));
+    if (!t->s_own) HIP_TRY(t, make_stream(t->s_own));
+    if (!t->h_ctl.p) HIP_TRY(t, make_pinned(t->h_ctl, 256));
     return TD_OK;
 }
 // A copy (or fill) the host waits for: on the call's stream, then that stream is synchronised.  Never the legacy stream.
@@ -338,7 +402,7 @@ int zero_wait(td_tokenizer* t, void* dst, size_t bytes, hipStream_t s) {
 // stream itself may be gone by now, the event is ours).
 void drain(td_tokenizer* t) {
     if (t->has_last && t->last_done) (void)hipEventSynchronize(t->last_done);
-    for (hipStream_t st : {t->s_own, t->s_h2d, t->s_k, t->s_d2h, t->s_aux}) if (st) (void)hipStreamSynchronize(st);
+    for (hipStream_t st : {t->s_own.h, t->s_h2d.h, t->s_k.h, t->s_d2h.h, t->s_aux.h}) if (st) (void)hipStreamSynchronize(st);
 }
 
 // Runs f() with the handle locked and its device current; a failure's message is published to this thread's slot.
@@ -367,7 +431,7 @@ int order_before(td_tokenizer* t, hipStream_t stream) {
     return TD_OK;
 }
 int order_after(td_tokenizer* t, hipStream_t stream) {
-    if (!t->last_done) HIP_TRY(t, hipEventCreateWithFlags(&t->last_done, hipEventDisableTiming));
+    if (!t->last_done) HIP_TRY(t, make_event(t->last_done));
     HIP_TRY(t, hipEventRecord(t->last_done, stream));
     t->last_stream = stream;
     t->has_last = true;
@@ -409,7 +473,7 @@ static CollLayout coll_layout(const td_tokenizer* t, int64_t n, int64_t n_tiles,
     for (int c = 0; c < K_MISS_CLASSES; ++c) {
         const int64_t worst = n / minlen[c] + 1;
         int64_t cls = dense ? worst : std::min<int64_t>(worst, std::max<int64_t>(n / share[c] + 1, 65536));
-        if (t->coll_shrink > 1) cls = cls / t->coll_shrink + 1;
+        if (t->opt.coll_shrink > 1) cls = cls / t->opt.coll_shrink + 1;
         const int64_t per_list = std::min<int64_t>((cls + COLL_SUBS - 1) / COLL_SUBS + 64, 0x7FFFFFF0ll);
         L.base[c] = at;
         L.cap[c] = (uint32_t)per_list;
@@ -434,7 +498,7 @@ static uint32_t dd_tile_bits(int64_t n) {
 }
 static uint32_t dd_entries(const td_tokenizer* t, int64_t n) {
     const uint32_t most = 1u << std::min<uint32_t>(39 - dd_tile_bits(n), 21);  // (21 bits: what a TOK_DUPREF slot has for the seat)
-    if (t->dd_entries_opt) return std::min(t->dd_entries_opt, most);
+    if (t->opt.dd_entries_opt) return std::min(t->opt.dd_entries_opt, most);
     uint32_t e = 4096;
     while (e < (2u << 20) && e < most && (int64_t)e * 128 < n) e <<= 1;
     return std::min(e, most);
@@ -449,7 +513,7 @@ int reserve_ws(td_tokenizer* t, int64_t n, int64_t n_docs, bool dense = false) {
     if ((rc = ensure(t, t->tile_flag, (size_t)(n_tiles + 2) * 4))) return rc;   // (per pre-tokenizer tile: fewer than n_tiles)
     if ((rc = ensure(t, t->tile_carry, (size_t)(n_tiles + 2) * 8))) return rc;
     if ((rc = ensure(t, t->tile_state, (size_t)(n_tiles + 2) * 8))) return rc;   // (per pre-tokenizer tile too)
-    if (t->direct && t->H.pattern_kind != PATTERN_GENERIC && (rc = ensure(t, t->slab, (size_t)direct_grid_blocks() * SLAB_RING * SLAB_WORDS * 4))) return rc;
+    if (t->opt.direct && t->H.pattern_kind != PATTERN_GENERIC && (rc = ensure(t, t->slab, (size_t)direct_grid_blocks() * SLAB_RING * SLAB_WORDS * 4))) return rc;
     if ((rc = ensure(t, t->stage, (size_t)std::max<int64_t>(n_tiles, 1) * K_STAGE * 4))) return rc;
     if ((rc = ensure(t, t->stage2, (size_t)std::max<int64_t>(n_tiles, 1) * K_STAGE * 4))) return rc;  // ids of merged pieces
     if ((rc = ensure(t, t->tile_count, (size_t)(n_tiles + 1) * 4))) return rc;
@@ -474,7 +538,7 @@ int reserve_ws(td_tokenizer* t, int64_t n, int64_t n_docs, bool dense = false) {
     if ((rc = ensure(t, t->tile_first_doc, (size_t)(n_tiles + 1) * 4))) return rc;
     if ((rc = ensure(t, t->chunk_pref, (size_t)(n_tiles / 4096 + 2) * 8))) return rc;
     if ((rc = ensure(t, t->long_list, (size_t)(n / (K_MAXSHORT + 1) + n_tiles + 16) * sizeof(LongEntry)))) return rc;
-    const int64_t pool_bytes = t->pool_bytes_opt > 0 ? t->pool_bytes_opt : std::max<int64_t>(64ll << 20, 2 * n);
+    const int64_t pool_bytes = t->opt.pool_bytes_opt > 0 ? t->opt.pool_bytes_opt : std::max<int64_t>(64ll << 20, 2 * n);
     if ((rc = ensure(t, t->pool, (size_t)pool_bytes))) return rc;
     if ((rc = ensure(t, t->ctl, CTL_BYTES + TD_GP_SCRATCH_BYTES))) return rc;
     return TD_OK;
@@ -524,7 +588,7 @@ int encode_device_locked(td_tokenizer* t, const void* d_text, int64_t n, const v
     a.giant_count = &ctl->giant_count;
     a.gp_ctl = ctl->gp_ctl;
     a.gp_scratch = (uint32_t*)((char*)t->ctl.p + CTL_BYTES);  // (behind the control block; needs no reset)
-    a.gp_coop_min = t->gp_coop_min;
+    a.gp_coop_min = t->opt.gp_coop_min;
     a.tile_draw = &ctl->tile_draw;
     a.far_count = &ctl->far_tiles;
     a.ph_bar = &ctl->ph_bar;
@@ -553,10 +617,10 @@ int encode_device_locked(td_tokenizer* t, const void* d_text, int64_t n, const v
         a.coll_count = (uint32_t*)t->coll_ctr.p;
         a.ovf_count = &ctl->ovf_count;
     }
-    a.dedupe = (t->dedupe && n_tiles < (1ll << 24)) ? 1 : 0;  // (a table entry keeps the tile in 24 bits)
+    a.dedupe = (t->opt.dedupe && n_tiles < (1ll << 24)) ? 1 : 0;  // (a table entry keeps the tile in 24 bits)
     a.dd_seat_bits = std::min<uint32_t>(39 - dd_tile_bits(n), 21);
-    a.dd_minlen = t->dd_minlen;
-    a.dd_replicas = t->dd_replicas;
+    a.dd_minlen = t->opt.dd_minlen;
+    a.dd_replicas = t->opt.dd_replicas;
     a.dd_stats = ctl->dd_stats;
     a.dd_table = a.dedupe ? (unsigned long long*)t->dd_table.p : nullptr;
     a.dd_mask = a.dedupe ? dd_entries(t, n) - 1u : 0u;
@@ -575,9 +639,9 @@ int encode_device_locked(td_tokenizer* t, const void* d_text, int64_t n, const v
     a.flagged_list = (uint32_t*)t->flagged_list.p;
     a.deferred_list = (uint32_t*)t->deferred_list.p;
     a.deferred_count = &ctl->deferred_count;
-    a.fused = t->fused ? 1 : 0;
-    a.pack_split = t->pack_split ? 1 : 0;
-    a.direct = (t->direct && t->fused && !t->sp_active && t->H.pattern_kind != PATTERN_GENERIC && d_out && !t->stop_after) ? 1 : 0;
+    a.fused = t->opt.fused ? 1 : 0;
+    a.pack_split = t->opt.pack_split ? 1 : 0;
+    a.direct = (t->opt.direct && t->opt.fused && !t->sp_active && t->H.pattern_kind != PATTERN_GENERIC && d_out && !t->stop_after) ? 1 : 0;
     a.tile_state = (unsigned long long*)t->tile_state.p;
     a.slab = (uint32_t*)t->slab.p;
     a.direct_tiles = &ctl->direct_tiles;
@@ -615,11 +679,13 @@ int encode_device_locked(td_tokenizer* t, const void* d_text, int64_t n, const v
         a.sp.n = t->sp_n;
         a.sp.maxlen = t->sp_maxlen;
     }
-    td_tokenizer::Ev3 ev{};
+    hipEvent_t* prof = nullptr;
     if (t->profile) {
-        if (!t->ev_free.empty()) { ev = t->ev_free.back(); t->ev_free.pop_back(); }
+        td_tokenizer::Ev3 ev;  // (a failure frees the events it has made so far)
+        if (!t->ev_free.empty()) { ev = std::move(t->ev_free.back()); t->ev_free.pop_back(); }
         else for (auto& e : ev.e) HIP_TRY(t, hipEventCreate(&e));
-        t->ev_pending.push_back(ev);
+        t->ev_pending.push_back(std::move(ev));
+        prof = t->ev_pending.back().e;
     }
     // A call that repeats the previous one exactly (same buffers, sizes, stream: a loop over a resident batch, one rank's step
     // of a multi-GPU job) can replay the step as ONE hipGraph launch instead of its dozen kernel launches (opt-in: TD_OPT_GRAPH):
@@ -635,7 +701,7 @@ int encode_device_locked(td_tokenizer* t, const void* d_text, int64_t n, const v
     {
         bool sparse = t->seen_counters && t->last_far == 0 && t->last_deferred == 0 && t->last_giant == 0 &&
                       t->last_flagged * 64 <= n_tiles && t->last_long * 16 <= n_tiles;
-        if (t->sparse_opt >= 0) sparse = t->sparse_opt != 0;
+        if (t->opt.sparse_opt >= 0) sparse = t->opt.sparse_opt != 0;
         a.sparse = (sparse && a.fused && !a.direct && !t->sp_active && t->H.pattern_kind != PATTERN_GENERIC && !t->stop_after) ? 1 : 0;
         t->last_sparse = a.sparse != 0;
         a.pack_dense = (!a.sparse && a.pack_split && pack_dense_opt) ? 1 : 0;  // (the sparse sequence keeps its six launches: td_pack_rest takes the odd tile with many markers)
@@ -645,11 +711,11 @@ int encode_device_locked(td_tokenizer* t, const void* d_text, int64_t n, const v
     // ... when the handle has SEEN long pieces: the fork and the join cost a step without any ~13 us (English: -2 % at 256 MiB), a step
     // with a hundred thousand of them gains 4-7 %.  What the last call whose counters were read had (td_device_status, every host-buffer
     // entry point) decides; a handle that never reads them stays in line.
-    if (t->overlap && t->last_long >= 2048 && !a.sparse) {
+    if (t->opt.overlap && t->last_long >= 2048 && !a.sparse) {
         hipError_t ae = hipSuccess;
-        if (!t->s_aux) ae = hipStreamCreateWithFlags(&t->s_aux, hipStreamNonBlocking);  // (a stream priority, either way, changes nothing: r6 call 17)
-        if (ae == hipSuccess && !t->e_fork) ae = hipEventCreateWithFlags(&t->e_fork, hipEventDisableTiming);
-        if (ae == hipSuccess && !t->e_join) ae = hipEventCreateWithFlags(&t->e_join, hipEventDisableTiming);
+        if (!t->s_aux) ae = make_stream(t->s_aux);  // (a stream priority, either way, changes nothing: r6 call 17)
+        if (ae == hipSuccess && !t->e_fork) ae = make_event(t->e_fork);
+        if (ae == hipSuccess && !t->e_join) ae = make_event(t->e_join);
         if (ae == hipSuccess) { aux_v = LaunchAux{t->s_aux, t->e_fork, t->e_join}; aux = &aux_v; }
         else (void)hipGetLastError();  // (no second stream: everything in line)
     }
@@ -657,7 +723,7 @@ int encode_device_locked(td_tokenizer* t, const void* d_text, int64_t n, const v
     hipStreamCaptureStatus cap_status = hipStreamCaptureStatusNone;
     if (stream && hipStreamIsCapturing(stream, &cap_status) != hipSuccess) { cap_status = hipStreamCaptureStatusNone; (void)hipGetLastError(); }
     // (a caller that is capturing this stream into a graph of its own gets the plain launches captured there)
-    if (t->graphs && !t->profile && !t->stop_after && cap_status == hipStreamCaptureStatusNone) {
+    if (t->opt.graphs && !t->profile && !t->stop_after && cap_status == hipStreamCaptureStatusNone) {
         const bool same_as_graph = t->graph_exec && t->graph_stream == stream && memcmp(&a, &t->graph_key, sizeof a) == 0;
         if (same_as_graph) {
             HIP_TRY(t, hipGraphLaunch(t->graph_exec, stream));
@@ -667,15 +733,17 @@ int encode_device_locked(td_tokenizer* t, const void* d_text, int64_t n, const v
         if (repeats) {
             drop_graph(t);
             hipGraph_t g = nullptr;
-            hipError_t ce = t->s_cap ? hipSuccess : hipStreamCreateWithFlags(&t->s_cap, hipStreamNonBlocking);
+            hipError_t ce = t->s_cap ? hipSuccess : make_stream(t->s_cap);
             if (ce == hipSuccess) ce = hipStreamBeginCapture(t->s_cap, hipStreamCaptureModeThreadLocal);
             if (ce == hipSuccess) {
                 const hipError_t le = launch_encode(a, t->s_cap, nullptr, aux);
                 ce = hipStreamEndCapture(t->s_cap, &g);  // (always: also ends a capture that was invalidated)
                 if (le != hipSuccess) ce = le;
             }
-            if (ce == hipSuccess && g && hipGraphInstantiate(&t->graph_exec, g, nullptr, nullptr, 0) == hipSuccess) {
+            hipGraphExec_t ge = nullptr;
+            if (ce == hipSuccess && g && hipGraphInstantiate(&ge, g, nullptr, nullptr, 0) == hipSuccess) {
                 (void)hipGraphDestroy(g);
+                t->graph_exec = GraphExec(ge);
                 t->graph_key = a;
                 t->graph_stream = stream;
                 t->graph_failures = 0;
@@ -683,10 +751,9 @@ int encode_device_locked(td_tokenizer* t, const void* d_text, int64_t n, const v
                 return order_after(t, stream);
             }
             if (g) (void)hipGraphDestroy(g);
-            t->graph_exec = nullptr;
             (void)hipGetLastError();
             // not this time: plain launches below; two more identical calls try again, three failures in a row give up
-            if (++t->graph_failures >= 3) t->graphs = false;
+            if (++t->graph_failures >= 3) t->opt.graphs = false;
             t->has_last_key = false;
         } else {
             t->last_key = a;
@@ -694,7 +761,7 @@ int encode_device_locked(td_tokenizer* t, const void* d_text, int64_t n, const v
             t->has_last_key = true;
         }
     }
-    HIP_TRY(t, launch_encode(a, stream, t->profile ? ev.e : nullptr, aux));
+    HIP_TRY(t, launch_encode(a, stream, prof, aux));
     return order_after(t, stream);
 }
 
@@ -704,10 +771,10 @@ int device_status_locked(td_tokenizer* t, hipStream_t stream, int64_t* err_pos) 
     int rc0 = own_streams(t);
     if (rc0) return rc0;
     static_assert(sizeof(Ctl) <= 256, "h_ctl");
-    HIP_TRY(t, hipMemcpyAsync(t->h_ctl, t->ctl.p, sizeof(Ctl), hipMemcpyDeviceToHost, stream));  // (behind the call's kernels)
+    HIP_TRY(t, hipMemcpyAsync(t->h_ctl.p, t->ctl.p, sizeof(Ctl), hipMemcpyDeviceToHost, stream));  // (behind the call's kernels)
     HIP_TRY(t, hipStreamSynchronize(stream));
-    if (!t->has_last || t->last_stream == stream) bury(t);  // nothing of this handle is in flight any more
-    return absorb_ctl(t, *(const Ctl*)t->h_ctl, stream, err_pos);
+    if (!t->has_last || t->last_stream == stream) t->graveyard.clear();  // nothing of this handle is in flight any more
+    return absorb_ctl(t, *(const Ctl*)t->h_ctl.p, stream, err_pos);
 }
 
 // the control block of a finished call, on the host: counters the launch sequence / second stream are chosen by, the device's error (if any)
@@ -938,21 +1005,7 @@ int td_create(const char* pat_str, int64_t n_vocab, const uint8_t* token_bytes, 
         return TD_E_INVALID;
     }
     td_tokenizer* t = new td_tokenizer;
-    if (const char* e = getenv("TD_FUSED")) t->fused = atoi(e) != 0;
-    if (const char* e = getenv("TD_GRAPH")) t->graphs = atoi(e) != 0;
-    if (const char* e = getenv("TD_DIRECT")) t->direct = atoi(e) != 0;
-    if (const char* e = getenv("TD_PACK_SPLIT")) t->pack_split = atoi(e) != 0;
-    if (const char* e = getenv("TD_DEDUPE")) t->dedupe = atoi(e) != 0;
-    if (const char* e = getenv("TD_OVERLAP")) t->overlap = atoi(e) != 0;
-    if (const char* e = getenv("TD_MID_PATH")) t->mid_enabled = atoi(e) != 0;
-    if (const char* e = getenv("TD_SMALL_RESIDENT")) t->small_resident = atoi(e) != 0;
-    if (const char* e = getenv("TD_SMALL_IDLE_US")) { const long v = atol(e); if (v >= 1 && v <= 1000000) t->small_idle_ticks = (unsigned long long)v * 100ull; }
-    if (const char* e = getenv("TD_SPARSE")) { const int v = atoi(e); if (v >= -1 && v <= 1) t->sparse_opt = v; }
-    if (const char* e = getenv("TD_GP_COOP_MIN")) { if (atol(e) >= 1024) t->gp_coop_min = (uint32_t)std::min<long>(atol(e), 0x7FFFFFFF); }
-    if (const char* e = getenv("TD_DD_REPLICAS")) { const int v = atoi(e); if (v >= 1 && v <= 16 && !(v & (v - 1))) t->dd_replicas = (uint32_t)v; }
-    if (const char* e = getenv("TD_DD_MINLEN")) t->dd_minlen = (uint32_t)std::max(2, atoi(e));
-    if (const char* e = getenv("TD_DD_ENTRIES")) { const long v = atol(e); if (v >= 2 && v <= (1l << 24) && !(v & (v - 1))) t->dd_entries_opt = (uint32_t)v; }
-    if (const char* e = getenv("TD_COLL_SHRINK")) t->coll_shrink = std::max(1, atoi(e));
+    t->opt = Options::from_env();
     std::string err;
     int rc = build_tables(pat_str, n_vocab, token_bytes, token_offsets, ranks, n_special, special_bytes, special_offsets,
                           special_ids, t->H, err);
@@ -1056,9 +1109,7 @@ int td_clone(td_tokenizer* src, td_tokenizer** out) {
         t = new td_tokenizer(src->shared);
         t->dT = src->dT; t->dTp = src->dTp; t->device = src->device;
         t->d_rx = src->d_rx; t->d_rx_s1 = src->d_rx_s1; t->d_rx_s2 = src->d_rx_s2; t->d_ctab = src->d_ctab;
-        t->pool_bytes_opt = src->pool_bytes_opt; t->graphs = src->graphs; t->fused = src->fused; t->direct = src->direct; t->pack_split = src->pack_split; t->dedupe = src->dedupe; t->overlap = src->overlap; t->sparse_opt = src->sparse_opt; t->gp_coop_min = src->gp_coop_min; t->dd_entries_opt = src->dd_entries_opt; t->dd_minlen = src->dd_minlen; t->dd_replicas = src->dd_replicas; t->coll_shrink = src->coll_shrink;
-        t->device_specials = src->device_specials; t->small_enabled = src->small_enabled; t->mid_enabled = src->mid_enabled; t->small_resident = src->small_resident; t->small_idle_ticks = src->small_idle_ticks;
-        t->pipe_chunk_bytes = src->pipe_chunk_bytes; t->pipe_threads = src->pipe_threads;
+        t->opt = src->opt;
     }
     DeviceGuard dg(t->device);
     int rc = own_streams(t);
@@ -1073,39 +1124,15 @@ int td_clone(td_tokenizer* src, td_tokenizer** out) {
     return TD_OK;
 }
 
+// The handle's members free themselves (owner types); what td_destroy adds is the condition that makes that safe: they are
+// destroyed only after everything the handle has in flight is done (drain, the resident small-call kernel's stream — it reads
+// the pinned small-path buffers), and with the handle's device current.
 void td_destroy(td_tokenizer* t) {
     if (!t) return;
-    {
-        DeviceGuard dg(t->device);  // reached from finalisers at arbitrary points: the caller's device must survive
-        drain(t);  // (not hipDeviceSynchronize: other handles' and the application's streams are none of this handle's business)
-        bury(t);
-        drop_graph(t);
-        for (auto& ev : t->ev_pending) for (auto e : ev.e) (void)hipEventDestroy(e);
-        for (auto& ev : t->ev_free) for (auto e : ev.e) (void)hipEventDestroy(e);
-        if (t->last_done) (void)hipEventDestroy(t->last_done);
-        for (auto& sl : t->pipe) {
-            for (void* hp : {sl.h_text, sl.h_offs, sl.h_tok, (void*)sl.h_ctl}) if (hp) (void)hipHostFree(hp);
-            for (DevBuf* b : {&sl.d_text, &sl.d_offs, &sl.d_tok, &sl.d_toff}) if (b->p) (void)hipFree(b->p);
-            for (hipEvent_t e : {sl.ev_h2d, sl.ev_k, sl.ev_off, sl.ev_tok}) if (e) (void)hipEventDestroy(e);
-        }
-        for (hipStream_t st : {t->s_h2d, t->s_k, t->s_d2h, t->s_own, t->s_cap, t->s_aux}) if (st) (void)hipStreamDestroy(st);
-        for (hipEvent_t e : {t->e_fork, t->e_join}) if (e) (void)hipEventDestroy(e);
-        if (t->h_ctl) (void)hipHostFree(t->h_ctl);
-        if (t->s_res) { (void)hipStreamSynchronize(t->s_res); (void)hipStreamDestroy(t->s_res); }  // (the resident small-call kernel leaves by itself within its idle time)
-        if (t->small_in) (void)hipHostFree(t->small_in);
-        if (t->mid_in) (void)hipHostFree(t->mid_in);
-        if (t->mid_out) (void)hipHostFree(t->mid_out);
-        if (t->small_dec_in) (void)hipHostFree(t->small_dec_in);
-        if (t->small_dec_out) (void)hipHostFree(t->small_dec_out);
-        if (t->small_out) (void)hipHostFree(t->small_out);
-        DevBuf* bufs[] = {&t->dd_table, &t->rest_mask, &t->coll_ctr, &t->gx_prefix, &t->tile_state, &t->slab, &t->docbits, &t->startbits, &t->slow_list, &t->tile_flag, &t->tile_carry, &t->stage, &t->stage2, &t->tile_count, &t->tile_extra, &t->miss_list, &t->flagged_list, &t->deferred_list, &t->gap_list, &t->gapbits, &t->gx_exit, &t->gx_state, &t->sp_bytes, &t->sp_off, &t->sp_len, &t->sp_id, &t->sp_parent, &t->sp_first2, &t->sp_hit, &t->sp_acc, &t->sp_cpos, &t->sp_clit, &t->sp_ccount, &t->tile_base, &t->doc_slot, &t->long_list,
-                          &t->pool, &t->ctl, &t->tile_first_doc, &t->chunk_pref, &t->h2d_text, &t->h2d_offs, &t->d_tokens, &t->d_offsets, &t->dec_tokens,
-                          &t->dec_off, &t->dec_out, &t->off_heads, &t->off_chunks, &t->off_docs, &t->off_rank, &t->off_starts, &t->rows_scan, &t->rows_out, &t->rows_pos,
-                          &t->rows_aux, &t->rows_counts};
-        for (DevBuf* b : bufs)
-            if (b->p) (void)hipFree(b->p);
-    }
     if (g_thread_err_owner == t) g_thread_err_owner = nullptr;
+    DeviceGuard dg(t->device);  // reached from finalisers at arbitrary points: the caller's device must survive
+    drain(t);  // (not hipDeviceSynchronize: other handles' and the application's streams are none of this handle's business)
+    if (t->s_res) (void)hipStreamSynchronize(t->s_res);  // (the resident small-call kernel leaves by itself within its idle time)
     delete t;
 }
 
@@ -1272,25 +1299,28 @@ void parallel_memcpy(void* dst, const void* src, size_t bytes, int threads) {
     for (auto& x : th) x.join();
 }
 
-int pinned_ensure(td_tokenizer* t, void*& p, size_t& cap, size_t bytes) {
-    if (cap >= bytes && p) return TD_OK;
-    if (p) HIP_TRY(t, hipHostFree(p));
-    p = nullptr; cap = 0;
-    const size_t want = bytes + bytes / 8 + 4096;
-    HIP_TRY(t, hipHostMalloc(&p, want, hipHostMallocDefault));
-    cap = want;
+int pinned_ensure(td_tokenizer* t, PinnedBuf& b, size_t bytes) {
+    if (b.cap >= bytes && b.p) return TD_OK;
+    b = PinnedBuf();  // (the old one first)
+    HIP_TRY(t, make_pinned(b, bytes + bytes / 8 + 4096));
     return TD_OK;
 }
 
+// The streams, events and control-block copies of the pipeline: made aside and moved in only when all of them exist, so that
+// a failure leaves the handle without a pipeline, never with half of one (and null streams).
 int pipe_init(td_tokenizer* t) {
     if (t->s_h2d) return TD_OK;
-    HIP_TRY(t, hipStreamCreateWithFlags(&t->s_h2d, hipStreamNonBlocking));
-    HIP_TRY(t, hipStreamCreateWithFlags(&t->s_k, hipStreamNonBlocking));
-    HIP_TRY(t, hipStreamCreateWithFlags(&t->s_d2h, hipStreamNonBlocking));
-    for (auto& sl : t->pipe) {
-        for (hipEvent_t* e : {&sl.ev_h2d, &sl.ev_k, &sl.ev_off, &sl.ev_tok}) HIP_TRY(t, hipEventCreateWithFlags(e, hipEventDisableTiming));
-        HIP_TRY(t, hipHostMalloc((void**)&sl.h_ctl, sizeof(Ctl), hipHostMallocDefault));
+    Stream h2d, k, d2h;
+    td_tokenizer::PipeSlot slots[td_tokenizer::PIPE_SLOTS];
+    for (Stream* st : {&h2d, &k, &d2h}) HIP_TRY(t, make_stream(*st));
+    for (auto& sl : slots) {
+        for (Event* e : {&sl.ev_h2d, &sl.ev_k, &sl.ev_off, &sl.ev_tok}) HIP_TRY(t, make_event(*e));
+        HIP_TRY(t, make_pinned(sl.h_ctl, sizeof(Ctl)));
     }
+    for (int i = 0; i < td_tokenizer::PIPE_SLOTS; ++i) t->pipe[i] = std::move(slots[i]);  // (the slots have no buffers yet)
+    t->s_k = std::move(k);
+    t->s_d2h = std::move(d2h);
+    t->s_h2d = std::move(h2d);
     return TD_OK;
 }
 
@@ -1298,12 +1328,12 @@ int encode_batch_pipelined(td_tokenizer* t, const uint8_t* text, const int64_t* 
                            int32_t* out_tokens, int64_t out_capacity, int64_t* out_offsets, int64_t* n_tokens) {
     int rc;
     if ((rc = pipe_init(t))) return rc;
-    if (!t->pool_threads || t->pool_threads->size() != std::max(t->pipe_threads - 1, 1)) t->pool_threads.reset(new CopyPool(std::max(t->pipe_threads - 1, 1)));
+    if (!t->pool_threads || t->pool_threads->size() != std::max(t->opt.pipe_threads - 1, 1)) t->pool_threads.reset(new CopyPool(std::max(t->opt.pipe_threads - 1, 1)));
     if ((rc = order_before(t, t->s_k))) return rc;
     // chunks: whole documents, about pipe_chunk_bytes each (inputs of less than six such chunks: a sixth of the input, down to an
     // eighth of pipe_chunk_bytes — the pipeline needs a few chunks in flight to hide anything)
     const int64_t n_all = doc_offsets[n_docs] - doc_offsets[0];
-    const int64_t chunk_bytes = std::min(t->pipe_chunk_bytes, std::max<int64_t>(t->pipe_chunk_bytes / 8, n_all / 6));
+    const int64_t chunk_bytes = std::min(t->opt.pipe_chunk_bytes, std::max<int64_t>(t->opt.pipe_chunk_bytes / 8, n_all / 6));
     std::vector<int64_t> cd{0};
     for (int64_t d = 0; d < n_docs;) {
         const int64_t lo = doc_offsets[d];
@@ -1342,8 +1372,8 @@ int encode_batch_pipelined(td_tokenizer* t, const uint8_t* text, const int64_t* 
         const int64_t d0 = cd[(size_t)i], d1 = cd[(size_t)i + 1], b0 = doc_offsets[d0], nb = doc_offsets[d1] - b0;
         const auto t0 = now();
         int r;
-        if ((r = pinned_ensure(t, sl.h_text, sl.h_text_cap, (size_t)nb + 64))) return r;
-        in_job[i % NS] = t->pool_threads->copy(sl.h_text, text + b0, (size_t)nb);
+        if ((r = pinned_ensure(t, sl.h_text, (size_t)nb + 64))) return r;
+        in_job[i % NS] = t->pool_threads->copy(sl.h_text.p, text + b0, (size_t)nb);
         lap(5, t0);
         return TD_OK;
     };
@@ -1353,29 +1383,29 @@ int encode_batch_pipelined(td_tokenizer* t, const uint8_t* text, const int64_t* 
         pend[(size_t)i] = {d0, d1, b0, nb, 0};
         int r;
         auto t0 = now();
-        if ((r = pinned_ensure(t, sl.h_offs, sl.h_offs_cap, (size_t)(nd + 1) * 8))) return r;
+        if ((r = pinned_ensure(t, sl.h_offs, (size_t)(nd + 1) * 8))) return r;
         if ((r = ensure(t, sl.d_text, (size_t)nb + 64))) return r;
         if ((r = ensure(t, sl.d_offs, (size_t)(nd + 1) * 8))) return r;
         if ((r = ensure(t, sl.d_toff, (size_t)(nd + 1) * 8))) return r;
         if ((r = ensure(t, sl.d_tok, (size_t)std::max<int64_t>(nb, 1) * 4))) return r;  // worst case one id per byte
-        int64_t* ho = (int64_t*)sl.h_offs;
+        int64_t* ho = (int64_t*)sl.h_offs.p;
         for (int64_t k = 0; k <= nd; ++k) ho[k] = doc_offsets[d0 + k] - b0;
         lap(1, t0);
         t0 = now();
         if (in_job[i % NS]) { t->pool_threads->wait(in_job[i % NS]); in_job[i % NS].reset(); }
         lap(0, t0);
         t0 = now();
-        if (nb > 0) HIP_TRY(t, hipMemcpyAsync(sl.d_text.p, sl.h_text, (size_t)nb, hipMemcpyHostToDevice, t->s_h2d));
-        HIP_TRY(t, hipMemcpyAsync(sl.d_offs.p, sl.h_offs, (size_t)(nd + 1) * 8, hipMemcpyHostToDevice, t->s_h2d));
+        if (nb > 0) HIP_TRY(t, hipMemcpyAsync(sl.d_text.p, sl.h_text.p, (size_t)nb, hipMemcpyHostToDevice, t->s_h2d));
+        HIP_TRY(t, hipMemcpyAsync(sl.d_offs.p, sl.h_offs.p, (size_t)(nd + 1) * 8, hipMemcpyHostToDevice, t->s_h2d));
         HIP_TRY(t, hipEventRecord(sl.ev_h2d, t->s_h2d));
         HIP_TRY(t, hipStreamWaitEvent(t->s_k, sl.ev_h2d, 0));
         if ((r = encode_device_locked(t, sl.d_text.p, nb, sl.d_offs.p, nd, mode, sl.d_tok.p, std::max<int64_t>(nb, 1), sl.d_toff.p, t->s_k))) return r;
         // the chunk's error word and the workspace counters travel with its offsets (the next chunk resets the counters)
         if (publish) {
-            HIP_TRY(t, launch_pipe_publish(t->ctl.p, (uint32_t)sizeof(Ctl), sl.h_ctl, (const int64_t*)sl.d_toff.p, nd + 1, (int64_t*)sl.h_offs, t->s_k));
+            HIP_TRY(t, launch_pipe_publish(t->ctl.p, (uint32_t)sizeof(Ctl), sl.h_ctl.p, (const int64_t*)sl.d_toff.p, nd + 1, (int64_t*)sl.h_offs.p, t->s_k));
         } else {
-            HIP_TRY(t, hipMemcpyAsync(sl.h_ctl, t->ctl.p, sizeof(Ctl), hipMemcpyDeviceToHost, t->s_k));
-            HIP_TRY(t, hipMemcpyAsync(sl.h_offs, sl.d_toff.p, (size_t)(nd + 1) * 8, hipMemcpyDeviceToHost, t->s_k));
+            HIP_TRY(t, hipMemcpyAsync(sl.h_ctl.p, t->ctl.p, sizeof(Ctl), hipMemcpyDeviceToHost, t->s_k));
+            HIP_TRY(t, hipMemcpyAsync(sl.h_offs.p, sl.d_toff.p, (size_t)(nd + 1) * 8, hipMemcpyDeviceToHost, t->s_k));
         }
         HIP_TRY(t, hipEventRecord(sl.ev_off, t->s_k));
         lap(1, t0);
@@ -1388,13 +1418,14 @@ int encode_batch_pipelined(td_tokenizer* t, const uint8_t* text, const int64_t* 
         HIP_TRY(t, hipEventSynchronize(sl.ev_off));
         lap(2, t0);
         const int64_t nd = P.d1 - P.d0;
-        const int64_t* to = (const int64_t*)sl.h_offs;
+        const int64_t* to = (const int64_t*)sl.h_offs.p;
+        const Ctl& c = *(const Ctl*)sl.h_ctl.p;
         P.ntok = to[nd];
-        t->last_direct += sl.h_ctl->direct_tiles;  // (td_info: sums over the call's chunks)
-        t->last_timeouts += sl.h_ctl->lb_timeouts;
-        if (sl.h_ctl->err != 0 && first_err == TD_OK) {
-            first_err = sl.h_ctl->err;
-            const long long pos = sl.h_ctl->err_pos + (first_err == TD_E_UNKNOWN_BYTE || first_err == TD_E_SCRATCH ? P.b0 : 0);
+        t->last_direct += c.direct_tiles;  // (td_info: sums over the call's chunks)
+        t->last_timeouts += c.lb_timeouts;
+        if (c.err != 0 && first_err == TD_OK) {
+            first_err = c.err;
+            const long long pos = c.err_pos + (first_err == TD_E_UNKNOWN_BYTE || first_err == TD_E_SCRATCH ? P.b0 : 0);
             t->err = first_err == TD_E_UNKNOWN_BYTE ? "No value found for piece at byte offset " + std::to_string(pos) + ": byte sequence is not in the vocabulary"
                                                     : "device error " + std::to_string(first_err) + " near byte offset " + std::to_string(pos);
         }
@@ -1405,11 +1436,11 @@ int encode_batch_pipelined(td_tokenizer* t, const uint8_t* text, const int64_t* 
         t0 = now();
         if (out_job[i % NS]) { t->pool_threads->wait(out_job[i % NS]); out_job[i % NS].reset(); }
         lap(3, t0);
-        if ((r = pinned_ensure(t, sl.h_tok, sl.h_tok_cap, (size_t)std::max<int64_t>(P.ntok, 1) * 4))) return r;
+        if ((r = pinned_ensure(t, sl.h_tok, (size_t)std::max<int64_t>(P.ntok, 1) * 4))) return r;
         if (P.ntok > 0 && !capacity_miss && first_err == TD_OK)
         {
-            if (d2h_blocks > 0) HIP_TRY(t, launch_pipe_copy_out(sl.d_tok.p, sl.h_tok, P.ntok, d2h_blocks, t->s_d2h));
-            else HIP_TRY(t, hipMemcpyAsync(sl.h_tok, sl.d_tok.p, (size_t)P.ntok * 4, hipMemcpyDeviceToHost, t->s_d2h));
+            if (d2h_blocks > 0) HIP_TRY(t, launch_pipe_copy_out(sl.d_tok.p, sl.h_tok.p, P.ntok, d2h_blocks, t->s_d2h));
+            else HIP_TRY(t, hipMemcpyAsync(sl.h_tok.p, sl.d_tok.p, (size_t)P.ntok * 4, hipMemcpyDeviceToHost, t->s_d2h));
         }
         HIP_TRY(t, hipEventRecord(sl.ev_tok, t->s_d2h));
         const int64_t base = tok_base;
@@ -1424,7 +1455,7 @@ int encode_batch_pipelined(td_tokenizer* t, const uint8_t* text, const int64_t* 
         HIP_TRY(t, hipEventSynchronize(sl.ev_tok));
         lap(4, t0);
         t0 = now();
-        if (P.ntok > 0 && !capacity_miss && first_err == TD_OK) out_job[i % NS] = t->pool_threads->copy(out_tokens + P.nbytes, sl.h_tok, (size_t)P.ntok * 4);
+        if (P.ntok > 0 && !capacity_miss && first_err == TD_OK) out_job[i % NS] = t->pool_threads->copy(out_tokens + P.nbytes, sl.h_tok.p, (size_t)P.ntok * 4);
         lap(5, t0);
         return TD_OK;
     };
@@ -1477,18 +1508,21 @@ constexpr size_t SMALL_OUT_BYTES = 64 + (SMALL_MAX_DOCS + 2) * 8 + SMALL_MAX_BYT
 int encode_batch_small(td_tokenizer* t, const uint8_t* text, const int64_t* doc_offsets, int64_t n_docs, int mode,
                        int32_t* out_tokens, int64_t out_capacity, int64_t* out_offsets, int64_t* n_tokens) {
     const int64_t n = doc_offsets[n_docs];
-    if (!t->small_in) {
-        HIP_TRY(t, hipHostMalloc(&t->small_in, SMALL_IN_BYTES, hipHostMallocDefault));
-        HIP_TRY(t, hipHostMalloc(&t->small_out, SMALL_OUT_BYTES, hipHostMallocDefault));
-        memset(t->small_out, 0, SMALL_OUT_BYTES);
+    if (!t->small_in.p) {  // (both or neither)
+        PinnedBuf in, out;
+        HIP_TRY(t, make_pinned(in, SMALL_IN_BYTES));
+        HIP_TRY(t, make_pinned(out, SMALL_OUT_BYTES));
+        memset(out.p, 0, SMALL_OUT_BYTES);
+        t->small_in = std::move(in);
+        t->small_out = std::move(out);
     }
     int rc;
     if ((rc = own_streams(t))) return rc;
     const size_t offs_bytes = (((size_t)(n_docs + 1) * 8) + 15) & ~(size_t)15;
-    uint8_t* in = (uint8_t*)t->small_in;
+    uint8_t* in = (uint8_t*)t->small_in.p;
     memcpy(in + 64, doc_offsets, (size_t)(n_docs + 1) * 8);
     memcpy(in + 64 + offs_bytes, text, (size_t)n);
-    uint8_t* out = (uint8_t*)t->small_out;
+    uint8_t* out = (uint8_t*)t->small_out.p;
     SmallArgs a;
     a.Tp = t->dTp;
     a.doc_offsets = (const int64_t*)(in + 64);
@@ -1502,18 +1536,18 @@ int encode_batch_small(td_tokenizer* t, const uint8_t* text, const int64_t* doc_
     a.use_fastpath = (mode == TD_MODE_ENCODE) || t->H.merge_closed;
     volatile unsigned long long* seqp = &a.status->seq;
     hipStream_t s = t->s_own;
-    if (t->small_resident) {
+    if (t->opt.small_resident) {
         // the request for td_small_resident: header fields, then the sequence number (release); the kernel is launched when the last one
         // has left (its generation stands at out + 40 then) — it reads tables and pinned buffers only, so it needs no ordering with the
         // handle's other work
-        if (!t->s_res) HIP_TRY(t, hipStreamCreateWithFlags(&t->s_res, hipStreamNonBlocking));
+        if (!t->s_res) HIP_TRY(t, make_stream(t->s_res));
         SmallMailbox* mb = (SmallMailbox*)in;
         mb->n = a.n; mb->n_docs = a.n_docs; mb->use_fastpath = a.use_fastpath; mb->offs_bytes = (int)offs_bytes;
         __atomic_store_n(&mb->seq, a.seq, __ATOMIC_RELEASE);
         volatile unsigned long long* exitp = (volatile unsigned long long*)(out + 40);
         auto launch = [&]() -> int {
             ++t->res_gen;
-            HIP_TRY(t, launch_small_resident(t->dTp, in, out, t->res_gen, t->small_idle_ticks, t->s_res));
+            HIP_TRY(t, launch_small_resident(t->dTp, in, out, t->res_gen, t->opt.small_idle_ticks, t->s_res));
             return TD_OK;
         };
         if (t->res_gen == 0 || __atomic_load_n(exitp, __ATOMIC_ACQUIRE) == t->res_gen) { if ((rc = launch())) return rc; }
@@ -1578,20 +1612,20 @@ int encode_batch_mid(td_tokenizer* t, const uint8_t* text, const int64_t* doc_of
     const size_t offs_bytes = (((size_t)(n_docs + 1) * 8) + 63) & ~(size_t)63;
     const size_t in_bytes = offs_bytes + (size_t)n + 64;
     const size_t out_bytes = 512 + offs_bytes + (size_t)n * 4 + 64;
-    if ((rc = pinned_ensure(t, t->mid_in, t->mid_in_cap, in_bytes))) return rc;
-    if (!t->mid_out || t->mid_out_cap < out_bytes) {
-        if ((rc = pinned_ensure(t, t->mid_out, t->mid_out_cap, out_bytes))) return rc;
-        memset(t->mid_out, 0, 512);
+    if ((rc = pinned_ensure(t, t->mid_in, in_bytes))) return rc;
+    if (!t->mid_out.p || t->mid_out.cap < out_bytes) {
+        if ((rc = pinned_ensure(t, t->mid_out, out_bytes))) return rc;
+        memset(t->mid_out.p, 0, 512);
     }
     if ((rc = ensure(t, t->mid_dev, in_bytes))) return rc;
     if ((rc = own_streams(t))) return rc;
     hipStream_t s = t->s_own;
     if ((rc = order_before(t, s))) return rc;
-    uint8_t* in = (uint8_t*)t->mid_in;
+    uint8_t* in = (uint8_t*)t->mid_in.p;
     memcpy(in, doc_offsets, (size_t)(n_docs + 1) * 8);
     memcpy(in + offs_bytes, text, (size_t)n);
     HIP_TRY(t, hipMemcpyAsync(t->mid_dev.p, in, offs_bytes + (size_t)n, hipMemcpyHostToDevice, s));
-    uint8_t* out = (uint8_t*)t->mid_out;  // [0, 256): control block | [256]: sequence number | 512: offsets | ids
+    uint8_t* out = (uint8_t*)t->mid_out.p;  // [0, 256): control block | [256]: sequence number | 512: offsets | ids
     int64_t* h_offs = (int64_t*)(out + 512);
     int32_t* h_tok = (int32_t*)(out + 512 + offs_bytes);
     rc = encode_device_locked(t, (uint8_t*)t->mid_dev.p + offs_bytes, n, t->mid_dev.p, n_docs, mode, h_tok, std::max<int64_t>(n, 1), h_offs, s);
@@ -1609,7 +1643,7 @@ int encode_batch_mid(td_tokenizer* t, const uint8_t* text, const int64_t* doc_of
             return TD_E_HIP;
         }
     }
-    if (!t->has_last || t->last_stream == s) bury(t);  // (the sequence number is written behind the step's last kernel: nothing of this handle is in flight)
+    if (!t->has_last || t->last_stream == s) t->graveyard.clear();  // (the sequence number is written behind the step's last kernel: nothing of this handle is in flight)
     if ((rc = absorb_ctl(t, *(const Ctl*)out, s, nullptr))) return rc;
     memcpy(out_offsets, h_offs, (size_t)(n_docs + 1) * 8);
     const int64_t total = out_offsets[n_docs];
@@ -1634,13 +1668,13 @@ int encode_batch_locked(td_tokenizer* t, const uint8_t* text, const int64_t* doc
     if ((rc = check_offsets(t, "doc_offsets", doc_offsets, n_docs, text))) return rc;
     const int64_t n = doc_offsets[n_docs];
     const bool plain = t->gx_prefix_host != nullptr || out_starts;  // (context prefixes of a generic pattern, starts: the plain path below, whatever the size)
-    if (n > 0 && n <= SMALL_MAX_BYTES && n_docs <= SMALL_MAX_DOCS && t->small_enabled && t->H.pattern_kind != PATTERN_GENERIC && !out_starts) {  // (the one-launch kernel knows the family's scanners only)
+    if (n > 0 && n <= SMALL_MAX_BYTES && n_docs <= SMALL_MAX_DOCS && t->opt.small_enabled && t->H.pattern_kind != PATTERN_GENERIC && !out_starts) {  // (the one-launch kernel knows the family's scanners only)
         rc = encode_batch_small(t, text, doc_offsets, n_docs, mode, out_tokens, out_capacity, out_offsets, n_tokens);
         if (rc != -1) return rc;  // (-1: a piece above 64 bytes; the general path below handles it)
     }
-    if (n > 0 && n <= MID_MAX_BYTES && n_docs <= MID_MAX_DOCS && t->mid_enabled && !plain)
+    if (n > 0 && n <= MID_MAX_BYTES && n_docs <= MID_MAX_DOCS && t->opt.mid_enabled && !plain)
         return encode_batch_mid(t, text, doc_offsets, n_docs, mode, out_tokens, out_capacity, out_offsets, n_tokens);
-    if (n >= t->pipe_chunk_bytes / 2 && out_tokens && !plain)  // (default: from 32 MiB on)
+    if (n >= t->opt.pipe_chunk_bytes / 2 && out_tokens && !plain)  // (default: from 32 MiB on)
         return encode_batch_pipelined(t, text, doc_offsets, n_docs, mode, out_tokens, out_capacity, out_offsets, n_tokens);
     if ((rc = ensure(t, t->h2d_text, (size_t)n + 64))) return rc;
     if ((rc = ensure(t, t->h2d_offs, (size_t)(n_docs + 1) * 8))) return rc;
@@ -1742,21 +1776,24 @@ int td_decode_device(td_tokenizer* t, const void* d_tokens, int64_t n_tokens, vo
 // decode_bytes on at most SMALL_DEC_MAX_TOKENS ids: ONE launch over pinned host buffers (td_small_decode).  Returns TD_OK, a
 // TD_E_* code, or -1: more bytes than the kernel's window holds (the general path takes the call).
 static int decode_bytes_small(td_tokenizer* t, const int32_t* tokens, int64_t n_tokens, uint8_t* out, int64_t out_capacity, int64_t* n_bytes) {
-    if (!t->small_dec_in) {
-        HIP_TRY(t, hipHostMalloc(&t->small_dec_in, SMALL_DEC_MAX_TOKENS * 4 + 64, hipHostMallocDefault));
-        HIP_TRY(t, hipHostMalloc(&t->small_dec_out, 64 + SMALL_DEC_MAX_BYTES, hipHostMallocDefault));
-        memset(t->small_dec_out, 0, 64 + SMALL_DEC_MAX_BYTES);
+    if (!t->small_dec_in.p) {  // (both or neither)
+        PinnedBuf in, out;
+        HIP_TRY(t, make_pinned(in, SMALL_DEC_MAX_TOKENS * 4 + 64));
+        HIP_TRY(t, make_pinned(out, 64 + SMALL_DEC_MAX_BYTES));
+        memset(out.p, 0, 64 + SMALL_DEC_MAX_BYTES);
+        t->small_dec_in = std::move(in);
+        t->small_dec_out = std::move(out);
     }
     int rc;
     if ((rc = own_streams(t))) return rc;
     hipStream_t s = t->s_own;
     if ((rc = order_before(t, s))) return rc;
-    memcpy(t->small_dec_in, tokens, (size_t)n_tokens * 4);
+    memcpy(t->small_dec_in.p, tokens, (size_t)n_tokens * 4);
     SmallDecArgs a;
     a.Tp = t->dTp;
-    a.tokens = (const int32_t*)t->small_dec_in;
-    a.status = (SmallStatus*)t->small_dec_out;
-    a.out = (uint8_t*)t->small_dec_out + 64;
+    a.tokens = (const int32_t*)t->small_dec_in.p;
+    a.status = (SmallStatus*)t->small_dec_out.p;
+    a.out = (uint8_t*)t->small_dec_out.p + 64;
     a.seq = ++t->small_seq;
     a.n = (int)n_tokens;
     HIP_TRY(t, launch_small_decode(a, s));
@@ -1793,7 +1830,7 @@ int td_decode_bytes(td_tokenizer* t, const int32_t* tokens, int64_t n_tokens, ui
     if (n_tokens == 0) return TD_OK;
     return locked(t, [&] {
         int rc;
-        if (n_tokens <= SMALL_DEC_MAX_TOKENS && t->small_enabled) {
+        if (n_tokens <= SMALL_DEC_MAX_TOKENS && t->opt.small_enabled) {
             rc = decode_bytes_small(t, tokens, n_tokens, out, out_capacity, n_bytes);
             if (rc != -1) return rc;
         }
@@ -1812,8 +1849,8 @@ int td_decode_bytes(td_tokenizer* t, const int32_t* tokens, int64_t n_tokens, ui
         if (rc == TD_E_BAD_TOKEN && err_pos >= 0 && err_pos < n_tokens)
             t->err = "Invalid token for decoding: " + std::to_string(tokens[err_pos]);  // reference: tiktoken.cpp:249
         if (rc) return rc;
-        if ((rc = copy_wait(t, t->h_ctl, a.chunk_pref + (n_tokens + 4095) / 4096, 8, hipMemcpyDeviceToHost, s))) return rc;
-        const int64_t total = *(const int64_t*)t->h_ctl;
+        if ((rc = copy_wait(t, t->h_ctl.p, a.chunk_pref + (n_tokens + 4095) / 4096, 8, hipMemcpyDeviceToHost, s))) return rc;
+        const int64_t total = *(const int64_t*)t->h_ctl.p;
         if (n_bytes) *n_bytes = total;
         if (total > out_capacity) { t->err = "decode capacity too small"; return (int)TD_E_CAPACITY; }
         if (total > 0 && !out) { t->err = "null out"; return (int)TD_E_INVALID; }
@@ -2035,7 +2072,7 @@ int encode_special_locked(td_tokenizer* t, const uint8_t* text, const int64_t* d
     // Batches of a MiB and more: the search runs on the device (td_special.hip; the same cuts, td_encode_device_with_special)
     // when the allowed set can be named by ids (no other special string shares an allowed one's id) and the caller does not
     // ask for the last segment (the single-string entry points do, for last_piece_token_len).
-    if (t->device_specials && !last_seg_lo && !out_starts && doc_offsets[n_docs] >= (1ll << 20) && t->H.pattern_kind != PATTERN_GENERIC && ix.count > 0) {
+    if (t->opt.device_specials && !last_seg_lo && !out_starts && doc_offsets[n_docs] >= (1ll << 20) && t->H.pattern_kind != PATTERN_GENERIC && ix.count > 0) {
         std::vector<int32_t> ids;
         bool nameable = true;
         for (const auto& e : ix.ents) {
@@ -2497,73 +2534,26 @@ int64_t td_info(const td_tokenizer* t, int what) {
 int td_set_option(td_tokenizer* t, int what, int64_t value) {
     if (!t) return TD_E_INVALID;
     std::lock_guard<std::mutex> g(t->mu);
-    if (what == TD_OPT_LONG_POOL_BYTES && value >= (1 << 20)) {
-        t->pool_bytes_opt = value;
-        return TD_OK;
-    }
+    Options& o = t->opt;
+    auto relaunch = [t] { drop_graph(t); t->has_last_key = false; return (int)TD_OK; };  // (options that change the captured launches)
+    switch (what) {
+        case TD_OPT_LONG_POOL_BYTES: if (value < (1 << 20)) break; o.pool_bytes_opt = value; return TD_OK;
 #ifdef TD_ABLATE
-    if (what == 99) {  // tuning builds only (tools/build_variant.sh -DTD_ABLATE): phase ablation, results are garbage when != 0
-        t->stop_after = (int)value;
-        return TD_OK;
-    }
+        case 99: t->stop_after = (int)value; return TD_OK;  // tuning builds only (tools/build_variant.sh -DTD_ABLATE): phase ablation, results are garbage when != 0
 #endif
-    if (what == TD_OPT_FUSED) {
-        t->fused = value != 0;
-        return TD_OK;
-    }
-    if (what == TD_OPT_DIRECT) {
-        t->direct = value != 0;
-        return TD_OK;
-    }
-    if (what == TD_OPT_DEVICE_SPECIALS) {
-        t->device_specials = value != 0;
-        return TD_OK;
-    }
-    if (what == TD_OPT_PACK_SPLIT) {
-        t->pack_split = value != 0;
-        drop_graph(t); t->has_last_key = false;
-        return TD_OK;
-    }
-    if (what == TD_OPT_SPARSE && value >= -1 && value <= 1) {
-        t->sparse_opt = (int)value;
-        drop_graph(t); t->has_last_key = false;
-        return TD_OK;
-    }
-    if (what == TD_OPT_OVERLAP) {
-        t->overlap = value != 0;
-        drop_graph(t); t->has_last_key = false;
-        return TD_OK;
-    }
-    if (what == TD_OPT_GIANT_COOP_MIN && value >= 1024) {
-        t->gp_coop_min = (uint32_t)std::min<int64_t>(value, 0x7FFFFFFF);
-        drop_graph(t); t->has_last_key = false;
-        return TD_OK;
-    }
-    if (what == TD_OPT_DEDUPE) {
-        t->dedupe = value != 0;
-        drop_graph(t); t->has_last_key = false;
-        return TD_OK;
-    }
-    if (what == TD_OPT_GRAPH) {
-        t->graphs = value != 0;
-        if (!t->graphs) { drop_graph(t); t->has_last_key = false; }
-        return TD_OK;
-    }
-    if (what == TD_OPT_PROFILE) {
-        t->profile = value != 0;
-        return TD_OK;
-    }
-    if (what == TD_OPT_PIPE_CHUNK_BYTES && value >= 4096) {
-        t->pipe_chunk_bytes = value;
-        return TD_OK;
-    }
-    if (what == TD_OPT_SMALL_PATH) {
-        t->small_enabled = value != 0;
-        return TD_OK;
-    }
-    if (what == TD_OPT_PIPE_THREADS && value >= 1 && value <= 256) {
-        t->pipe_threads = (int)value;
-        return TD_OK;
+        case TD_OPT_FUSED: o.fused = value != 0; return TD_OK;
+        case TD_OPT_DIRECT: o.direct = value != 0; return TD_OK;
+        case TD_OPT_DEVICE_SPECIALS: o.device_specials = value != 0; return TD_OK;
+        case TD_OPT_PACK_SPLIT: o.pack_split = value != 0; return relaunch();
+        case TD_OPT_SPARSE: if (value < -1 || value > 1) break; o.sparse_opt = (int)value; return relaunch();
+        case TD_OPT_OVERLAP: o.overlap = value != 0; return relaunch();
+        case TD_OPT_GIANT_COOP_MIN: if (value < 1024) break; o.gp_coop_min = (uint32_t)std::min<int64_t>(value, 0x7FFFFFFF); return relaunch();
+        case TD_OPT_DEDUPE: o.dedupe = value != 0; return relaunch();
+        case TD_OPT_GRAPH: o.graphs = value != 0; return o.graphs ? (int)TD_OK : relaunch();
+        case TD_OPT_PROFILE: t->profile = value != 0; return TD_OK;
+        case TD_OPT_PIPE_CHUNK_BYTES: if (value < 4096) break; o.pipe_chunk_bytes = value; return TD_OK;
+        case TD_OPT_SMALL_PATH: o.small_enabled = value != 0; return TD_OK;
+        case TD_OPT_PIPE_THREADS: if (value < 1 || value > 256) break; o.pipe_threads = (int)value; return TD_OK;
     }
     return TD_E_INVALID;
 }
@@ -2584,8 +2574,8 @@ int td_profile_read_ex(td_tokenizer* t, double* ms_sums, int n_segments, int64_t
                 sum[k] += ms;
             }
             ++n;
-            t->ev_free.push_back(ev);
         }
+        for (auto& ev : t->ev_pending) t->ev_free.push_back(std::move(ev));
         t->ev_pending.clear();
         for (int k = 0; k < n_segments; ++k) ms_sums[k] = k + 1 < TD_PROF_EVENTS ? sum[k] : 0.0;
         if (launches) *launches = n;
