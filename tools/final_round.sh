@@ -7,7 +7,7 @@ cd $R
 nproc > $O/host.txt; grep -m1 "model name" /proc/cpuinfo >> $O/host.txt
 timeout 900 python -m pytest tests -m gpu -x -q > $O/pytest_gpu.log 2>&1; tail -3 $O/pytest_gpu.log
 timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1; tail -1 $O/smoke.log
-( time timeout 900 python bench.py > $O/bench_default.json 2> $O/bench_default.err ) 2> $O/bench_default.time; tail -3 $O/bench_default.time
+( time timeout 900 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err ) 2> $O/bench_default.time; tail -3 $O/bench_default.time
 python - "$O/bench_default.json" <<'PY'
 import json, sys
 j = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); r = j["roofline"]
@@ -16,7 +16,7 @@ print('cpu_baseline', j.get("cpu_baseline", {}).get("value"), 'python', (j.get("
 for k, v in (j.get("configs") or {}).items():
     print(f'  {k:<34} {v.get("value")} GB/s  {v.get("ms_per_step")} ms  {v.get("verified_vs_oracle", v.get("error"))}  ({v.get("wall_s")} s)')
 PY
-timeout 400 python bench.py --gpus 2 --same-gpu --dist-backend gloo --no-cpu-baseline --steps 30 > $O/bench_2rank_same_gpu_gloo.json 2> $O/bench_2rank.err; python -c "
+timeout 400 python bench.py --full --gpus 2 --same-gpu --dist-backend gloo --no-cpu-baseline --steps 30 > $O/bench_2rank_same_gpu_gloo.json 2> $O/bench_2rank.err; python -c "
 import json,sys; j=json.loads(open('$O/bench_2rank_same_gpu_gloo.json').read().strip().splitlines()[-1]); print('2 ranks on one GPU (gloo):', j['value'], 'GB/s', j['config']['verified_vs_oracle'], j['config']['parallelism'][:60])" 2>&1 | tail -1
 bash tools/measure_workload.sh $tag english 1024 > $O/measure_english.log 2>&1; tail -14 $O/measure_english.log
 # (fabric traffic of configs 4 and 5 too, on the shipping sources; these also leave stats_<corpus>_256.txt)
@@ -32,6 +32,6 @@ timeout 200 python tools/gpu_giant.py > $O/giant_pieces.txt 2>&1; grep -v amdgpu
 # (the direct placement against the staged form on the final sources, same box and corpus)
 timeout 300 python tools/gpu_opt_ab.py english 1024 20 DIRECT=1,0 > $O/direct_ab.txt 2>&1; grep -v amdgpu $O/direct_ab.txt | tail -12
 # (the sparse launch sequence against the dense one on plain text, 128 MiB and 1024 MiB)
-for mb in 128 1024; do for sp in 1 0; do TD_SPARSE=$sp timeout 300 python bench.py --corpus english --size-mb $mb --no-cpu-baseline --no-side-configs --steps 50 2>/dev/null | python -c "
+for mb in 128 1024; do for sp in 1 0; do TD_SPARSE=$sp timeout 300 python bench.py --full --corpus english --size-mb $mb --no-cpu-baseline --no-side-configs --steps 50 2>/dev/null | python -c "
 import json,sys; j=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('english $mb MiB, TD_SPARSE=$sp:', j['value'], 'GB/s', j['ms_per_step'], 'ms', j['launch_mode']['launch_sequence'], 'plain launches', j['launch_mode']['ms_per_step_plain_launches'], 'ms; graph replay', j['launch_mode']['ms_per_step_graph_replay'], 'ms')"; done; done > $O/sequences_ab.txt 2>&1; cat $O/sequences_ab.txt
 find $O -name "*.db" -size +20M -delete
