@@ -284,6 +284,58 @@ int td_encode_batch_rows(td_tokenizer* t, const uint8_t* text, const int64_t* do
                          const td_rows_spec* spec, int32_t* out_ids, int64_t rows_capacity, int32_t* out_positions, int32_t* out_aux,
                          int64_t* counts);
 
+/* ---- whole documents packed into rows by best-fit decreasing (td_pack.hip) ------------------------------------------------
+ * td_rows_spec with layout = TD_ROWS_BESTFIT; flags 0 or TD_ROWS_TRUNCATE (TD_ROWS_DROP_LAST is invalid here).  bos / eos / pad
+ * are checked as for the other layouts.  The td_make_rows* entry points reject this layout and this flag.
+ *   Slots: document d has n_d = b + L_d + e slots, [BOS] ids [EOS] (an empty document without BOS and EOS: none, no segment).
+ *     TD_ROWS_TRUNCATE: the body is cut to min(L_d, S - b - e) ids, so the document still ends with EOS (S < b + e: TD_E_INVALID).
+ *     Otherwise (split) a document with n_d > S is cut at multiples of S of its own slots: floor(n_d / S) full chunks and a
+ *     remainder chunk of n_d mod S slots (if > 0).
+ *   Items are all chunks, sorted by length descending, then document ascending, then chunk ascending.  In that order each goes
+ *   into the row whose free slot count is the smallest one >= its length (ties: the lowest row index); if no row has room, a
+ *   new row is appended.  Rows are numbered in the order they were opened, so the full chunks are rows 0 .. F - 1 in (document,
+ *   chunk) order.  Inside a row the segments sit in placement order from slot 0 and pad_id fills the tail.
+ *   Outputs (td_pack_outputs; every field but ids may be NULL):
+ *     ids          int32 [rows * S]
+ *     positions    int32 [rows * S]  the index inside the segment (a split document's later chunks restart at 0); pad slots 0
+ *     cu_seqlens   int32 the segment boundaries over the flattened [rows * S]: every real segment and every row's pad tail is a
+ *                  segment; the last entry is rows * S.  Room: n_docs + 2 * rows_capacity + 1 entries, and rows_capacity * S < 2^31.
+ *     row_lengths  int32 [rows]  the real slots of every row
+ *     seg_docs     int64, one per cu_seqlens segment: the document, or -1 for a pad tail.  Room: n_docs + 2 * rows_capacity.
+ *   counts[4] (int64) = {rows, R (real slots), segments (pad tails included), documents cut (split or truncated)}.
+ *   Too few rows: TD_E_CAPACITY with counts[0] = the rows needed, and nothing is written to any output.  A caller who cannot
+ *   plan first may use rows <= floor(2 * T / S) + 1 with T = n_ids + n_docs * (b + e): best-fit decreasing never leaves two
+ *   rows at most half full.  n_docs < 2^31. */
+#define TD_ROWS_BESTFIT 2
+#define TD_ROWS_TRUNCATE 2 /* flags (TD_ROWS_BESTFIT only) */
+typedef struct td_pack_outputs {
+    int32_t* ids;
+    int32_t* positions;
+    int32_t* cu_seqlens;
+    int32_t* row_lengths;
+    int64_t* seg_docs;
+} td_pack_outputs;
+
+/* The counts of the packing, on the host, from tok_offsets[n_docs + 1] alone (no handle, no device).  doc_row / doc_slot (each
+ * [n_docs], may be NULL): the row and in-row slot of the document's packed chunk (its only chunk, or its remainder when split);
+ * -1 where it has none.  tok_offsets must start at 0 and not decrease. */
+int td_pack_plan(const int64_t* tok_offsets, int64_t n_docs, const td_rows_spec* spec, int64_t* counts, int64_t* doc_row,
+                 int64_t* doc_slot);
+/* Host buffers, synchronously.  tok_offsets is checked like every host entry point's offsets. */
+int td_pack_rows(td_tokenizer* t, const int32_t* ids, int64_t n_tokens, const int64_t* tok_offsets, int64_t n_docs,
+                 const td_rows_spec* spec, const td_pack_outputs* host_out, int64_t rows_capacity, int64_t* counts);
+/* Device buffers.  Unlike every other rows entry point this one SYNCHRONISES ONCE: it reads a small table of run lengths back to
+ * plan the rows, so it waits for the caller's earlier work on hip_stream.  counts (HOST memory), capacity errors and offset
+ * errors (tok_offsets decreasing or negative, tok_offsets[n_docs] > n_tokens) come back synchronously, before anything is
+ * written; the kernels that write dev_out are then enqueued on hip_stream and run asynchronously. */
+int td_pack_rows_device(td_tokenizer* t, const void* d_ids, int64_t n_tokens, const void* d_tok_offsets, int64_t n_docs,
+                        const td_rows_spec* spec, const td_pack_outputs* dev_out, int64_t rows_capacity, int64_t* counts,
+                        void* hip_stream);
+/* td_encode_batch (TD_MODE_ENCODE / TD_MODE_ORDINARY, no allowed special tokens) and td_pack_rows in one call: the ids stay on
+ * the device.  Synchronous. */
+int td_encode_batch_pack_rows(td_tokenizer* t, const uint8_t* text, const int64_t* doc_offsets, int64_t n_docs, int mode,
+                              const td_rows_spec* spec, const td_pack_outputs* host_out, int64_t rows_capacity, int64_t* counts);
+
 /* Options. */
 #define TD_OPT_LONG_POOL_BYTES 1 /* scratch for pieces longer than 64 bytes (default max(64 MiB, 2 x input)) */
 #define TD_OPT_PROFILE 2         /* 1: bracket the kernels of every td_encode_device call with HIP events on the

@@ -21,8 +21,9 @@ TD_MODE_ORDINARY = 1
 TD_E_INVALID = 1
 TD_E_BAD_TOKEN = 8
 TD_UNIT_BYTES, TD_UNIT_CHARS = 0, 1
-TD_ROWS_CONCAT, TD_ROWS_PAD = 0, 1
+TD_ROWS_CONCAT, TD_ROWS_PAD, TD_ROWS_BESTFIT = 0, 1, 2
 TD_ROWS_DROP_LAST = 1
+TD_ROWS_TRUNCATE = 2
 TD_INFO_N_PAIRS, TD_INFO_MERGE_CLOSED, TD_INFO_MAX_ID, TD_INFO_TILE_BYTES = 1, 2, 3, 4
 TD_INFO_WORKSPACE_BYTES, TD_INFO_N_SPECIAL, TD_INFO_LONG_PIECES, TD_INFO_FAR_PIECES = 5, 6, 7, 8
 TD_OPT_LONG_POOL_BYTES = 1
@@ -56,6 +57,7 @@ EXPORTS = [
     "td_comm_unique_id", "td_comm_create", "td_comm_destroy", "td_comm_gather_counts", "td_comm_bases", "td_comm_gather_tokens",
     "td_comm_last_error", "td_encode_device_with_special", "td_token_starts", "td_token_starts_device", "td_encode_batch_with_starts",
     "td_encode_device_with_starts", "td_make_rows_device", "td_make_rows", "td_encode_batch_rows",
+    "td_pack_plan", "td_pack_rows", "td_pack_rows_device", "td_encode_batch_pack_rows",
 ]
 
 
@@ -118,6 +120,14 @@ def load_library():
     lib.td_make_rows.argtypes = [vp, vp, i64, vp, i64, vp, vp, i64, vp, vp, vp]
     lib.td_encode_batch_rows.restype = i32
     lib.td_encode_batch_rows.argtypes = [vp, vp, vp, i64, i32, vp, vp, i64, vp, vp, vp]
+    lib.td_pack_plan.restype = i32
+    lib.td_pack_plan.argtypes = [vp, i64, vp, vp, vp, vp]
+    lib.td_pack_rows.restype = i32
+    lib.td_pack_rows.argtypes = [vp, vp, i64, vp, i64, vp, vp, i64, vp]
+    lib.td_pack_rows_device.restype = i32
+    lib.td_pack_rows_device.argtypes = [vp, vp, i64, vp, i64, vp, vp, i64, vp, vp]
+    lib.td_encode_batch_pack_rows.restype = i32
+    lib.td_encode_batch_pack_rows.argtypes = [vp, vp, vp, i64, i32, vp, vp, i64, vp]
     lib.td_comm_unique_id.restype = i32
     lib.td_comm_unique_id.argtypes = [vp]
     lib.td_comm_create.restype = i32
@@ -224,6 +234,41 @@ def rows_capacity_of(spec: RowsSpec, n_ids: int, n_docs: int) -> int:
         return n_docs
     t = n_ids + n_docs * ((spec.bos_id >= 0) + (spec.eos_id >= 0))
     return t // spec.seq_len if spec.flags & TD_ROWS_DROP_LAST else -(-t // spec.seq_len)
+
+
+class PackOutputs(ctypes.Structure):
+    """td_pack_outputs (include/tokendagger_hip.h): addresses, 0 / None for an output not wanted."""
+    _fields_ = [("ids", ctypes.c_void_p), ("positions", ctypes.c_void_p), ("cu_seqlens", ctypes.c_void_p), ("row_lengths", ctypes.c_void_p),
+                ("seg_docs", ctypes.c_void_p)]
+
+
+def pack_spec(seq_len: int, bos: int = -1, eos: int = -1, pad: int = 0, truncate: bool = False) -> RowsSpec:
+    """A TD_ROWS_BESTFIT spec: whole documents packed into rows by best-fit decreasing."""
+    return RowsSpec(TD_ROWS_BESTFIT, seq_len, bos, eos, pad, TD_ROWS_TRUNCATE if truncate else 0)
+
+
+def pack_rows_capacity_of(spec: RowsSpec, n_ids: int, n_docs: int) -> int:
+    """A bound on the rows td_pack_rows writes without planning first: floor(2 T / S) + 1, T = n_ids + n_docs * (b + e)."""
+    t = n_ids + n_docs * ((spec.bos_id >= 0) + (spec.eos_id >= 0))
+    return 2 * t // spec.seq_len + 1
+
+
+def pack_plan(tok_offsets, spec: RowsSpec, placement: bool = False):
+    """td_pack_plan (host only, no device): counts int64[4] = rows, real slots, segments, documents cut; with placement=True
+    also (doc_row, doc_slot) int64[n_docs], where each document's packed chunk sits (-1: none)."""
+    lib = load_library()
+    o = np.ascontiguousarray(tok_offsets, dtype=np.int64)
+    n_docs = len(o) - 1
+    if n_docs < 0:
+        raise ValueError("tok_offsets must have n_docs + 1 entries")
+    counts = np.zeros(4, dtype=np.int64)
+    row = np.empty(max(n_docs, 1), dtype=np.int64) if placement else None
+    slot = np.empty(max(n_docs, 1), dtype=np.int64) if placement else None
+    rc = lib.td_pack_plan(o.ctypes.data, n_docs, ctypes.byref(spec), counts.ctypes.data, row.ctypes.data if placement else None,
+                          slot.ctypes.data if placement else None)
+    if rc != TD_OK:
+        raise TokenDaggerHipError(rc, "td_pack_plan: invalid spec or tok_offsets")
+    return (counts, row[:n_docs], slot[:n_docs]) if placement else counts
 
 
 def _as_u8(data) -> np.ndarray:
@@ -512,6 +557,72 @@ class HipTokenizer:
                                                    ctypes.byref(spec), out.ctypes.data, rows, pos.ctypes.data if pos is not None else None,
                                                    ax.ctypes.data if ax is not None else None, counts.ctypes.data))
         return self._rows_result(spec, out, pos, ax, counts, n_docs)
+
+    # ---- best-fit rows (TD_ROWS_BESTFIT) --------------------------------------------------------------------
+    @staticmethod
+    def _pack_buffers(spec: RowsSpec, rows: int, n_docs: int, positions: bool, cu_seqlens: bool, lengths: bool, docs: bool):
+        S = spec.seq_len
+        slots = max(rows * S, 1)
+        nseg = max(n_docs + 2 * rows + 1, 1)
+        b = [np.empty(slots, dtype=np.int32), np.empty(slots, dtype=np.int32) if positions else None,
+             np.empty(nseg, dtype=np.int32) if cu_seqlens else None, np.empty(max(rows, 1), dtype=np.int32) if lengths else None,
+             np.empty(nseg, dtype=np.int64) if docs else None]
+        return b, PackOutputs(*[x.ctypes.data if x is not None else None for x in b])
+
+    @staticmethod
+    def _pack_result(spec: RowsSpec, b, counts):
+        r, S, nseg = int(counts[0]), spec.seq_len, int(counts[2])
+        ids, pos, cu, lens, docs = b
+        return (ids[:r * S].reshape(r, S).copy(), pos[:r * S].reshape(r, S).copy() if pos is not None else None,
+                cu[:nseg + 1].copy() if cu is not None else None, lens[:r].copy() if lens is not None else None,
+                docs[:nseg].copy() if docs is not None else None, counts)
+
+    def pack_rows(self, ids, tok_offsets, spec: RowsSpec, positions: bool = False, cu_seqlens: bool = True, lengths: bool = False,
+                  docs: bool = False, rows_capacity: int | None = None):
+        """td_pack_rows -> (ids int32[rows, S], positions int32[rows, S] | None, cu_seqlens int32[segs + 1] | None,
+        row_lengths int32[rows] | None, seg_docs int64[segs] | None, counts int64[4]).  The default capacity is the exact rows
+        (td_pack_plan)."""
+        t = np.ascontiguousarray(ids, dtype=np.int32)
+        o = np.ascontiguousarray(tok_offsets, dtype=np.int64)
+        n_docs = len(o) - 1
+        rows = rows_capacity if rows_capacity is not None else int(pack_plan(o, spec)[0])
+        b, outs = self._pack_buffers(spec, rows, n_docs, positions, cu_seqlens, lengths, docs)
+        counts = np.zeros(4, dtype=np.int64)
+        self._check(self._lib.td_pack_rows(self._h, t.ctypes.data if len(t) else None, len(t), o.ctypes.data, n_docs, ctypes.byref(spec),
+                                           ctypes.byref(outs), rows, counts.ctypes.data))
+        return self._pack_result(spec, b, counts)
+
+    def pack_rows_device(self, d_ids: int, n_tokens: int, d_tok_offsets: int, n_docs: int, spec: RowsSpec, d_out_ids: int,
+                         rows_capacity: int, d_positions: int = 0, d_cu_seqlens: int = 0, d_row_lengths: int = 0, d_seg_docs: int = 0,
+                         stream: int = 0) -> np.ndarray:
+        """td_pack_rows_device: raw device pointers.  Synchronises once on `stream` to plan; returns counts int64[4] (host);
+        the output kernels then run asynchronously on `stream`."""
+        outs = PackOutputs(d_out_ids or None, d_positions or None, d_cu_seqlens or None, d_row_lengths or None, d_seg_docs or None)
+        counts = np.zeros(4, dtype=np.int64)
+        rc = self._lib.td_pack_rows_device(self._h, d_ids or None, n_tokens, d_tok_offsets, n_docs, ctypes.byref(spec), ctypes.byref(outs),
+                                           rows_capacity, counts.ctypes.data, stream or None)
+        try:
+            self._check(rc)
+        except TokenDaggerHipError as ex:
+            ex.counts = counts  # (TD_E_CAPACITY: counts[0] = the rows needed)
+            raise
+        return counts
+
+    def encode_batch_pack_rows(self, text, doc_offsets, spec: RowsSpec, mode: int = TD_MODE_ENCODE, positions: bool = False,
+                               cu_seqlens: bool = True, lengths: bool = False, docs: bool = False, rows_capacity: int | None = None):
+        """td_encode_batch_pack_rows: encode + td_pack_rows in one call; same result tuple as pack_rows.  The default capacity is
+        the bound for the most ids the text can give (one per byte)."""
+        buf = _as_u8(text)
+        offs = np.ascontiguousarray(doc_offsets, dtype=np.int64)
+        n_docs = len(offs) - 1
+        rows = rows_capacity if rows_capacity is not None else pack_rows_capacity_of(spec, int(offs[-1]) if len(offs) else 0, n_docs)
+        if rows_capacity is None and cu_seqlens:
+            rows = min(rows, ((1 << 31) - 1) // spec.seq_len)  # (cu_seqlens entries are int32)
+        b, outs = self._pack_buffers(spec, rows, n_docs, positions, cu_seqlens, lengths, docs)
+        counts = np.zeros(4, dtype=np.int64)
+        self._check(self._lib.td_encode_batch_pack_rows(self._h, buf.ctypes.data if len(buf) else None, offs.ctypes.data, n_docs, mode,
+                                                        ctypes.byref(spec), ctypes.byref(outs), rows, counts.ctypes.data))
+        return self._pack_result(spec, b, counts)
 
     def device_status_pos(self, stream: int = 0) -> tuple[int, int]:
         """td_device_status without raising: (code, err_pos)."""

@@ -609,6 +609,70 @@ public:
         });
     }
 
+    // ---- best-fit rows (td_pack_rows, td_encode_batch_pack_rows) ------------------------------------------------------------------
+    // -> (ids int32[rows, S], positions int32[rows, S], cu_seqlens int32[segs + 1], row_lengths int32[rows], seg_docs int64[segs],
+    //     counts int64[4]); an output not asked for is None
+    template <class F>
+    py::tuple pack_call(const td_rows_spec& sp, int64_t rows_cap, int64_t n_docs, bool positions, bool cu, bool lengths, bool docs, F&& call) {
+        const int64_t S = sp.seq_len > 0 ? sp.seq_len : 1, slots = std::max<int64_t>(rows_cap * S, 1);
+        const int64_t nseg = std::max<int64_t>(n_docs + 2 * rows_cap + 1, 1);
+        py::array_t<int32_t> ids(slots), pos(positions ? slots : 0), cs(cu ? nseg : 0), ls(lengths ? std::max<int64_t>(rows_cap, 1) : 0);
+        py::array_t<int64_t> ds(docs ? nseg : 0), counts(4);
+        int rc;
+        {
+            td_pack_outputs o{ids.mutable_data(), positions ? pos.mutable_data() : nullptr, cu ? cs.mutable_data() : nullptr,
+                              lengths ? ls.mutable_data() : nullptr, docs ? ds.mutable_data() : nullptr};
+            int64_t* cp = counts.mutable_data();
+            py::gil_scoped_release rel;
+            rc = call(&o, cp);
+        }
+        if (rc != TD_OK) fail();
+        const int64_t rows = counts.data()[0], segs = counts.data()[2];
+        ids.resize({(py::ssize_t)(rows * S)}, false);
+        py::object p = py::none(), c = py::none(), l = py::none(), d = py::none();
+        if (positions) {
+            pos.resize({(py::ssize_t)(rows * S)}, false);
+            p = pos.attr("reshape")(rows, S);
+        }
+        if (cu) { cs.resize({(py::ssize_t)(segs + 1)}, false); c = cs; }
+        if (lengths) { ls.resize({(py::ssize_t)rows}, false); l = ls; }
+        if (docs) { ds.resize({(py::ssize_t)segs}, false); d = ds; }
+        return py::make_tuple(ids.attr("reshape")(rows, S), p, c, l, d, counts);
+    }
+    py::tuple ids_to_packed_rows(py::array_t<int32_t, py::array::c_style | py::array::forcecast> ids,
+                                 py::array_t<int64_t, py::array::c_style | py::array::forcecast> tok_offsets, int64_t seq_len, int64_t bos,
+                                 int64_t eos, int64_t pad, bool truncate, bool positions, bool cu, bool lengths, bool docs) {
+        const int64_t n_docs = (int64_t)tok_offsets.size() - 1;
+        if (n_docs < 0) throw TiktokenError("tok_offsets must have n_docs+1 entries");
+        const td_rows_spec sp{TD_ROWS_BESTFIT, seq_len, bos, eos, pad, truncate ? TD_ROWS_TRUNCATE : 0};
+        int64_t plan[4] = {0, 0, 0, 0};
+        const int64_t* op = tok_offsets.data();
+        if (td_pack_plan(op, n_docs, &sp, plan, nullptr, nullptr) != TD_OK) throw TiktokenError("invalid seq_len / flags or tok_offsets");
+        const int64_t cap = plan[0], n = (int64_t)ids.size();
+        const int32_t* tp = ids.data();
+        return pack_call(sp, cap, n_docs, positions, cu, lengths, docs, [&](const td_pack_outputs* o, int64_t* cp) {
+            return td_pack_rows(h_, tp, n, op, n_docs, &sp, o, cap, cp);
+        });
+    }
+    py::tuple encode_batch_numpy_packed_rows(py::array_t<uint8_t, py::array::c_style | py::array::forcecast> text,
+                                             py::array_t<int64_t, py::array::c_style | py::array::forcecast> offsets, int64_t seq_len,
+                                             int64_t bos, int64_t eos, int64_t pad, bool truncate, bool positions, bool cu, bool lengths,
+                                             bool docs, int mode) {
+        const int64_t n_docs = (int64_t)offsets.size() - 1;
+        if (n_docs < 0) throw TiktokenError("offsets must have n_docs+1 entries");
+        if (offsets.data()[n_docs] > (int64_t)text.size()) throw TiktokenError("offsets exceed the text buffer");
+        const td_rows_spec sp{TD_ROWS_BESTFIT, seq_len, bos, eos, pad, truncate ? TD_ROWS_TRUNCATE : 0};
+        // (at most one id per byte; the bound of include/tokendagger_hip.h)
+        const int64_t T = offsets.data()[n_docs] + n_docs * ((bos >= 0) + (eos >= 0));
+        int64_t cap = seq_len > 0 ? 2 * T / seq_len + 1 : 0;
+        if (cu && seq_len > 0) cap = std::min<int64_t>(cap, (((int64_t)1 << 31) - 1) / seq_len);  // (cu_seqlens entries are int32)
+        const uint8_t* tp = text.data();
+        const int64_t* op = offsets.data();
+        return pack_call(sp, cap, n_docs, positions, cu, lengths, docs, [&](const td_pack_outputs* o, int64_t* cp) {
+            return td_encode_batch_pack_rows(h_, tp, op, n_docs, mode, &sp, o, cap, cp);
+        });
+    }
+
     // list[str] in, list[list[int]] out through ONE device batch (PackedTexts / IntCache above)
     py::list encode_batch(const py::sequence& texts, int mode) {
         PackedTexts in(texts);
@@ -770,6 +834,12 @@ PYBIND11_MODULE(_tokendagger_core, m) {
         .def("ids_to_rows", &CoreBPE::ids_to_rows, py::arg("ids"), py::arg("tok_offsets"), py::arg("seq_len"), py::arg("layout") = TD_ROWS_CONCAT,
              py::arg("bos") = -1, py::arg("eos") = -1, py::arg("pad") = 0, py::arg("drop_last") = false, py::arg("positions") = false,
              py::arg("aux") = true)
+        .def("ids_to_packed_rows", &CoreBPE::ids_to_packed_rows, py::arg("ids"), py::arg("tok_offsets"), py::arg("seq_len"), py::arg("bos") = -1,
+             py::arg("eos") = -1, py::arg("pad") = 0, py::arg("truncate") = false, py::arg("positions") = false, py::arg("cu_seqlens") = true,
+             py::arg("lengths") = true, py::arg("docs") = false)
+        .def("encode_batch_numpy_packed_rows", &CoreBPE::encode_batch_numpy_packed_rows, py::arg("text"), py::arg("offsets"), py::arg("seq_len"),
+             py::arg("bos") = -1, py::arg("eos") = -1, py::arg("pad") = 0, py::arg("truncate") = false, py::arg("positions") = false,
+             py::arg("cu_seqlens") = true, py::arg("lengths") = true, py::arg("docs") = false, py::arg("mode") = TD_MODE_ENCODE)
         .def("decode_batch", &CoreBPE::decode_batch, py::arg("docs"))
         .def("encode_batch_special", &CoreBPE::encode_batch_special, py::arg("texts"), py::arg("allowed_special"))
         .def("token_bytes", &CoreBPE::token_bytes, py::arg("id"))

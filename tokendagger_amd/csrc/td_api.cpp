@@ -19,6 +19,7 @@
 #include "td_kernels.h"
 #include "td_offsets.h"
 #include "td_rows.h"
+#include "td_pack.h"
 #include "td_regex.h"
 #include "td_tables.h"
 #include "td_vocab.h"
@@ -291,6 +292,10 @@ struct td_tokenizer {
     // training rows (td_rows.hip): the cu_seqlens scan's status words, the host entry points' outputs on the device
     DevBuf rows_scan, rows_out, rows_pos, rows_aux, rows_counts;
     bool rows_last = false;  // the last call launched the rows kernels (the unit of a TD_E_CAPACITY position)
+    // best-fit packing (td_pack.hip): the items, the sort's and the scan's scratch, the header + runs read back, the plan uploaded,
+    // the segments; the host entry points' row lengths and segment documents on the device
+    DevBuf pack_key, pack_val, pack_key2, pack_val2, pack_full, pack_pref, pack_tmp, pack_hdr, pack_plan, pack_seg, pack_len, pack_docs;
+    PinnedBuf pack_h, pack_up;
     // The library never touches the legacy (null) stream on its own: a legacy-stream operation is illegal while ANY thread of
     // the process captures a blocking stream, and synchronises with every blocking stream of every other thread.  Copies the
     // host waits for, table uploads and the host-buffer entry points run on `s_own` (non-blocking, private to the handle);
@@ -989,6 +994,200 @@ int rows_capacity_fail(td_tokenizer* t, int64_t rows, int64_t* counts) {
     counts[1] = counts[2] = counts[3] = 0;
     t->err = "output capacity too small: " + std::to_string(rows) + " rows needed";
     return TD_E_CAPACITY;
+}
+
+// ---- best-fit packing (td_pack.hip) ------------------------------------------------------------------------------------------
+// The checks of a TD_ROWS_BESTFIT spec that need no handle.  want_cu: cu_seqlens requested.
+const char* pack_spec_error(const td_rows_spec* sp, int64_t rows_capacity, bool want_cu) {
+    if (!sp) return "null td_rows_spec";
+    if (sp->layout != TD_ROWS_BESTFIT) return "layout must be TD_ROWS_BESTFIT";
+    if (sp->seq_len < 1 || sp->seq_len > INT32_MAX) return "seq_len must be in 1 .. 2^31 - 1";
+    if (sp->flags & ~(int64_t)TD_ROWS_TRUNCATE) return "flags must be 0 or TD_ROWS_TRUNCATE";
+    if (sp->pad_id < INT32_MIN || sp->pad_id > INT32_MAX) return "pad_id must be an int32";
+    const int64_t k = (sp->bos_id >= 0) + (sp->eos_id >= 0);
+    if ((sp->flags & TD_ROWS_TRUNCATE) && sp->seq_len < k) return "TD_ROWS_TRUNCATE needs seq_len >= the BOS and EOS slots";
+    if (rows_capacity < 0) return "rows_capacity must be >= 0";
+    if (rows_capacity > ((int64_t)1 << 62) / sp->seq_len) return "rows_capacity * seq_len is too large";
+    if (want_cu && rows_capacity * sp->seq_len >= ((int64_t)1 << 31))
+        return "cu_seqlens entries are int32: rows_capacity * seq_len must stay below 2^31";
+    return nullptr;
+}
+
+const char* pack_args_error(const td_rows_spec* sp, int64_t n_docs, int64_t rows_capacity, const td_pack_outputs* o) {
+    if (!o) return "null td_pack_outputs";
+    if (n_docs > INT32_MAX) return "n_docs must be below 2^31";
+    if (rows_capacity > 0 && !o->ids) return "null ids output";
+    return pack_spec_error(sp, rows_capacity, o->cu_seqlens != nullptr);
+}
+
+// A document's slots after truncation, its full chunks and its remainder (the one item that is not a full row).
+struct PackDoc {
+    int64_t n, full, rem;
+    bool cut;
+};
+PackDoc pack_doc(const td_rows_spec* sp, int64_t L) {
+    const int64_t S = sp->seq_len, b = sp->bos_id >= 0, e = sp->eos_id >= 0;
+    PackDoc p;
+    if (sp->flags & TD_ROWS_TRUNCATE) {
+        const int64_t body = std::min(L, S - b - e);
+        p.n = b + body + e;
+        p.full = p.n == S;
+        p.rem = p.n == S ? 0 : p.n;
+        p.cut = body < L;
+    } else {
+        p.n = b + L + e;
+        p.full = p.n / S;
+        p.rem = p.n % S;
+        p.cut = p.n > S;
+    }
+    return p;
+}
+
+int ensure_pinned(td_tokenizer* t, PinnedBuf& b, size_t bytes) {  // (only after a synchronisation: nothing reads the old one)
+    if (b.p && b.cap >= bytes) return TD_OK;
+    HIP_TRY(t, make_pinned(b, bytes + bytes / 8 + 256));
+    return TD_OK;
+}
+
+// The device pipeline up to the plan: items, scan, sort and run-length encode on `s`, one read-back and synchronisation, the
+// host plan.  Fills `a` (everything but the outputs and the segment arrays) and counts.  Offsets that are negative, decreasing
+// or beyond n_tokens: TD_E_INVALID, nothing launched behind the read-back.
+int pack_prepare(td_tokenizer* t, const void* d_ids, int64_t n_tokens, const void* d_toff, int64_t n_docs, const td_rows_spec* sp,
+                 hipStream_t s, PackArgs& a, PackPlan& plan, int64_t* counts) {
+    int rc;
+    if ((rc = order_before(t, s))) return rc;
+    memset(&a, 0, sizeof a);
+    a.ids = (const int32_t*)d_ids;
+    a.n_tokens = n_tokens;
+    a.tok_off = (const int64_t*)d_toff;
+    a.n_docs = n_docs;
+    a.S = sp->seq_len;
+    a.b = sp->bos_id >= 0;
+    a.e = sp->eos_id >= 0;
+    a.truncate = (sp->flags & TD_ROWS_TRUNCATE) ? 1 : 0;
+    a.bos = a.b ? (int32_t)sp->bos_id : 0;
+    a.eos = a.e ? (int32_t)sp->eos_id : 0;
+    a.pad = (int32_t)sp->pad_id;
+    const size_t nd = (size_t)std::max<int64_t>(n_docs, 1);
+    for (DevBuf* b : {&t->pack_key, &t->pack_val, &t->pack_key2, &t->pack_val2})
+        if ((rc = ensure(t, *b, nd * 4))) return rc;
+    if ((rc = ensure(t, t->pack_full, nd * 8)) || (rc = ensure(t, t->pack_pref, nd * 8))) return rc;
+    if ((rc = ensure(t, t->pack_hdr, PACK_HDR * 8 + nd * 8))) return rc;
+    a.key = (uint32_t*)t->pack_key.p;
+    a.val = (uint32_t*)t->pack_val.p;
+    a.full = (int64_t*)t->pack_full.p;
+    a.hdr = (long long*)t->pack_hdr.p;
+    uint32_t* runs_key = (uint32_t*)(a.hdr + PACK_HDR);
+    uint32_t* runs_cnt = runs_key + nd;
+    size_t tb = 0;
+    HIP_TRY(t, pack_sort_runs(nullptr, tb, a, (uint32_t*)t->pack_key2.p, (uint32_t*)t->pack_val2.p, (int64_t*)t->pack_pref.p, runs_key, runs_cnt, s));
+    if ((rc = ensure(t, t->pack_tmp, tb))) return rc;
+    HIP_TRY(t, hipMemsetAsync(a.hdr, 0, PACK_HDR * 8, s));
+    HIP_TRY(t, launch_pack_items(a, s));
+    HIP_TRY(t, pack_sort_runs(t->pack_tmp.p, tb, a, (uint32_t*)t->pack_key2.p, (uint32_t*)t->pack_val2.p, (int64_t*)t->pack_pref.p, runs_key, runs_cnt, s));
+    // the header and the first runs in one round trip
+    const int64_t k0 = std::min<int64_t>(n_docs, PACK_RUNS_FIRST);
+    if ((rc = ensure_pinned(t, t->pack_h, PACK_HDR * 8 + (size_t)k0 * 8))) return rc;
+    long long* h = (long long*)t->pack_h.p;
+    uint32_t* h_key = (uint32_t*)(h + PACK_HDR);
+    uint32_t* h_cnt = h_key + k0;
+    HIP_TRY(t, hipMemcpyAsync(h, a.hdr, PACK_HDR * 8, hipMemcpyDeviceToHost, s));
+    if (k0 > 0) {
+        HIP_TRY(t, hipMemcpyAsync(h_key, runs_key, (size_t)k0 * 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(t, hipMemcpyAsync(h_cnt, runs_cnt, (size_t)k0 * 4, hipMemcpyDeviceToHost, s));
+    }
+    HIP_TRY(t, hipStreamSynchronize(s));
+    if (h[PH_ERR]) {
+        t->err = "tok_offsets: document " + std::to_string(n_docs - h[PH_ERR_DOC]) +
+                 " has offsets that are negative, decreasing or beyond n_tokens";
+        return TD_E_INVALID;
+    }
+    const int64_t n_runs = (int64_t)(uint32_t)h[PH_RUNS];
+    std::vector<uint32_t> more_key, more_cnt;
+    if (n_runs > k0) {  // (S > PACK_RUNS_FIRST and that many distinct lengths)
+        more_key.resize(n_runs - k0);
+        more_cnt.resize(n_runs - k0);
+        if ((rc = copy_wait(t, more_key.data(), runs_key + k0, (size_t)(n_runs - k0) * 4, hipMemcpyDeviceToHost, s))) return rc;
+        if ((rc = copy_wait(t, more_cnt.data(), runs_cnt + k0, (size_t)(n_runs - k0) * 4, hipMemcpyDeviceToHost, s))) return rc;
+    }
+    std::vector<int64_t> lens, cnts;
+    for (int64_t r = 0; r < n_runs; ++r) {
+        const uint32_t key = r < k0 ? h_key[r] : more_key[r - k0];
+        if ((int64_t)key == a.S) continue;  // documents without a remainder item
+        lens.push_back(a.S - (int64_t)key);
+        cnts.push_back(r < k0 ? h_cnt[r] : more_cnt[r - k0]);
+    }
+    pack_plan_runs(a.S, h[PH_FULL], h[PH_REAL], lens.data(), cnts.data(), (int64_t)lens.size(), plan);
+    a.full_rows = plan.full;
+    a.n_mixed = (int64_t)plan.fill.size();
+    a.n_items = h[PH_ITEMS];
+    a.rows = plan.rows;
+    a.segs = plan.segs;
+    a.pref = (const int64_t*)t->pack_pref.p;
+    a.sorted_doc = (const uint32_t*)t->pack_val2.p;
+    counts[0] = plan.rows;
+    counts[1] = plan.real;
+    counts[2] = plan.segs;
+    counts[3] = h[PH_CUT];
+    return TD_OK;
+}
+
+// Uploads the plan and enqueues td_pack_segments + td_pack_slots into the outputs of o (device pointers).
+int pack_emit(td_tokenizer* t, PackArgs& a, const PackPlan& plan, const td_pack_outputs& o, hipStream_t s) {
+    int rc;
+    const size_t n_pl = plan.pl.size(), n_m = plan.fill.size();
+    const size_t up = n_pl * sizeof(PackPlacement) + (n_m + n_m + 1) * 8;
+    if ((rc = ensure_pinned(t, t->pack_up, up))) return rc;
+    if ((rc = ensure(t, t->pack_plan, up))) return rc;
+    char* hp = (char*)t->pack_up.p;
+    if (n_pl) memcpy(hp, plan.pl.data(), n_pl * sizeof(PackPlacement));
+    if (n_m) memcpy(hp + n_pl * sizeof(PackPlacement), plan.fill.data(), n_m * 8);
+    memcpy(hp + n_pl * sizeof(PackPlacement) + n_m * 8, plan.seg0.data(), (n_m + 1) * 8);
+    HIP_TRY(t, hipMemcpyAsync(t->pack_plan.p, hp, up, hipMemcpyHostToDevice, s));
+    const char* dp = (const char*)t->pack_plan.p;
+    a.pl = (const PackPlacement*)dp;
+    a.n_pl = (int64_t)n_pl;
+    a.fill = (const int64_t*)(dp + n_pl * sizeof(PackPlacement));
+    a.seg0 = a.fill + n_m;
+    const size_t ns = (size_t)plan.segs + 1;
+    if ((rc = ensure(t, t->pack_seg, ns * 8 * 3))) return rc;
+    a.seg_start = (int64_t*)t->pack_seg.p;
+    a.seg_doc = a.seg_start + ns;
+    a.seg_q0 = a.seg_doc + ns;
+    a.out = o.ids;
+    a.pos = o.positions;
+    a.cu = o.cu_seqlens;
+    a.lengths = o.row_lengths;
+    a.docs = o.seg_docs;
+    HIP_TRY(t, launch_pack_outputs(a, s));
+    return order_after(t, s);
+}
+
+// Host entry points: packs ids already on the device into the handle's buffers, then copies them into host_out.
+int pack_to_host(td_tokenizer* t, const void* d_ids, int64_t n_ids, const void* d_toff, int64_t n_docs, const td_rows_spec* sp,
+                 const td_pack_outputs& ho, int64_t cap, int64_t* counts, hipStream_t s) {
+    int rc;
+    PackArgs a;
+    PackPlan plan;
+    if ((rc = pack_prepare(t, d_ids, n_ids, d_toff, n_docs, sp, s, a, plan, counts))) return rc;
+    if (plan.rows > cap) return rows_capacity_fail(t, plan.rows, counts);
+    const size_t slots = (size_t)std::max<int64_t>(plan.rows * sp->seq_len, 1), ns = (size_t)plan.segs + 1;
+    td_pack_outputs d{};
+    if ((rc = ensure(t, t->rows_out, slots * 4))) return rc;
+    d.ids = (int32_t*)t->rows_out.p;
+    if (ho.positions) { if ((rc = ensure(t, t->rows_pos, slots * 4))) return rc; d.positions = (int32_t*)t->rows_pos.p; }
+    if (ho.cu_seqlens) { if ((rc = ensure(t, t->rows_aux, ns * 4))) return rc; d.cu_seqlens = (int32_t*)t->rows_aux.p; }
+    if (ho.row_lengths) { if ((rc = ensure(t, t->pack_len, (size_t)std::max<int64_t>(plan.rows, 1) * 4))) return rc; d.row_lengths = (int32_t*)t->pack_len.p; }
+    if (ho.seg_docs) { if ((rc = ensure(t, t->pack_docs, ns * 8))) return rc; d.seg_docs = (int64_t*)t->pack_docs.p; }
+    if ((rc = pack_emit(t, a, plan, d, s))) return rc;
+    const size_t n_slots = (size_t)(plan.rows * sp->seq_len);
+    if ((rc = copy_wait(t, ho.ids, d.ids, n_slots * 4, hipMemcpyDeviceToHost, s))) return rc;
+    if (ho.positions && (rc = copy_wait(t, ho.positions, d.positions, n_slots * 4, hipMemcpyDeviceToHost, s))) return rc;
+    if (ho.cu_seqlens && (rc = copy_wait(t, ho.cu_seqlens, d.cu_seqlens, ns * 4, hipMemcpyDeviceToHost, s))) return rc;
+    if (ho.row_lengths && (rc = copy_wait(t, ho.row_lengths, d.row_lengths, (size_t)plan.rows * 4, hipMemcpyDeviceToHost, s))) return rc;
+    if (ho.seg_docs && (rc = copy_wait(t, ho.seg_docs, d.seg_docs, (size_t)plan.segs * 8, hipMemcpyDeviceToHost, s))) return rc;
+    HIP_TRY(t, hipStreamSynchronize(s));  // (nothing copied at all: the kernels are still done when the call returns)
+    return TD_OK;
 }
 
 }  // namespace
@@ -2505,6 +2704,123 @@ int td_encode_batch_rows(td_tokenizer* t, const uint8_t* text, const int64_t* do
         const int64_t rows = rows_needed(spec, total, n_docs);
         if (rows > rows_capacity) return rows_capacity_fail(t, rows, counts);
         return rows_to_host(t, t->d_tokens.p, dev_cap, t->d_offsets.p, n_docs, spec, rows, out_ids, out_positions, out_aux, counts, s);
+    });
+}
+
+int td_pack_plan(const int64_t* tok_offsets, int64_t n_docs, const td_rows_spec* spec, int64_t* counts, int64_t* doc_row,
+                 int64_t* doc_slot) {
+    if (!tok_offsets || n_docs < 0 || n_docs > INT32_MAX || !counts || pack_spec_error(spec, 0, false)) return TD_E_INVALID;
+    if (tok_offsets[0] != 0) return TD_E_INVALID;
+    for (int64_t d = 0; d < n_docs; ++d)
+        if (tok_offsets[d + 1] < tok_offsets[d]) return TD_E_INVALID;
+    const int64_t S = spec->seq_len;
+    std::vector<int64_t> rem((size_t)n_docs), order;
+    int64_t F = 0, R = 0, cut = 0;
+    for (int64_t d = 0; d < n_docs; ++d) {
+        const PackDoc p = pack_doc(spec, tok_offsets[d + 1] - tok_offsets[d]);
+        if (doc_row) doc_row[d] = p.full == 1 && p.rem == 0 ? F : -1;  // (a document that is exactly one full row)
+        if (doc_slot) doc_slot[d] = p.full == 1 && p.rem == 0 ? 0 : -1;
+        rem[d] = p.rem;
+        F += p.full;
+        R += p.n;
+        cut += p.cut;
+        if (p.rem) order.push_back(d);
+    }
+    std::stable_sort(order.begin(), order.end(), [&](int64_t x, int64_t y) { return rem[x] > rem[y]; });
+    std::vector<int64_t> lens, cnts;
+    for (const int64_t d : order) {
+        if (lens.empty() || lens.back() != rem[d]) { lens.push_back(rem[d]); cnts.push_back(0); }
+        ++cnts.back();
+    }
+    PackPlan plan;
+    pack_plan_runs(S, F, R, lens.data(), cnts.data(), (int64_t)lens.size(), plan);
+    if (doc_row || doc_slot)
+        for (const PackPlacement& p : plan.pl)
+            for (int64_t j = 0; j < p.count; ++j) {
+                const int64_t d = order[p.first_item + j];
+                if (doc_row) doc_row[d] = p.row;
+                if (doc_slot) doc_slot[d] = p.slot + j * p.len;
+            }
+    counts[0] = plan.rows;
+    counts[1] = R;
+    counts[2] = plan.segs;
+    counts[3] = cut;
+    return TD_OK;
+}
+
+int td_pack_rows(td_tokenizer* t, const int32_t* ids, int64_t n_tokens, const int64_t* tok_offsets, int64_t n_docs,
+                 const td_rows_spec* spec, const td_pack_outputs* host_out, int64_t rows_capacity, int64_t* counts) {
+    if (!t || !spec || !host_out || n_tokens < 0 || n_docs < 0 || !tok_offsets || !counts) return TD_E_INVALID;
+    if (const char* m = pack_args_error(spec, n_docs, rows_capacity, host_out))
+        return fail_unlocked(t, TD_E_INVALID, std::string("td_pack_rows: ") + m);
+    int rc;
+    if ((rc = rows_check_ids(t, spec))) return rc;
+    return locked(t, [&] {
+        int rc2;
+        if ((rc2 = check_offsets(t, "tok_offsets", tok_offsets, n_docs, ids))) return rc2;
+        const int64_t total = tok_offsets[n_docs];
+        if (total > n_tokens) { t->err = "tok_offsets[n_docs] exceeds n_tokens"; return (int)TD_E_INVALID; }
+        if ((rc2 = ensure(t, t->dec_tokens, (size_t)std::max<int64_t>(total, 1) * 4))) return rc2;
+        if ((rc2 = ensure(t, t->d_offsets, (size_t)(n_docs + 1) * 8))) return rc2;
+        if ((rc2 = own_streams(t))) return rc2;
+        hipStream_t s = t->s_own;
+        if ((rc2 = order_before(t, s))) return rc2;
+        if (total > 0) HIP_TRY(t, hipMemcpyAsync(t->dec_tokens.p, ids, (size_t)total * 4, hipMemcpyHostToDevice, s));
+        HIP_TRY(t, hipMemcpyAsync(t->d_offsets.p, tok_offsets, (size_t)(n_docs + 1) * 8, hipMemcpyHostToDevice, s));
+        return pack_to_host(t, t->dec_tokens.p, total, t->d_offsets.p, n_docs, spec, *host_out, rows_capacity, counts, s);
+    });
+}
+
+int td_pack_rows_device(td_tokenizer* t, const void* d_ids, int64_t n_tokens, const void* d_tok_offsets, int64_t n_docs,
+                        const td_rows_spec* spec, const td_pack_outputs* dev_out, int64_t rows_capacity, int64_t* counts,
+                        void* hip_stream) {
+    if (!t || !spec || !dev_out || n_tokens < 0 || n_docs < 0 || !d_tok_offsets || (n_tokens > 0 && !d_ids) || !counts)
+        return TD_E_INVALID;
+    if (const char* m = pack_args_error(spec, n_docs, rows_capacity, dev_out))
+        return fail_unlocked(t, TD_E_INVALID, std::string("td_pack_rows_device: ") + m);
+    int rc;
+    if ((rc = rows_check_ids(t, spec))) return rc;
+    return locked(t, [&] {
+        hipStream_t s = (hipStream_t)hip_stream;
+        PackArgs a;
+        PackPlan plan;
+        int rc2;
+        if ((rc2 = pack_prepare(t, d_ids, n_tokens, d_tok_offsets, n_docs, spec, s, a, plan, counts))) return rc2;
+        if (plan.rows > rows_capacity) return rows_capacity_fail(t, plan.rows, counts);
+        return pack_emit(t, a, plan, *dev_out, s);
+    });
+}
+
+int td_encode_batch_pack_rows(td_tokenizer* t, const uint8_t* text, const int64_t* doc_offsets, int64_t n_docs, int mode,
+                              const td_rows_spec* spec, const td_pack_outputs* host_out, int64_t rows_capacity, int64_t* counts) {
+    if (!t || !spec || !host_out || !doc_offsets || n_docs < 0 || !counts || (mode != TD_MODE_ENCODE && mode != TD_MODE_ORDINARY))
+        return TD_E_INVALID;
+    if (const char* m = pack_args_error(spec, n_docs, rows_capacity, host_out))
+        return fail_unlocked(t, TD_E_INVALID, std::string("td_encode_batch_pack_rows: ") + m);
+    int rc;
+    if ((rc = rows_check_ids(t, spec))) return rc;
+    return locked(t, [&] {
+        int rc2;
+        if ((rc2 = check_offsets(t, "doc_offsets", doc_offsets, n_docs, text))) return rc2;
+        const int64_t n = doc_offsets[n_docs];
+        const int64_t dev_cap = std::max<int64_t>(n, 1);  // (at most one id per byte)
+        if ((rc2 = ensure(t, t->h2d_text, (size_t)n + 64))) return rc2;
+        if ((rc2 = ensure(t, t->h2d_offs, (size_t)(n_docs + 1) * 8))) return rc2;
+        if ((rc2 = ensure(t, t->d_offsets, (size_t)(n_docs + 1) * 8))) return rc2;
+        if ((rc2 = ensure(t, t->d_tokens, (size_t)dev_cap * 4))) return rc2;
+        if ((rc2 = own_streams(t))) return rc2;
+        hipStream_t s = t->s_own;
+        if ((rc2 = order_before(t, s))) return rc2;
+        if (n > 0) {
+            HIP_TRY(t, hipMemcpyAsync(t->h2d_text.p, text, (size_t)n, hipMemcpyHostToDevice, s));
+            HIP_TRY(t, hipMemcpyAsync(t->h2d_offs.p, doc_offsets, (size_t)(n_docs + 1) * 8, hipMemcpyHostToDevice, s));
+            if ((rc2 = encode_device_locked(t, t->h2d_text.p, n, t->h2d_offs.p, n_docs, mode, t->d_tokens.p, dev_cap, t->d_offsets.p, s)))
+                return rc2;
+        } else {  // (nothing but empty documents: no encode)
+            HIP_TRY(t, hipMemsetAsync(t->d_offsets.p, 0, (size_t)(n_docs + 1) * 8, s));
+        }
+        if ((rc2 = device_status_locked(t, s, nullptr))) return rc2;  // (the encode's errors as such, before the packing reads its ids)
+        return pack_to_host(t, t->d_tokens.p, dev_cap, t->d_offsets.p, n_docs, spec, *host_out, rows_capacity, counts, s);
     });
 }
 

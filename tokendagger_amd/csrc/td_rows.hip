@@ -100,7 +100,7 @@ __device__ __forceinline__ int32_t rows_load1(const RowsArgs& a, int64_t src) {
 }
 
 // slots [j0, j0 + 4) below `end`; int4 when aligned (j0 is a multiple of 4)
-__device__ __forceinline__ void rows_store4(int32_t* p, int64_t j0, int64_t end, const int32_t v[4]) {
+__device__ __forceinline__ void rows_put4(int32_t* p, int64_t j0, int64_t end, const int32_t v[4]) {
     if (j0 + 4 <= end && (((uintptr_t)p) & 15) == 0) {
         *reinterpret_cast<int4*>(p + j0) = make_int4(v[0], v[1], v[2], v[3]);
     } else {
@@ -250,8 +250,8 @@ __global__ __launch_bounds__(ROWS_THREADS) void td_rows_concat(const RowsArgs a)
                 }
                 ps[q] = (int32_t)(j - (base > rs ? base : rs));
             }
-            rows_store4(a.out, j0, s1, v);
-            if (a.pos) rows_store4(a.pos, j0, s1, ps);
+            rows_put4(a.out, j0, s1, v);
+            if (a.pos) rows_put4(a.pos, j0, s1, ps);
         }
     }
     const long long tot = block_sum(segs, s_red);
@@ -315,8 +315,8 @@ __global__ __launch_bounds__(ROWS_THREADS) void td_rows_pad(const RowsArgs a) {
                     trunc += L > room;
                 }
             }
-            rows_store4(a.out, j0, s1, v);
-            if (a.pos) rows_store4(a.pos, j0, s1, ps);
+            rows_put4(a.out, j0, s1, v);
+            if (a.pos) rows_put4(a.pos, j0, s1, ps);
         }
     }
     const long long r = block_sum(real, s_red), s = block_sum(segs, s_red), t = block_sum(trunc, s_red);

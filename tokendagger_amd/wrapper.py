@@ -34,6 +34,17 @@ class Rows(NamedTuple):
     counts: np.ndarray              # int64 [4]: rows, real slots, segments, truncated documents
 
 
+class PackedRows(NamedTuple):
+    """Whole documents packed into rows by best-fit decreasing (Tokenizer.ids_to_packed_rows / encode_batch_to_packed_rows; the
+    contract: include/tokendagger_hip.h, TD_ROWS_BESTFIT)."""
+    ids: np.ndarray                 # int32 [rows, seq_len]
+    positions: np.ndarray | None    # int32 [rows, seq_len]: the index inside the segment; pad slots 0
+    cu_seqlens: np.ndarray | None   # int32 [segments + 1]: segment boundaries over the flattened rows, pad tails included
+    lengths: np.ndarray             # int32 [rows]: real slots of every row
+    docs: np.ndarray | None         # int64 [segments]: the document of every segment, -1 for a pad tail
+    counts: np.ndarray              # int64 [4]: rows, real slots, segments, documents cut
+
+
 class TokenDaggerError(Exception):
     """Base exception for TokenDagger errors (reference: wrapper.py:23-25)."""
 
@@ -322,6 +333,39 @@ class Tokenizer:
         except Exception as ex:
             raise TokenDaggerError(f"Making rows failed: {ex}")
         return self._rows(r, lay, seq_len, no_pad)
+
+    # Whole documents -> rows by best-fit decreasing: every document stays whole inside one row when it fits ([BOS] ids [EOS]);
+    # a longer one is cut at multiples of seq_len (or truncated with its EOS kept, truncate=True) and its last chunk packed like
+    # the others.  bos / eos / pad as for ids_to_rows.
+    def _packed(self, r, no_pad: bool) -> PackedRows:
+        ids, pos, cu, lens, docs, counts = r
+        if no_pad and int(counts[1]) < ids.size:
+            raise ValueError("the rows need padding: pass pad=, or eos= to pad with it")
+        return PackedRows(ids, pos, cu, lens, docs, counts)
+
+    def ids_to_packed_rows(self, ids: np.ndarray, tok_offsets: np.ndarray, seq_len: int, *, bos=None, eos=None, pad=None,
+                           truncate: bool = False, positions: bool = False, cu_seqlens: bool = True, docs: bool = False) -> PackedRows:
+        """Best-fit-decreasing rows from ids already encoded (int32 ids + int64 per-document token offsets)."""
+        _, b, e, p, no_pad = self._rows_args(seq_len, "concat", bos, eos, pad)
+        try:
+            r = self._core_bpe.ids_to_packed_rows(np.asarray(ids, dtype=np.int32), np.asarray(tok_offsets, dtype=np.int64), seq_len, b, e, p,
+                                                  truncate, positions, cu_seqlens, True, docs)
+        except Exception as ex:
+            raise TokenDaggerError(f"Packing rows failed: {ex}")
+        return self._packed(r, no_pad)
+
+    def encode_batch_to_packed_rows(self, text: np.ndarray | bytes, offsets: np.ndarray, seq_len: int, *, bos=None, eos=None, pad=None,
+                                    truncate: bool = False, positions: bool = False, cu_seqlens: bool = True, docs: bool = False,
+                                    ordinary: bool = False) -> PackedRows:
+        """encode_batch_to_numpy straight into best-fit-decreasing rows (one call; the ids never leave the device)."""
+        _, b, e, p, no_pad = self._rows_args(seq_len, "concat", bos, eos, pad)
+        buf = np.frombuffer(text, dtype=np.uint8) if isinstance(text, (bytes, bytearray)) else text
+        try:
+            r = self._core_bpe.encode_batch_numpy_packed_rows(buf, np.asarray(offsets, dtype=np.int64), seq_len, b, e, p, truncate, positions,
+                                                              cu_seqlens, True, docs, MODE_ORDINARY if ordinary else MODE_ENCODE)
+        except Exception as ex:
+            raise TokenDaggerError(f"Encoding failed: {ex}")
+        return self._packed(r, no_pad)
 
     # ------------------------------------------------------------------ decoding ---------------
     def decode_bytes(self, tokens: Sequence[int]) -> bytes:
