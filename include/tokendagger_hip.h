@@ -336,6 +336,60 @@ int td_pack_rows_device(td_tokenizer* t, const void* d_ids, int64_t n_tokens, co
 int td_encode_batch_pack_rows(td_tokenizer* t, const uint8_t* text, const int64_t* doc_offsets, int64_t n_docs, int mode,
                               const td_rows_spec* spec, const td_pack_outputs* host_out, int64_t rows_capacity, int64_t* counts);
 
+/* ---- overlapping window rows for documents longer than seq_len (td_windows.hip) -------------------------------------------
+ * One document per row, and every id kept: a document that does not fit continues in further rows of its own, and consecutive
+ * rows of a document repeat `overlap` ids (Hugging Face: stride + return_overflowing_tokens + overflow_to_sample_mapping).
+ * td_rows_spec with layout = TD_ROWS_WINDOWS and flags = 0 (TD_ROWS_DROP_LAST and TD_ROWS_TRUNCATE are TD_E_INVALID here);
+ * bos / eos / pad are checked as for the other layouts; `overlap` is an argument of its own.  The td_make_rows* and td_pack_*
+ * entry points reject this layout.
+ *   b = (bos_id >= 0), e = (eos_id >= 0), body room C = S - b - e, step = C - overlap.  C < 1, overlap < 0 or overlap >= C:
+ *   TD_E_INVALID.
+ *   Document d has w_d = max(1, ceil((L_d - overlap) / step)) windows: L_d <= C gives one, and an empty document has a row too.
+ *   Window k holds the document's ids [k * step, min(L_d, k * step + C)), so every window after the first repeats exactly
+ *   `overlap` ids and brings at least one new id, and the union of a document's windows is the document.
+ *   Window k of document d is row first_row[d] + k, first_row the exclusive prefix sum of w; rows = first_row[n_docs].
+ *   A row is [BOS] body [EOS] then pad_id; every window has its own BOS and EOS.
+ *   Outputs (td_window_outputs; every field but ids may be NULL):
+ *     ids          int32 [rows * S]
+ *     positions    int32 [rows * S]  0 .. len - 1 inside the row, pad slots 0
+ *     row_lengths  int32 [rows]      the real slots of the row
+ *     row_docs     int64 [rows]      the row's document
+ *     row_starts   int64 [rows]      k * step: the index of the row's first body id inside its document.  With the starts of
+ *                                    td_token_starts* the row's text begins at starts[tok_offsets[row_docs[r]] + row_starts[r]].
+ *   counts[4] (int64) = {rows, R (real slots), documents with more than one window, the largest w_d}.
+ *   With overlap = 0 and no L_d > C, ids, positions and row_lengths are TD_ROWS_PAD's byte for byte.
+ *   n_docs < 2^31, seq_len 1 .. 2^31 - 1; rows * S may exceed 2^31. */
+#define TD_ROWS_WINDOWS 3
+typedef struct td_window_outputs {
+    int32_t* ids;
+    int32_t* positions;
+    int32_t* row_lengths;
+    int64_t* row_docs;
+    int64_t* row_starts;
+} td_window_outputs;
+
+/* The counts, on the host, from tok_offsets[n_docs + 1] alone (no handle, no device); first_row[n_docs + 1] may be NULL.
+ * tok_offsets must start at 0 and not decrease. */
+int td_window_plan(const int64_t* tok_offsets, int64_t n_docs, const td_rows_spec* spec, int64_t overlap, int64_t* counts,
+                   int64_t* first_row);
+/* Host buffers, synchronously.  tok_offsets is checked like every host entry point's offsets.  The rows are known on the host:
+ * a capacity below them fails before any launch with TD_E_CAPACITY and counts[0] = the rows needed. */
+int td_window_rows(td_tokenizer* t, const int32_t* ids, int64_t n_tokens, const int64_t* tok_offsets, int64_t n_docs,
+                   const td_rows_spec* spec, int64_t overlap, const td_window_outputs* host_out, int64_t rows_capacity, int64_t* counts);
+/* DEVICE buffers, asynchronously on hip_stream: no synchronisation and no read-back.  d_counts (4 int64) is device memory.  More
+ * rows than rows_capacity raise TD_E_CAPACITY through td_device_status with err_pos = the rows needed and counts[0] = the same,
+ * and nothing is written to any output.  tok_offsets that decrease, are negative or end above n_tokens raise TD_E_INVALID
+ * (err_pos: a document with such offsets) and nothing is written either; whatever they hold, no id outside [0, n_tokens) is
+ * read and nothing is written outside the capacities given. */
+int td_window_rows_device(td_tokenizer* t, const void* d_ids, int64_t n_tokens, const void* d_tok_offsets, int64_t n_docs,
+                          const td_rows_spec* spec, int64_t overlap, const td_window_outputs* dev_out, int64_t rows_capacity,
+                          void* d_counts, void* hip_stream);
+/* td_encode_batch (TD_MODE_ENCODE / TD_MODE_ORDINARY, no allowed special tokens) and td_window_rows in one call: the ids stay on
+ * the device.  Synchronous. */
+int td_encode_batch_window_rows(td_tokenizer* t, const uint8_t* text, const int64_t* doc_offsets, int64_t n_docs, int mode,
+                                const td_rows_spec* spec, int64_t overlap, const td_window_outputs* host_out, int64_t rows_capacity,
+                                int64_t* counts);
+
 /* Options. */
 #define TD_OPT_LONG_POOL_BYTES 1 /* scratch for pieces longer than 64 bytes (default max(64 MiB, 2 x input)) */
 #define TD_OPT_PROFILE 2         /* 1: bracket the kernels of every td_encode_device call with HIP events on the

@@ -21,7 +21,7 @@ TD_MODE_ORDINARY = 1
 TD_E_INVALID = 1
 TD_E_BAD_TOKEN = 8
 TD_UNIT_BYTES, TD_UNIT_CHARS = 0, 1
-TD_ROWS_CONCAT, TD_ROWS_PAD, TD_ROWS_BESTFIT = 0, 1, 2
+TD_ROWS_CONCAT, TD_ROWS_PAD, TD_ROWS_BESTFIT, TD_ROWS_WINDOWS = 0, 1, 2, 3
 TD_ROWS_DROP_LAST = 1
 TD_ROWS_TRUNCATE = 2
 TD_INFO_N_PAIRS, TD_INFO_MERGE_CLOSED, TD_INFO_MAX_ID, TD_INFO_TILE_BYTES = 1, 2, 3, 4
@@ -58,6 +58,7 @@ EXPORTS = [
     "td_comm_last_error", "td_encode_device_with_special", "td_token_starts", "td_token_starts_device", "td_encode_batch_with_starts",
     "td_encode_device_with_starts", "td_make_rows_device", "td_make_rows", "td_encode_batch_rows",
     "td_pack_plan", "td_pack_rows", "td_pack_rows_device", "td_encode_batch_pack_rows",
+    "td_window_plan", "td_window_rows", "td_window_rows_device", "td_encode_batch_window_rows",
 ]
 
 
@@ -128,6 +129,14 @@ def load_library():
     lib.td_pack_rows_device.argtypes = [vp, vp, i64, vp, i64, vp, vp, i64, vp, vp]
     lib.td_encode_batch_pack_rows.restype = i32
     lib.td_encode_batch_pack_rows.argtypes = [vp, vp, vp, i64, i32, vp, vp, i64, vp]
+    lib.td_window_plan.restype = i32
+    lib.td_window_plan.argtypes = [vp, i64, vp, i64, vp, vp]
+    lib.td_window_rows.restype = i32
+    lib.td_window_rows.argtypes = [vp, vp, i64, vp, i64, vp, i64, vp, i64, vp]
+    lib.td_window_rows_device.restype = i32
+    lib.td_window_rows_device.argtypes = [vp, vp, i64, vp, i64, vp, i64, vp, i64, vp, vp]
+    lib.td_encode_batch_window_rows.restype = i32
+    lib.td_encode_batch_window_rows.argtypes = [vp, vp, vp, i64, i32, vp, i64, vp, i64, vp]
     lib.td_comm_unique_id.restype = i32
     lib.td_comm_unique_id.argtypes = [vp]
     lib.td_comm_create.restype = i32
@@ -269,6 +278,33 @@ def pack_plan(tok_offsets, spec: RowsSpec, placement: bool = False):
     if rc != TD_OK:
         raise TokenDaggerHipError(rc, "td_pack_plan: invalid spec or tok_offsets")
     return (counts, row[:n_docs], slot[:n_docs]) if placement else counts
+
+
+class WindowOutputs(ctypes.Structure):
+    """td_window_outputs (include/tokendagger_hip.h): addresses, 0 / None for an output not wanted."""
+    _fields_ = [("ids", ctypes.c_void_p), ("positions", ctypes.c_void_p), ("row_lengths", ctypes.c_void_p), ("row_docs", ctypes.c_void_p),
+                ("row_starts", ctypes.c_void_p)]
+
+
+def windows_spec(seq_len: int, bos: int = -1, eos: int = -1, pad: int = 0) -> RowsSpec:
+    """A TD_ROWS_WINDOWS spec: one document per row, a longer document continues in overlapping rows of its own."""
+    return RowsSpec(TD_ROWS_WINDOWS, seq_len, bos, eos, pad, 0)
+
+
+def window_plan(tok_offsets, spec: RowsSpec, overlap: int = 0, first_row: bool = False):
+    """td_window_plan (host only, no device): counts int64[4] = rows, real slots, documents with more than one window, the
+    largest window count; with first_row=True also first_row int64[n_docs + 1], the first row of every document."""
+    lib = load_library()
+    o = np.ascontiguousarray(tok_offsets, dtype=np.int64)
+    n_docs = len(o) - 1
+    if n_docs < 0:
+        raise ValueError("tok_offsets must have n_docs + 1 entries")
+    counts = np.zeros(4, dtype=np.int64)
+    fr = np.empty(n_docs + 1, dtype=np.int64) if first_row else None
+    rc = lib.td_window_plan(o.ctypes.data, n_docs, ctypes.byref(spec), overlap, counts.ctypes.data, fr.ctypes.data if first_row else None)
+    if rc != TD_OK:
+        raise TokenDaggerHipError(rc, "td_window_plan: invalid spec, overlap or tok_offsets")
+    return (counts, fr) if first_row else counts
 
 
 def _as_u8(data) -> np.ndarray:
@@ -623,6 +659,67 @@ class HipTokenizer:
         self._check(self._lib.td_encode_batch_pack_rows(self._h, buf.ctypes.data if len(buf) else None, offs.ctypes.data, n_docs, mode,
                                                         ctypes.byref(spec), ctypes.byref(outs), rows, counts.ctypes.data))
         return self._pack_result(spec, b, counts)
+
+    # ---- window rows (TD_ROWS_WINDOWS) ------------------------------------------------------------------------
+    @staticmethod
+    def _window_buffers(spec: RowsSpec, rows: int, positions: bool, lengths: bool, docs: bool, starts: bool):
+        slots, nr = max(rows * spec.seq_len, 1), max(rows, 1)
+        b = [np.empty(slots, dtype=np.int32), np.empty(slots, dtype=np.int32) if positions else None,
+             np.empty(nr, dtype=np.int32) if lengths else None, np.empty(nr, dtype=np.int64) if docs else None,
+             np.empty(nr, dtype=np.int64) if starts else None]
+        return b, WindowOutputs(*[x.ctypes.data if x is not None else None for x in b])
+
+    @staticmethod
+    def _window_result(spec: RowsSpec, b, counts):
+        r, S = int(counts[0]), spec.seq_len
+        ids, pos, lens, docs, starts = b
+        return (ids[:r * S].reshape(r, S).copy(), pos[:r * S].reshape(r, S).copy() if pos is not None else None,
+                lens[:r].copy() if lens is not None else None, docs[:r].copy() if docs is not None else None,
+                starts[:r].copy() if starts is not None else None, counts)
+
+    def window_rows(self, ids, tok_offsets, spec: RowsSpec, overlap: int = 0, positions: bool = False, lengths: bool = True,
+                    docs: bool = True, starts: bool = True, rows_capacity: int | None = None):
+        """td_window_rows -> (ids int32[rows, S], positions int32[rows, S] | None, row_lengths int32[rows] | None,
+        row_docs int64[rows] | None, row_starts int64[rows] | None, counts int64[4]).  The default capacity is the exact rows
+        (td_window_plan)."""
+        t = np.ascontiguousarray(ids, dtype=np.int32)
+        o = np.ascontiguousarray(tok_offsets, dtype=np.int64)
+        n_docs = len(o) - 1
+        rows = rows_capacity if rows_capacity is not None else int(window_plan(o, spec, overlap)[0])
+        b, outs = self._window_buffers(spec, rows, positions, lengths, docs, starts)
+        counts = np.zeros(4, dtype=np.int64)
+        rc = self._lib.td_window_rows(self._h, t.ctypes.data if len(t) else None, len(t), o.ctypes.data, n_docs, ctypes.byref(spec), overlap,
+                                      ctypes.byref(outs), rows, counts.ctypes.data)
+        try:
+            self._check(rc)
+        except TokenDaggerHipError as ex:
+            ex.counts = counts  # (TD_E_CAPACITY: counts[0] = the rows needed)
+            raise
+        return self._window_result(spec, b, counts)
+
+    def window_rows_device(self, d_ids: int, n_tokens: int, d_tok_offsets: int, n_docs: int, spec: RowsSpec, overlap: int, d_out_ids: int,
+                           rows_capacity: int, d_positions: int = 0, d_row_lengths: int = 0, d_row_docs: int = 0, d_row_starts: int = 0,
+                           d_counts: int = 0, stream: int = 0):
+        """td_window_rows_device: raw device pointers, asynchronous on `stream`; check with device_status(stream)."""
+        outs = WindowOutputs(d_out_ids or None, d_positions or None, d_row_lengths or None, d_row_docs or None, d_row_starts or None)
+        self._check(self._lib.td_window_rows_device(self._h, d_ids or None, n_tokens, d_tok_offsets, n_docs, ctypes.byref(spec), overlap,
+                                                    ctypes.byref(outs), rows_capacity, d_counts or None, stream or None))
+
+    def encode_batch_window_rows(self, text, doc_offsets, spec: RowsSpec, overlap: int = 0, mode: int = TD_MODE_ENCODE,
+                                 positions: bool = False, lengths: bool = True, docs: bool = True, starts: bool = True,
+                                 rows_capacity: int | None = None):
+        """td_encode_batch_window_rows: encode + td_window_rows in one call; same result tuple as window_rows.  The default
+        capacity is the most rows the text can need (one id per byte: every document one row, and one more per `step` ids)."""
+        buf = _as_u8(text)
+        offs = np.ascontiguousarray(doc_offsets, dtype=np.int64)
+        n_docs = len(offs) - 1
+        step = spec.seq_len - (spec.bos_id >= 0) - (spec.eos_id >= 0) - overlap
+        rows = rows_capacity if rows_capacity is not None else n_docs + (int(offs[-1]) if len(offs) else 0) // max(step, 1)
+        b, outs = self._window_buffers(spec, rows, positions, lengths, docs, starts)
+        counts = np.zeros(4, dtype=np.int64)
+        self._check(self._lib.td_encode_batch_window_rows(self._h, buf.ctypes.data if len(buf) else None, offs.ctypes.data, n_docs, mode,
+                                                          ctypes.byref(spec), overlap, ctypes.byref(outs), rows, counts.ctypes.data))
+        return self._window_result(spec, b, counts)
 
     def device_status_pos(self, stream: int = 0) -> tuple[int, int]:
         """td_device_status without raising: (code, err_pos)."""

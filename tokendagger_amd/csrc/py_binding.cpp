@@ -673,6 +673,68 @@ public:
         });
     }
 
+    // ---- window rows (td_window_rows, td_encode_batch_window_rows) ----------------------------------------------------------------
+    // -> (ids int32[rows, S], positions int32[rows, S], row_lengths int32[rows], row_docs int64[rows], row_starts int64[rows],
+    //     counts int64[4]); an output not asked for is None
+    template <class F>
+    py::tuple window_call(const td_rows_spec& sp, int64_t rows_cap, bool positions, bool lengths, bool docs, bool starts, F&& call) {
+        const int64_t S = sp.seq_len > 0 ? sp.seq_len : 1, slots = std::max<int64_t>(rows_cap * S, 1), nr = std::max<int64_t>(rows_cap, 1);
+        py::array_t<int32_t> ids(slots), pos(positions ? slots : 0), ls(lengths ? nr : 0);
+        py::array_t<int64_t> ds(docs ? nr : 0), ss(starts ? nr : 0), counts(4);
+        int rc;
+        {
+            td_window_outputs o{ids.mutable_data(), positions ? pos.mutable_data() : nullptr, lengths ? ls.mutable_data() : nullptr,
+                                docs ? ds.mutable_data() : nullptr, starts ? ss.mutable_data() : nullptr};
+            int64_t* cp = counts.mutable_data();
+            py::gil_scoped_release rel;
+            rc = call(&o, cp);
+        }
+        if (rc != TD_OK) fail();
+        const int64_t rows = counts.data()[0];
+        ids.resize({(py::ssize_t)(rows * S)}, false);
+        py::object p = py::none(), l = py::none(), d = py::none(), st = py::none();
+        if (positions) {
+            pos.resize({(py::ssize_t)(rows * S)}, false);
+            p = pos.attr("reshape")(rows, S);
+        }
+        if (lengths) { ls.resize({(py::ssize_t)rows}, false); l = ls; }
+        if (docs) { ds.resize({(py::ssize_t)rows}, false); d = ds; }
+        if (starts) { ss.resize({(py::ssize_t)rows}, false); st = ss; }
+        return py::make_tuple(ids.attr("reshape")(rows, S), p, l, d, st, counts);
+    }
+    py::tuple ids_to_window_rows(py::array_t<int32_t, py::array::c_style | py::array::forcecast> ids,
+                                 py::array_t<int64_t, py::array::c_style | py::array::forcecast> tok_offsets, int64_t seq_len, int64_t overlap,
+                                 int64_t bos, int64_t eos, int64_t pad, bool positions, bool lengths, bool docs, bool starts) {
+        const int64_t n_docs = (int64_t)tok_offsets.size() - 1;
+        if (n_docs < 0) throw TiktokenError("tok_offsets must have n_docs+1 entries");
+        const td_rows_spec sp{TD_ROWS_WINDOWS, seq_len, bos, eos, pad, 0};
+        int64_t plan[4] = {0, 0, 0, 0};
+        const int64_t* op = tok_offsets.data();
+        if (td_window_plan(op, n_docs, &sp, overlap, plan, nullptr) != TD_OK) throw TiktokenError("invalid seq_len / overlap or tok_offsets");
+        const int64_t cap = plan[0], n = (int64_t)ids.size();
+        const int32_t* tp = ids.data();
+        return window_call(sp, cap, positions, lengths, docs, starts, [&](const td_window_outputs* o, int64_t* cp) {
+            return td_window_rows(h_, tp, n, op, n_docs, &sp, overlap, o, cap, cp);
+        });
+    }
+    py::tuple encode_batch_numpy_window_rows(py::array_t<uint8_t, py::array::c_style | py::array::forcecast> text,
+                                             py::array_t<int64_t, py::array::c_style | py::array::forcecast> offsets, int64_t seq_len,
+                                             int64_t overlap, int64_t bos, int64_t eos, int64_t pad, bool positions, bool lengths, bool docs,
+                                             bool starts, int mode) {
+        const int64_t n_docs = (int64_t)offsets.size() - 1;
+        if (n_docs < 0) throw TiktokenError("offsets must have n_docs+1 entries");
+        if (offsets.data()[n_docs] > (int64_t)text.size()) throw TiktokenError("offsets exceed the text buffer");
+        const td_rows_spec sp{TD_ROWS_WINDOWS, seq_len, bos, eos, pad, 0};
+        // (at most one id per byte: a row per document and one more per `step` ids; a spec the library rejects gets no room)
+        const int64_t step = seq_len - (bos >= 0) - (eos >= 0) - overlap;
+        const int64_t cap = step > 0 && overlap >= 0 ? n_docs + offsets.data()[n_docs] / step : 0;
+        const uint8_t* tp = text.data();
+        const int64_t* op = offsets.data();
+        return window_call(sp, cap, positions, lengths, docs, starts, [&](const td_window_outputs* o, int64_t* cp) {
+            return td_encode_batch_window_rows(h_, tp, op, n_docs, mode, &sp, overlap, o, cap, cp);
+        });
+    }
+
     // list[str] in, list[list[int]] out through ONE device batch (PackedTexts / IntCache above)
     py::list encode_batch(const py::sequence& texts, int mode) {
         PackedTexts in(texts);
@@ -840,6 +902,12 @@ PYBIND11_MODULE(_tokendagger_core, m) {
         .def("encode_batch_numpy_packed_rows", &CoreBPE::encode_batch_numpy_packed_rows, py::arg("text"), py::arg("offsets"), py::arg("seq_len"),
              py::arg("bos") = -1, py::arg("eos") = -1, py::arg("pad") = 0, py::arg("truncate") = false, py::arg("positions") = false,
              py::arg("cu_seqlens") = true, py::arg("lengths") = true, py::arg("docs") = false, py::arg("mode") = TD_MODE_ENCODE)
+        .def("ids_to_window_rows", &CoreBPE::ids_to_window_rows, py::arg("ids"), py::arg("tok_offsets"), py::arg("seq_len"), py::arg("overlap") = 0,
+             py::arg("bos") = -1, py::arg("eos") = -1, py::arg("pad") = 0, py::arg("positions") = false, py::arg("lengths") = true,
+             py::arg("docs") = true, py::arg("starts") = true)
+        .def("encode_batch_numpy_window_rows", &CoreBPE::encode_batch_numpy_window_rows, py::arg("text"), py::arg("offsets"), py::arg("seq_len"),
+             py::arg("overlap") = 0, py::arg("bos") = -1, py::arg("eos") = -1, py::arg("pad") = 0, py::arg("positions") = false,
+             py::arg("lengths") = true, py::arg("docs") = true, py::arg("starts") = true, py::arg("mode") = TD_MODE_ENCODE)
         .def("decode_batch", &CoreBPE::decode_batch, py::arg("docs"))
         .def("encode_batch_special", &CoreBPE::encode_batch_special, py::arg("texts"), py::arg("allowed_special"))
         .def("token_bytes", &CoreBPE::token_bytes, py::arg("id"))

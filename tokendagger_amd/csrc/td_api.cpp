@@ -20,6 +20,7 @@
 #include "td_offsets.h"
 #include "td_rows.h"
 #include "td_pack.h"
+#include "td_windows.h"
 #include "td_regex.h"
 #include "td_tables.h"
 #include "td_vocab.h"
@@ -291,6 +292,8 @@ struct td_tokenizer {
     DevBuf off_heads, off_chunks, off_docs, off_rank, off_starts;
     // training rows (td_rows.hip): the cu_seqlens scan's status words, the host entry points' outputs on the device
     DevBuf rows_scan, rows_out, rows_pos, rows_aux, rows_counts;
+    // window rows (td_windows.hip): the scan words and first_row, the host entry points' per-row outputs on the device
+    DevBuf win_scan, win_first, win_len, win_docs, win_starts;
     bool rows_last = false;  // the last call launched the rows kernels (the unit of a TD_E_CAPACITY position)
     // best-fit packing (td_pack.hip): the items, the sort's and the scan's scratch, the header + runs read back, the plan uploaded,
     // the segments; the host entry points' row lengths and segment documents on the device
@@ -994,6 +997,101 @@ int rows_capacity_fail(td_tokenizer* t, int64_t rows, int64_t* counts) {
     counts[1] = counts[2] = counts[3] = 0;
     t->err = "output capacity too small: " + std::to_string(rows) + " rows needed";
     return TD_E_CAPACITY;
+}
+
+// ---- window rows (td_windows.hip) ---------------------------------------------------------------------------------------------
+// The checks of a TD_ROWS_WINDOWS spec that need no handle.
+const char* window_spec_error(const td_rows_spec* sp, int64_t overlap, int64_t rows_capacity) {
+    if (!sp) return "null td_rows_spec";
+    if (sp->layout != TD_ROWS_WINDOWS) return "layout must be TD_ROWS_WINDOWS";
+    if (sp->seq_len < 1 || sp->seq_len > INT32_MAX) return "seq_len must be in 1 .. 2^31 - 1";
+    if (sp->flags != 0) return "flags must be 0";
+    if (sp->pad_id < INT32_MIN || sp->pad_id > INT32_MAX) return "pad_id must be an int32";
+    const int64_t C = sp->seq_len - (sp->bos_id >= 0) - (sp->eos_id >= 0);
+    if (C < 1) return "seq_len must leave room for one id beside BOS and EOS";
+    if (overlap < 0 || overlap >= C) return "overlap must be in 0 .. seq_len - BOS - EOS - 1";
+    if (rows_capacity < 0) return "rows_capacity must be >= 0";
+    if (rows_capacity > ((int64_t)1 << 62) / sp->seq_len) return "rows_capacity * seq_len is too large";
+    return nullptr;
+}
+
+const char* window_args_error(const td_rows_spec* sp, int64_t overlap, int64_t n_docs, int64_t rows_capacity, const td_window_outputs* o) {
+    if (!o) return "null td_window_outputs";
+    if (n_docs > INT32_MAX) return "n_docs must stay below 2^31";
+    if (rows_capacity > 0 && !o->ids) return "null ids output";
+    return window_spec_error(sp, overlap, rows_capacity);
+}
+
+// w_d = max(1, ceil((L - overlap) / step))
+int64_t window_count(int64_t L, int64_t C, int64_t overlap) { return L <= C ? 1 : (L - overlap + (C - overlap) - 1) / (C - overlap); }
+
+// Enqueues the scan and the slot kernel into the outputs of o (device pointers); d_counts is device memory.
+int window_launch_locked(td_tokenizer* t, const void* d_ids, int64_t n_tokens, const void* d_toff, int64_t n_docs, const td_rows_spec* sp,
+                         int64_t overlap, const td_window_outputs& o, int64_t cap, void* d_counts, hipStream_t s) {
+    int rc;
+    if ((rc = order_before(t, s))) return rc;
+    t->rows_last = true;
+    WindowArgs a;
+    memset(&a, 0, sizeof a);
+    a.ids = (const int32_t*)d_ids;
+    a.n_tokens = n_tokens;
+    a.tok_off = (const int64_t*)d_toff;
+    a.n_docs = n_docs;
+    a.b = sp->bos_id >= 0;
+    a.e = sp->eos_id >= 0;
+    a.S = sp->seq_len;
+    a.C = a.S - a.b - a.e;
+    a.overlap = overlap;
+    a.step = a.C - overlap;
+    a.s_magic = ~0ull / (unsigned long long)a.S;
+    a.step_magic = ~0ull / (unsigned long long)a.step;
+    a.bos = a.b ? (int32_t)sp->bos_id : 0;
+    a.eos = a.e ? (int32_t)sp->eos_id : 0;
+    a.pad = (int32_t)sp->pad_id;
+    a.out = o.ids;
+    a.rows_cap = cap;
+    a.pos = o.positions;
+    a.row_len = o.row_lengths;
+    a.row_doc = o.row_docs;
+    a.row_start = o.row_starts;
+    a.counts = (long long*)d_counts;
+    const size_t scan_bytes = (size_t)windows_scan_words(n_docs) * 8;
+    if ((rc = ensure(t, t->win_scan, scan_bytes))) return rc;
+    if ((rc = ensure(t, t->win_first, (size_t)(n_docs + 1) * 8))) return rc;
+    a.scan = (unsigned long long*)t->win_scan.p;
+    a.first_row = (int64_t*)t->win_first.p;
+    HIP_TRY(t, hipMemsetAsync(a.scan, 0, WIN_SCAN_HEAD * 8, s));
+    Ctl* ctl = (Ctl*)t->ctl.p;
+    a.err = &ctl->err;
+    a.err_pos = &ctl->err_pos;
+    HIP_TRY(t, launch_windows(a, s));
+    return order_after(t, s);
+}
+
+// Host entry points: `rows` rows (known on the host, checked against the capacity by the caller) from ids already on the device,
+// into the handle's buffers, then into host_out.
+int window_to_host(td_tokenizer* t, const void* d_ids, int64_t n_ids, const void* d_toff, int64_t n_docs, const td_rows_spec* sp,
+                   int64_t overlap, const td_window_outputs& ho, int64_t rows, int64_t* counts, hipStream_t s) {
+    int rc;
+    const size_t slots = (size_t)std::max<int64_t>(rows * sp->seq_len, 1), nr = (size_t)std::max<int64_t>(rows, 1);
+    td_window_outputs d{};
+    if ((rc = ensure(t, t->rows_out, slots * 4))) return rc;
+    d.ids = (int32_t*)t->rows_out.p;
+    if (ho.positions) { if ((rc = ensure(t, t->rows_pos, slots * 4))) return rc; d.positions = (int32_t*)t->rows_pos.p; }
+    if (ho.row_lengths) { if ((rc = ensure(t, t->win_len, nr * 4))) return rc; d.row_lengths = (int32_t*)t->win_len.p; }
+    if (ho.row_docs) { if ((rc = ensure(t, t->win_docs, nr * 8))) return rc; d.row_docs = (int64_t*)t->win_docs.p; }
+    if (ho.row_starts) { if ((rc = ensure(t, t->win_starts, nr * 8))) return rc; d.row_starts = (int64_t*)t->win_starts.p; }
+    if ((rc = ensure(t, t->rows_counts, 4 * sizeof(int64_t)))) return rc;
+    if ((rc = window_launch_locked(t, d_ids, n_ids, d_toff, n_docs, sp, overlap, d, rows, t->rows_counts.p, s))) return rc;
+    if ((rc = device_status_locked(t, s, nullptr))) return rc;
+    if ((rc = copy_wait(t, counts, t->rows_counts.p, 4 * sizeof(int64_t), hipMemcpyDeviceToHost, s))) return rc;
+    const size_t n_slots = (size_t)(rows * sp->seq_len);
+    if ((rc = copy_wait(t, ho.ids, d.ids, n_slots * 4, hipMemcpyDeviceToHost, s))) return rc;
+    if (ho.positions && (rc = copy_wait(t, ho.positions, d.positions, n_slots * 4, hipMemcpyDeviceToHost, s))) return rc;
+    if (ho.row_lengths && (rc = copy_wait(t, ho.row_lengths, d.row_lengths, (size_t)rows * 4, hipMemcpyDeviceToHost, s))) return rc;
+    if (ho.row_docs && (rc = copy_wait(t, ho.row_docs, d.row_docs, (size_t)rows * 8, hipMemcpyDeviceToHost, s))) return rc;
+    if (ho.row_starts && (rc = copy_wait(t, ho.row_starts, d.row_starts, (size_t)rows * 8, hipMemcpyDeviceToHost, s))) return rc;
+    return TD_OK;
 }
 
 // ---- best-fit packing (td_pack.hip) ------------------------------------------------------------------------------------------
@@ -2821,6 +2919,111 @@ int td_encode_batch_pack_rows(td_tokenizer* t, const uint8_t* text, const int64_
         }
         if ((rc2 = device_status_locked(t, s, nullptr))) return rc2;  // (the encode's errors as such, before the packing reads its ids)
         return pack_to_host(t, t->d_tokens.p, dev_cap, t->d_offsets.p, n_docs, spec, *host_out, rows_capacity, counts, s);
+    });
+}
+
+int td_window_plan(const int64_t* tok_offsets, int64_t n_docs, const td_rows_spec* spec, int64_t overlap, int64_t* counts,
+                   int64_t* first_row) {
+    if (!tok_offsets || n_docs < 0 || n_docs > INT32_MAX || !counts || window_spec_error(spec, overlap, 0)) return TD_E_INVALID;
+    if (tok_offsets[0] != 0) return TD_E_INVALID;
+    const int64_t k = (spec->bos_id >= 0) + (spec->eos_id >= 0), C = spec->seq_len - k;
+    int64_t rows = 0, R = 0, multi = 0, mx = 0;
+    for (int64_t d = 0; d < n_docs; ++d) {
+        const int64_t L = tok_offsets[d + 1] - tok_offsets[d];
+        if (L < 0) return TD_E_INVALID;
+        const int64_t w = window_count(L, C, overlap);
+        if (first_row) first_row[d] = rows;
+        rows += w;
+        R += w * k + L + (w - 1) * overlap;
+        multi += w > 1;
+        mx = std::max(mx, w);
+    }
+    if (first_row) first_row[n_docs] = rows;
+    counts[0] = rows;
+    counts[1] = R;
+    counts[2] = multi;
+    counts[3] = mx;
+    return TD_OK;
+}
+
+int td_window_rows_device(td_tokenizer* t, const void* d_ids, int64_t n_tokens, const void* d_tok_offsets, int64_t n_docs,
+                          const td_rows_spec* spec, int64_t overlap, const td_window_outputs* dev_out, int64_t rows_capacity,
+                          void* d_counts, void* hip_stream) {
+    if (!t || !spec || !dev_out || n_tokens < 0 || n_docs < 0 || !d_tok_offsets || (n_tokens > 0 && !d_ids) || !d_counts)
+        return TD_E_INVALID;
+    if (const char* m = window_args_error(spec, overlap, n_docs, rows_capacity, dev_out))
+        return fail_unlocked(t, TD_E_INVALID, std::string("td_window_rows_device: ") + m);
+    int rc;
+    if ((rc = rows_check_ids(t, spec))) return rc;
+    return locked(t, [&] {
+        return window_launch_locked(t, d_ids, n_tokens, d_tok_offsets, n_docs, spec, overlap, *dev_out, rows_capacity, d_counts,
+                                    (hipStream_t)hip_stream);
+    });
+}
+
+int td_window_rows(td_tokenizer* t, const int32_t* ids, int64_t n_tokens, const int64_t* tok_offsets, int64_t n_docs,
+                   const td_rows_spec* spec, int64_t overlap, const td_window_outputs* host_out, int64_t rows_capacity, int64_t* counts) {
+    if (!t || !spec || !host_out || n_tokens < 0 || n_docs < 0 || !tok_offsets || !counts) return TD_E_INVALID;
+    if (const char* m = window_args_error(spec, overlap, n_docs, rows_capacity, host_out))
+        return fail_unlocked(t, TD_E_INVALID, std::string("td_window_rows: ") + m);
+    int rc;
+    if ((rc = rows_check_ids(t, spec))) return rc;
+    return locked(t, [&] {
+        int rc2;
+        if ((rc2 = check_offsets(t, "tok_offsets", tok_offsets, n_docs, ids))) return rc2;
+        const int64_t total = tok_offsets[n_docs];
+        if (total > n_tokens) { t->err = "tok_offsets[n_docs] exceeds n_tokens"; return (int)TD_E_INVALID; }
+        int64_t plan[4];
+        if (td_window_plan(tok_offsets, n_docs, spec, overlap, plan, nullptr) != TD_OK) { t->err = "invalid tok_offsets"; return (int)TD_E_INVALID; }
+        if (plan[0] > rows_capacity) return rows_capacity_fail(t, plan[0], counts);
+        if ((rc2 = ensure(t, t->dec_tokens, (size_t)std::max<int64_t>(total, 1) * 4))) return rc2;
+        if ((rc2 = ensure(t, t->d_offsets, (size_t)(n_docs + 1) * 8))) return rc2;
+        if ((rc2 = own_streams(t))) return rc2;
+        hipStream_t s = t->s_own;
+        if ((rc2 = order_before(t, s))) return rc2;
+        if (total > 0) HIP_TRY(t, hipMemcpyAsync(t->dec_tokens.p, ids, (size_t)total * 4, hipMemcpyHostToDevice, s));
+        HIP_TRY(t, hipMemcpyAsync(t->d_offsets.p, tok_offsets, (size_t)(n_docs + 1) * 8, hipMemcpyHostToDevice, s));
+        return window_to_host(t, t->dec_tokens.p, total, t->d_offsets.p, n_docs, spec, overlap, *host_out, plan[0], counts, s);
+    });
+}
+
+int td_encode_batch_window_rows(td_tokenizer* t, const uint8_t* text, const int64_t* doc_offsets, int64_t n_docs, int mode,
+                                const td_rows_spec* spec, int64_t overlap, const td_window_outputs* host_out, int64_t rows_capacity,
+                                int64_t* counts) {
+    if (!t || !spec || !host_out || !doc_offsets || n_docs < 0 || !counts || (mode != TD_MODE_ENCODE && mode != TD_MODE_ORDINARY))
+        return TD_E_INVALID;
+    if (const char* m = window_args_error(spec, overlap, n_docs, rows_capacity, host_out))
+        return fail_unlocked(t, TD_E_INVALID, std::string("td_encode_batch_window_rows: ") + m);
+    int rc;
+    if ((rc = rows_check_ids(t, spec))) return rc;
+    return locked(t, [&] {
+        int rc2;
+        if ((rc2 = check_offsets(t, "doc_offsets", doc_offsets, n_docs, text))) return rc2;
+        const int64_t n = doc_offsets[n_docs];
+        const int64_t dev_cap = std::max<int64_t>(n, 1);  // (at most one id per byte)
+        if ((rc2 = ensure(t, t->h2d_text, (size_t)n + 64))) return rc2;
+        if ((rc2 = ensure(t, t->h2d_offs, (size_t)(n_docs + 1) * 8))) return rc2;
+        if ((rc2 = ensure(t, t->d_offsets, (size_t)(n_docs + 1) * 8))) return rc2;
+        if ((rc2 = ensure(t, t->d_tokens, (size_t)dev_cap * 4))) return rc2;
+        if ((rc2 = own_streams(t))) return rc2;
+        hipStream_t s = t->s_own;
+        if ((rc2 = order_before(t, s))) return rc2;
+        if (n > 0) {
+            HIP_TRY(t, hipMemcpyAsync(t->h2d_text.p, text, (size_t)n, hipMemcpyHostToDevice, s));
+            HIP_TRY(t, hipMemcpyAsync(t->h2d_offs.p, doc_offsets, (size_t)(n_docs + 1) * 8, hipMemcpyHostToDevice, s));
+            if ((rc2 = encode_device_locked(t, t->h2d_text.p, n, t->h2d_offs.p, n_docs, mode, t->d_tokens.p, dev_cap, t->d_offsets.p, s)))
+                return rc2;
+        } else {  // (nothing but empty documents: no encode)
+            HIP_TRY(t, hipMemsetAsync(t->d_offsets.p, 0, (size_t)(n_docs + 1) * 8, s));
+        }
+        if ((rc2 = device_status_locked(t, s, nullptr))) return rc2;  // (the encode's errors as such, before the windows read its ids)
+        // the rows are known from the token offsets: they come back (8 bytes a document) and are planned on the host
+        std::vector<int64_t> toff((size_t)n_docs + 1);
+        if ((rc2 = copy_wait(t, toff.data(), t->d_offsets.p, (size_t)(n_docs + 1) * 8, hipMemcpyDeviceToHost, s))) return rc2;
+        int64_t plan[4];
+        if (td_window_plan(toff.data(), n_docs, spec, overlap, plan, nullptr) != TD_OK) { t->err = "invalid token offsets"; return (int)TD_E_INVALID; }
+        if (plan[0] > rows_capacity) return rows_capacity_fail(t, plan[0], counts);
+        return window_to_host(t, t->d_tokens.p, dev_cap, t->d_offsets.p, n_docs, spec, overlap, *host_out, plan[0], counts, s);
     });
 }
 

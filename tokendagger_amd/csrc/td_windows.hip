@@ -1,0 +1,325 @@
+// Overlapping window rows (td_window_rows*, td_encode_batch_window_rows): ids + per-document token offsets -> rows of S slots,
+// one document per row; a document longer than the body room C = S - b - e continues in further rows of its own, each starting
+// step = C - overlap ids after the one before.
+//
+// Document d has w_d = max(1, ceil((L_d - overlap) / step)) rows, and its first row is the exclusive prefix sum of w: unlike
+// CONCAT and PAD no closed form, unlike BESTFIT nothing sequential.  Three small launches make first_row[n_docs + 1]; no lane
+// waits for another workgroup in any of them, so there is nothing to bound:
+//
+//   td_win_count    w_d of 1024 documents a workgroup (the division by a host-computed multiplier), the offsets checks, the
+//                   chunk's rows into the scan words, the counts by one atomic a workgroup
+//   td_win_chunks   one workgroup: the chunks' rows -> their exclusive prefixes, first_row[n_docs] = rows (-1: bad offsets),
+//                   the capacity check, counts
+//   td_win_first    first_row[d] = the chunk's prefix + the scan inside the chunk
+//   td_win_slots    the slots.  td_rows_pad's shape: tiles of 4096 OUTPUT slots, four a lane stored as one int4, so a document of
+//                   a quarter of a million ids is written by as many lanes as its rows have slots.  The rows of a tile are
+//                   consecutive and their documents ascend: one 256-way search over first_row finds the document of the tile's
+//                   first row (inside [r - (rows - n_docs), r]: first_row[d] - d never decreases, so without a split document
+//                   the search is no step at all), the first rows of the tile's documents go to LDS, and a lane finds its row's
+//                   document there.  The tile in which a row starts writes the row's length, document and start.
+//
+// td_win_slots reads first_row[n_docs] itself (a kernel boundary lies behind td_win_chunks): above the capacity, or -1, it
+// leaves without a store.
+#include <hip/hip_runtime.h>
+
+#include "td_common.h"
+#include "td_windows.h"
+
+namespace td {
+
+namespace {
+
+__device__ __forceinline__ void win_raise(const WindowArgs& a, int code, int64_t pos) {
+    if (atomicCAS(a.err, 0, code) == 0) *a.err_pos = pos;
+}
+
+// x / d for 0 <= x < 2^63 by magic = floor((2^64 - 1) / d): the estimate is low by at most one
+__device__ __forceinline__ int64_t div_magic(int64_t x, int64_t d, unsigned long long magic) {
+    const unsigned long long D = (unsigned long long)d;
+    unsigned long long q = __umul64hi((unsigned long long)x, magic);
+    unsigned long long r = (unsigned long long)x - q * D;
+    for (int f = 0; f < 2 && r >= D; ++f) { ++q; r -= D; }
+    return (int64_t)q;
+}
+
+// L_d; 0 with `bad` set unless 0 <= tok_off[d] <= tok_off[d + 1] <= n_tokens
+__device__ __forceinline__ int64_t win_len(const WindowArgs& a, int64_t d, bool& bad) {
+    const int64_t lo = a.tok_off[d], hi = a.tok_off[d + 1];
+    if (lo < 0 || hi < lo || hi > a.n_tokens) {
+        bad = true;
+        return 0;
+    }
+    return hi - lo;
+}
+
+// w_d = max(1, ceil((L - overlap) / step)): L <= C is one window, more is at least two
+__device__ __forceinline__ int64_t win_count(const WindowArgs& a, int64_t L) {
+    return L <= a.C ? 1 : div_magic(L - a.overlap + a.step - 1, a.step, a.step_magic);
+}
+
+// the exclusive scan of `sum` over the workgroup's lanes, and its total
+__device__ __forceinline__ long long block_excl(long long sum, long long* s_wave, long long& total) {
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    long long incl = sum;
+    for (int dd = 1; dd < 64; dd <<= 1) {
+        const long long o = __shfl_up(incl, dd);
+        if (lane >= dd) incl += o;
+    }
+    __syncthreads();  // (the readers of an earlier call are done)
+    if (lane == 63) s_wave[wv] = incl;
+    __syncthreads();
+    long long before = 0;
+    total = 0;
+    for (int w = 0; w < WIN_THREADS / 64; ++w) {
+        if (w < wv) before += s_wave[w];
+        total += s_wave[w];
+    }
+    return before + incl - sum;
+}
+
+__global__ __launch_bounds__(WIN_THREADS) void td_win_count(const WindowArgs a) {
+    __shared__ long long s_red[4][WIN_THREADS / 64];
+    __shared__ int s_bad;
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    if (tid == 0) s_bad = 0;
+    long long rows = 0, real = 0, multi = 0, mx = 0;
+    bool bad = false;
+    int64_t bad_at = 0;
+    for (int q = 0; q < 4; ++q) {
+        const int64_t d = (int64_t)blockIdx.x * WIN_SCAN_DOCS + tid * 4 + q;
+        if (d >= a.n_docs) break;
+        bool bd = false;
+        const int64_t L = win_len(a, d, bd), w = win_count(a, L);
+        if (bd && !bad) bad_at = d;
+        bad |= bd;
+        rows += w;
+        real += w * (a.b + a.e) + L + (w - 1) * a.overlap;
+        multi += w > 1;
+        mx = w > mx ? w : mx;
+    }
+    if (a.n_docs == 0 && blockIdx.x == 0 && tid == 0) {
+        const int64_t o = a.tok_off[0];
+        bad = o < 0 || o > a.n_tokens;
+    }
+    for (int dd = 32; dd >= 1; dd >>= 1) {
+        rows += __shfl_xor(rows, dd);
+        real += __shfl_xor(real, dd);
+        multi += __shfl_xor(multi, dd);
+        const long long o = __shfl_xor(mx, dd);
+        mx = o > mx ? o : mx;
+    }
+    if (lane == 0) {
+        s_red[0][wv] = rows;
+        s_red[1][wv] = real;
+        s_red[2][wv] = multi;
+        s_red[3][wv] = mx;
+    }
+    __syncthreads();
+    if (bad) {
+        win_raise(a, TD_E_INVALID, bad_at);
+        s_bad = 1;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        rows = real = multi = mx = 0;
+        for (int w = 0; w < WIN_THREADS / 64; ++w) {
+            rows += s_red[0][w];
+            real += s_red[1][w];
+            multi += s_red[2][w];
+            mx = s_red[3][w] > mx ? s_red[3][w] : mx;
+        }
+        a.scan[WIN_SCAN_HEAD + blockIdx.x] = (unsigned long long)rows;
+        if (real) atomicAdd(&a.scan[0], (unsigned long long)real);
+        if (multi) atomicAdd(&a.scan[1], (unsigned long long)multi);
+        if (mx) atomicMax(&a.scan[2], (unsigned long long)mx);
+        if (s_bad) atomicAdd(&a.scan[3], 1ull);
+    }
+}
+
+__global__ __launch_bounds__(WIN_THREADS) void td_win_chunks(const WindowArgs a, int64_t nch) {
+    __shared__ long long s_wave[WIN_THREADS / 64];
+    const int tid = threadIdx.x;
+    unsigned long long* cs = a.scan + WIN_SCAN_HEAD;
+    long long carry = 0;
+    for (int64_t base = 0; base < nch; base += 4 * WIN_THREADS) {
+        long long v[4], sum = 0;
+        for (int q = 0; q < 4; ++q) {
+            const int64_t c = base + tid * 4 + q;
+            v[q] = c < nch ? (long long)cs[c] : 0;
+            sum += v[q];
+        }
+        long long total;
+        long long run = carry + block_excl(sum, s_wave, total);
+        for (int q = 0; q < 4; ++q) {
+            const int64_t c = base + tid * 4 + q;
+            if (c < nch) cs[c] = (unsigned long long)run;
+            run += v[q];
+        }
+        carry += total;
+    }
+    if (tid == 0) {
+        const bool bad = a.scan[3] != 0;
+        const int64_t rows = a.n_docs > 0 ? carry : 0;
+        a.first_row[a.n_docs] = bad ? -1 : rows;
+        const bool fits = !bad && rows <= a.rows_cap;
+        if (!bad && !fits) win_raise(a, TD_E_CAPACITY, rows);
+        a.counts[0] = bad ? 0 : rows;
+        a.counts[1] = fits ? (long long)a.scan[0] : 0;
+        a.counts[2] = fits ? (long long)a.scan[1] : 0;
+        a.counts[3] = fits ? (long long)a.scan[2] : 0;
+    }
+}
+
+__global__ __launch_bounds__(WIN_THREADS) void td_win_first(const WindowArgs a) {
+    __shared__ long long s_wave[WIN_THREADS / 64];
+    const int tid = threadIdx.x;
+    long long v[4], sum = 0;
+    for (int q = 0; q < 4; ++q) {
+        const int64_t d = (int64_t)blockIdx.x * WIN_SCAN_DOCS + tid * 4 + q;
+        bool bd = false;
+        v[q] = d < a.n_docs ? win_count(a, win_len(a, d, bd)) : 0;
+        sum += v[q];
+    }
+    long long total;
+    long long run = (long long)a.scan[WIN_SCAN_HEAD + blockIdx.x] + block_excl(sum, s_wave, total);
+    for (int q = 0; q < 4; ++q) {
+        const int64_t d = (int64_t)blockIdx.x * WIN_SCAN_DOCS + tid * 4 + q;
+        if (d < a.n_docs) a.first_row[d] = run;
+        run += v[q];
+    }
+}
+
+// ids[src] with 0 <= src < n_tokens checked (td_win_slots runs on checked offsets only: this is a second fence, not a path)
+__device__ __forceinline__ int32_t win_load1(const WindowArgs& a, int64_t src) {
+    if (src >= 0 && src < a.n_tokens) return a.ids[src];
+    win_raise(a, TD_E_INVALID, src);
+    return a.pad;
+}
+
+// slots [j0, j0 + 4) below `end`; int4 when aligned (j0 is a multiple of 4)
+__device__ __forceinline__ void win_put4(int32_t* p, int64_t j0, int64_t end, const int32_t v[4]) {
+    if (j0 + 4 <= end && (((uintptr_t)p) & 15) == 0) {
+        *reinterpret_cast<int4*>(p + j0) = make_int4(v[0], v[1], v[2], v[3]);
+    } else {
+        for (int q = 0; q < 4; ++q)
+            if (j0 + q < end) p[j0 + q] = v[q];
+    }
+}
+
+__global__ __launch_bounds__(WIN_THREADS) void td_win_slots(const WindowArgs a) {
+    __shared__ int32_t s_fr[WIN_LDS_DOCS];  // first rows of the tile's documents - r0, clamped to [-1, WIN_TILE + 2]
+    const int tid = threadIdx.x;
+    const int64_t rows = a.first_row[a.n_docs];
+    if (rows < 0 || rows > a.rows_cap) return;
+    const int64_t S = a.S, total = rows * S, extra = rows - a.n_docs;
+    const int64_t ntiles = (total + WIN_TILE - 1) / WIN_TILE;
+    for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+        const int64_t s0 = tile * WIN_TILE;
+        const int64_t s1 = s0 + WIN_TILE < total ? s0 + WIN_TILE : total;
+        const int64_t r0 = div_magic(s0, S, a.s_magic);
+        const int nr = (int)(div_magic(s1 - 1, S, a.s_magic) - r0) + 1;  // rows [r0, r0 + nr) have slots in the tile
+        __syncthreads();  // (the previous tile's readers of s_fr are done)
+        // d0: the last document with first_row[d] <= r0.  d <= first_row[d] <= d + extra bounds it; 256 probes a step
+        int64_t lo = r0 > extra ? r0 - extra : 0, hi = (r0 < a.n_docs - 1 ? r0 : a.n_docs - 1) + 1;
+        while (hi - lo > 1) {
+            const int64_t stp = (hi - lo + WIN_THREADS - 1) / WIN_THREADS;
+            const int64_t q = lo + (int64_t)tid * stp;
+            const int c = __syncthreads_count(tid > 0 && q < hi && a.first_row[q] <= r0);
+            hi = hi < lo + (int64_t)(c + 1) * stp ? hi : lo + (int64_t)(c + 1) * stp;
+            lo += (int64_t)c * stp;
+        }
+        const int64_t d0 = lo, fr0 = a.first_row[d0];
+        int nl = 0;  // documents with rows in the tile: s_fr[0, nl), and s_fr[nl] the first row of the next (>= nr)
+        for (int c0 = 0; c0 + WIN_THREADS <= WIN_LDS_DOCS; c0 += WIN_THREADS) {
+            const int64_t d = d0 + c0 + tid;
+            int32_t v = WIN_TILE + 2;
+            if (d <= a.n_docs) {
+                const int64_t r = a.first_row[d] - r0;
+                v = r < 0 ? -1 : r > WIN_TILE + 1 ? WIN_TILE + 2 : (int32_t)r;
+            }
+            s_fr[c0 + tid] = v;
+            const int c = __syncthreads_count(v < nr);
+            nl += c;
+            if (c < WIN_THREADS) break;
+        }
+        for (int it = 0; it < WIN_TILE / (4 * WIN_THREADS); ++it) {
+            const int64_t j0 = s0 + (int64_t)it * 4 * WIN_THREADS + 4 * tid;
+            if (j0 >= s1) break;
+            int64_t r = div_magic(j0, S, a.s_magic), o = j0 - r * S;
+            int i;
+            {  // the row's document: the last of the tile's with first row <= r
+                const int32_t x = (int32_t)(r - r0);
+                int l2 = 0, h2 = nl;
+                while (h2 - l2 > 1) {
+                    const int mid = (l2 + h2) >> 1;
+                    if (s_fr[mid] <= x) l2 = mid;
+                    else h2 = mid;
+                }
+                i = l2;
+            }
+            int64_t d = 0, tlo = 0, start = 0, body = 0, len = 0;
+            auto load_row = [&] {
+                d = d0 + i;
+                tlo = a.tok_off[d];
+                const int64_t L = a.tok_off[d + 1] - tlo;
+                start = (r - (i == 0 ? fr0 : r0 + s_fr[i])) * a.step;
+                body = L - start;
+                body = body < 0 ? 0 : body > a.C ? a.C : body;
+                len = a.b + body + a.e;
+            };
+            load_row();
+            int32_t v[4], ps[4];
+            bool fast = false;
+            const int64_t src = tlo + start + o - a.b;
+            if (o + 4 <= S && j0 + 4 <= s1 && o >= a.b && o + 4 <= a.b + body && src >= 0 && src + 4 <= a.n_tokens) {
+                const int32_t* p = a.ids + src;  // (four dwords: the sources are misaligned three times out of four)
+                v[0] = p[0]; v[1] = p[1]; v[2] = p[2]; v[3] = p[3];
+                fast = true;
+            }
+            for (int q = 0; q < 4; ++q) {
+                if (j0 + q >= s1) break;
+                if (q > 0 && ++o == S) {
+                    o = 0;
+                    ++r;
+                    if (i + 1 < nl && s_fr[i + 1] <= (int32_t)(r - r0)) ++i;
+                    load_row();
+                }
+                if (!fast) {
+                    if (o < a.b) v[q] = a.bos;
+                    else if (o < a.b + body) v[q] = win_load1(a, tlo + start + o - a.b);
+                    else if (a.e && o == a.b + body) v[q] = a.eos;
+                    else v[q] = a.pad;
+                }
+                ps[q] = o < len ? (int32_t)o : 0;
+                if (o == 0) {
+                    if (a.row_len) a.row_len[r] = (int32_t)len;
+                    if (a.row_doc) a.row_doc[r] = d;
+                    if (a.row_start) a.row_start[r] = start;
+                }
+            }
+            win_put4(a.out, j0, s1, v);
+            if (a.pos) win_put4(a.pos, j0, s1, ps);
+        }
+    }
+}
+
+}  // namespace
+
+int64_t windows_scan_words(int64_t n_docs) { return WIN_SCAN_HEAD + (n_docs > 0 ? (n_docs + WIN_SCAN_DOCS - 1) / WIN_SCAN_DOCS : 1); }
+
+hipError_t launch_windows(const WindowArgs& a, hipStream_t stream) {
+    const int64_t nch = windows_scan_words(a.n_docs) - WIN_SCAN_HEAD;
+    hipLaunchKernelGGL(td_win_count, dim3((unsigned)nch), dim3(WIN_THREADS), 0, stream, a);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(td_win_chunks, dim3(1), dim3(WIN_THREADS), 0, stream, a, nch);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    hipLaunchKernelGGL(td_win_first, dim3((unsigned)nch), dim3(WIN_THREADS), 0, stream, a);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    const int64_t tiles = (a.rows_cap * a.S + WIN_TILE - 1) / WIN_TILE;  // (the host keeps rows_cap * S far from overflow)
+    const int grid = (int)(tiles < 1 ? 1 : tiles < WIN_MAX_GRID ? tiles : WIN_MAX_GRID);
+    hipLaunchKernelGGL(td_win_slots, dim3(grid), dim3(WIN_THREADS), 0, stream, a);
+    return hipGetLastError();
+}
+
+}  // namespace td

@@ -45,6 +45,17 @@ class PackedRows(NamedTuple):
     counts: np.ndarray              # int64 [4]: rows, real slots, segments, documents cut
 
 
+class WindowRows(NamedTuple):
+    """One document per row, a longer document continued in overlapping rows of its own (Tokenizer.ids_to_window_rows /
+    encode_batch_to_window_rows; the contract: include/tokendagger_hip.h, TD_ROWS_WINDOWS)."""
+    ids: np.ndarray                 # int32 [rows, seq_len]
+    positions: np.ndarray | None    # int32 [rows, seq_len]: the index inside the row; pad slots 0
+    lengths: np.ndarray             # int32 [rows]: real slots of every row
+    docs: np.ndarray                # int64 [rows]: the row's document
+    starts: np.ndarray              # int64 [rows]: the index of the row's first body id inside its document
+    counts: np.ndarray              # int64 [4]: rows, real slots, documents with more than one window, the most windows of one
+
+
 class TokenDaggerError(Exception):
     """Base exception for TokenDagger errors (reference: wrapper.py:23-25)."""
 
@@ -366,6 +377,38 @@ class Tokenizer:
         except Exception as ex:
             raise TokenDaggerError(f"Encoding failed: {ex}")
         return self._packed(r, no_pad)
+
+    # One document per row with every id kept: a document longer than the row's room continues in further rows of its own, each
+    # repeating the last `overlap` ids of the row before (Hugging Face: stride + return_overflowing_tokens).  bos / eos / pad as
+    # for ids_to_rows; every row gets its own BOS and EOS.
+    def _windows(self, r, no_pad: bool) -> WindowRows:
+        ids, pos, lens, docs, starts, counts = r
+        if no_pad and int(counts[1]) < ids.size:
+            raise ValueError("the rows need padding: pass pad=, or eos= to pad with it")
+        return WindowRows(ids, pos, lens, docs, starts, counts)
+
+    def ids_to_window_rows(self, ids: np.ndarray, tok_offsets: np.ndarray, seq_len: int, *, overlap: int = 0, bos=None, eos=None, pad=None,
+                           positions: bool = False) -> WindowRows:
+        """Window rows from ids already encoded (int32 ids + int64 per-document token offsets)."""
+        _, b, e, p, no_pad = self._rows_args(seq_len, "pad", bos, eos, pad)
+        try:
+            r = self._core_bpe.ids_to_window_rows(np.asarray(ids, dtype=np.int32), np.asarray(tok_offsets, dtype=np.int64), seq_len,
+                                                  int(overlap), b, e, p, positions, True, True, True)
+        except Exception as ex:
+            raise TokenDaggerError(f"Making window rows failed: {ex}")
+        return self._windows(r, no_pad)
+
+    def encode_batch_to_window_rows(self, text: np.ndarray | bytes, offsets: np.ndarray, seq_len: int, *, overlap: int = 0, bos=None,
+                                    eos=None, pad=None, positions: bool = False, ordinary: bool = False) -> WindowRows:
+        """encode_batch_to_numpy straight into window rows (one call; the ids never leave the device)."""
+        _, b, e, p, no_pad = self._rows_args(seq_len, "pad", bos, eos, pad)
+        buf = np.frombuffer(text, dtype=np.uint8) if isinstance(text, (bytes, bytearray)) else text
+        try:
+            r = self._core_bpe.encode_batch_numpy_window_rows(buf, np.asarray(offsets, dtype=np.int64), seq_len, int(overlap), b, e, p,
+                                                              positions, True, True, True, MODE_ORDINARY if ordinary else MODE_ENCODE)
+        except Exception as ex:
+            raise TokenDaggerError(f"Encoding failed: {ex}")
+        return self._windows(r, no_pad)
 
     # ------------------------------------------------------------------ decoding ---------------
     def decode_bytes(self, tokens: Sequence[int]) -> bytes:

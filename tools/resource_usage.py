@@ -1,4 +1,5 @@
-"""hipcc -Rpass-analysis=kernel-resource-usage of the device sources -> profiles/r<round>_resource_usage.txt (usage: tools/resource_usage.py <round>)
+"""hipcc -Rpass-analysis=kernel-resource-usage of the device sources -> profiles/r<round>_resource_usage.txt (usage: tools/resource_usage.py <round>; a name
+instead of a number, e.g. `windows`, writes profiles/<name>_resource_usage.txt)
 (VGPRs, spilled VGPRs, scratch bytes per lane, waves/SIMD, LDS bytes per workgroup of every kernel)."""
 import re
 import subprocess
@@ -11,7 +12,7 @@ import bench
 
 out = [f"# hipcc --offload-arch=gfx950 -O3 -Rpass-analysis=kernel-resource-usage on these sources (kernel source sha {bench.kernel_source_sha()})",
        "# kernel | VGPRs | spilled VGPRs | scratch B/lane | waves/SIMD | LDS B/workgroup"]
-for src in ("td_kernels.hip", "td_generic.hip", "td_special.hip"):
+for src in ("td_kernels.hip", "td_generic.hip", "td_special.hip", "td_windows.hip"):
     p = subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", f"-I{ROOT / 'include'}", "-c",
                         str(ROOT / "tokendagger_amd" / "csrc" / src), "-o", "/dev/null", "-Rpass-analysis=kernel-resource-usage"],
                        capture_output=True, text=True)
@@ -25,7 +26,8 @@ for src in ("td_kernels.hip", "td_generic.hip", "td_special.hip"):
             cur = {"name": subprocess.run(["c++filt", v], capture_output=True, text=True).stdout.strip()}
         cur[k] = v
         if k.startswith("LDS"):
-            name = cur["name"].replace("td::", "").replace("(td::EncodeArgs)", "")
+            name = cur["name"].replace("td::", "").replace("(td::EncodeArgs)", "").replace("(anonymous namespace)::", "").replace("(td::WindowArgs)", "")
             out.append(f"{name} | {cur['VGPRs']} | {cur['VGPRs Spill']} | {cur['ScratchSize [bytes/lane]']} | {cur['Occupancy [waves/SIMD]']} | {v}")
-(ROOT / "profiles" / f"r{int(sys.argv[1]) if len(sys.argv) > 1 else 6}_resource_usage.txt").write_text("\n".join(out) + "\n")
+tag = sys.argv[1] if len(sys.argv) > 1 else "6"
+(ROOT / "profiles" / f"{'r' + tag if tag.isdigit() else tag}_resource_usage.txt").write_text("\n".join(out) + "\n")
 print("\n".join(out))
