@@ -542,6 +542,26 @@ class HipTokenizer:
         return out[:int(o[-1])]
 
     # ---- training rows (TD_ROWS_*) ------------------------------------------------------------------
+    @staticmethod
+    def _rows_buffers(kind: str, spec: RowsSpec, rows: int, n_docs: int, *want: bool):
+        """The host outputs of a rows call -> (arrays, their addresses, counts): ids, then positions and the further outputs of
+        `kind` where wanted (None otherwise).  "rows": aux; "pack": cu_seqlens, row_lengths, seg_docs; "windows": row_lengths,
+        row_docs, row_starts."""
+        slots, nseg = rows * spec.seq_len, n_docs + 2 * rows + 1
+        sizes = {"rows": [(n_docs + rows + 1 if spec.layout == TD_ROWS_CONCAT else n_docs, np.int32)],
+                 "pack": [(nseg, np.int32), (rows, np.int32), (nseg, np.int64)],
+                 "windows": [(rows, np.int32), (rows, np.int64), (rows, np.int64)]}[kind]
+        b = [np.empty(max(n, 1), dtype=dt) if w else None for w, (n, dt) in zip((True, *want), [(slots, np.int32)] * 2 + sizes)]
+        return b, [x.ctypes.data if x is not None else None for x in b], np.zeros(4, dtype=np.int64)
+
+    @staticmethod
+    def _rows_result(kind: str, spec: RowsSpec, b, counts, n_docs: int):
+        """The arrays of _rows_buffers cut to what the call wrote: ids and positions as [rows, S], the further outputs, counts."""
+        r, S, c2 = int(counts[0]), spec.seq_len, int(counts[2])
+        lens = {"rows": [c2 + 1 if spec.layout == TD_ROWS_CONCAT else n_docs], "pack": [c2 + 1, r, c2], "windows": [r, r, r]}[kind]
+        return (*(x[:r * S].reshape(r, S).copy() if x is not None else None for x in b[:2]),
+                *(x[:n].copy() if x is not None else None for x, n in zip(b[2:], lens)), counts)
+
     def make_rows(self, ids, tok_offsets, spec: RowsSpec, positions: bool = False, aux: bool = True, rows_capacity: int | None = None):
         """td_make_rows -> (ids int32[rows, S], positions int32[rows, S] or None, aux or None, counts int64[4]).
         aux: cu_seqlens (CONCAT, int32[n_seg + 1]) or lengths (PAD, int32[n_docs])."""
@@ -549,25 +569,10 @@ class HipTokenizer:
         o = np.ascontiguousarray(tok_offsets, dtype=np.int64)
         n_docs = len(o) - 1
         rows = rows_capacity if rows_capacity is not None else rows_capacity_of(spec, int(o[-1]) if len(o) else 0, n_docs)
-        S = spec.seq_len
-        out = np.empty(max(rows * S, 1), dtype=np.int32)
-        pos = np.empty(max(rows * S, 1), dtype=np.int32) if positions else None
-        concat = spec.layout == TD_ROWS_CONCAT
-        ax = np.empty(max(n_docs + rows + 1 if concat else n_docs, 1), dtype=np.int32) if aux else None
-        counts = np.zeros(4, dtype=np.int64)
+        b, (d_out, d_pos, d_aux), counts = self._rows_buffers("rows", spec, rows, n_docs, positions, aux)
         self._check(self._lib.td_make_rows(self._h, t.ctypes.data if len(t) else None, len(t), o.ctypes.data, n_docs, ctypes.byref(spec),
-                                           out.ctypes.data, rows, pos.ctypes.data if pos is not None else None,
-                                           ax.ctypes.data if ax is not None else None, counts.ctypes.data))
-        return self._rows_result(spec, out, pos, ax, counts, n_docs)
-
-    @staticmethod
-    def _rows_result(spec, out, pos, ax, counts, n_docs):
-        r, S = int(counts[0]), spec.seq_len
-        ids = out[:r * S].reshape(r, S).copy()
-        p = pos[:r * S].reshape(r, S).copy() if pos is not None else None
-        if ax is not None:
-            ax = ax[:int(counts[2]) + 1].copy() if spec.layout == TD_ROWS_CONCAT else ax[:n_docs].copy()
-        return ids, p, ax, counts
+                                           d_out, rows, d_pos, d_aux, counts.ctypes.data))
+        return self._rows_result("rows", spec, b, counts, n_docs)
 
     def make_rows_device(self, d_ids: int, n_tokens: int, d_tok_offsets: int, n_docs: int, spec: RowsSpec, d_out_ids: int,
                          rows_capacity: int, d_positions: int = 0, d_aux: int = 0, d_counts: int = 0, stream: int = 0):
@@ -583,36 +588,12 @@ class HipTokenizer:
         offs = np.ascontiguousarray(doc_offsets, dtype=np.int64)
         n_docs = len(offs) - 1
         rows = rows_capacity if rows_capacity is not None else rows_capacity_of(spec, int(offs[-1]) if len(offs) else 0, n_docs)
-        S = spec.seq_len
-        out = np.empty(max(rows * S, 1), dtype=np.int32)
-        pos = np.empty(max(rows * S, 1), dtype=np.int32) if positions else None
-        concat = spec.layout == TD_ROWS_CONCAT
-        ax = np.empty(max(n_docs + rows + 1 if concat else n_docs, 1), dtype=np.int32) if aux else None
-        counts = np.zeros(4, dtype=np.int64)
+        b, (d_out, d_pos, d_aux), counts = self._rows_buffers("rows", spec, rows, n_docs, positions, aux)
         self._check(self._lib.td_encode_batch_rows(self._h, buf.ctypes.data if len(buf) else None, offs.ctypes.data, n_docs, mode,
-                                                   ctypes.byref(spec), out.ctypes.data, rows, pos.ctypes.data if pos is not None else None,
-                                                   ax.ctypes.data if ax is not None else None, counts.ctypes.data))
-        return self._rows_result(spec, out, pos, ax, counts, n_docs)
+                                                   ctypes.byref(spec), d_out, rows, d_pos, d_aux, counts.ctypes.data))
+        return self._rows_result("rows", spec, b, counts, n_docs)
 
     # ---- best-fit rows (TD_ROWS_BESTFIT) --------------------------------------------------------------------
-    @staticmethod
-    def _pack_buffers(spec: RowsSpec, rows: int, n_docs: int, positions: bool, cu_seqlens: bool, lengths: bool, docs: bool):
-        S = spec.seq_len
-        slots = max(rows * S, 1)
-        nseg = max(n_docs + 2 * rows + 1, 1)
-        b = [np.empty(slots, dtype=np.int32), np.empty(slots, dtype=np.int32) if positions else None,
-             np.empty(nseg, dtype=np.int32) if cu_seqlens else None, np.empty(max(rows, 1), dtype=np.int32) if lengths else None,
-             np.empty(nseg, dtype=np.int64) if docs else None]
-        return b, PackOutputs(*[x.ctypes.data if x is not None else None for x in b])
-
-    @staticmethod
-    def _pack_result(spec: RowsSpec, b, counts):
-        r, S, nseg = int(counts[0]), spec.seq_len, int(counts[2])
-        ids, pos, cu, lens, docs = b
-        return (ids[:r * S].reshape(r, S).copy(), pos[:r * S].reshape(r, S).copy() if pos is not None else None,
-                cu[:nseg + 1].copy() if cu is not None else None, lens[:r].copy() if lens is not None else None,
-                docs[:nseg].copy() if docs is not None else None, counts)
-
     def pack_rows(self, ids, tok_offsets, spec: RowsSpec, positions: bool = False, cu_seqlens: bool = True, lengths: bool = False,
                   docs: bool = False, rows_capacity: int | None = None):
         """td_pack_rows -> (ids int32[rows, S], positions int32[rows, S] | None, cu_seqlens int32[segs + 1] | None,
@@ -622,11 +603,11 @@ class HipTokenizer:
         o = np.ascontiguousarray(tok_offsets, dtype=np.int64)
         n_docs = len(o) - 1
         rows = rows_capacity if rows_capacity is not None else int(pack_plan(o, spec)[0])
-        b, outs = self._pack_buffers(spec, rows, n_docs, positions, cu_seqlens, lengths, docs)
-        counts = np.zeros(4, dtype=np.int64)
+        b, addr, counts = self._rows_buffers("pack", spec, rows, n_docs, positions, cu_seqlens, lengths, docs)
+        outs = PackOutputs(*addr)
         self._check(self._lib.td_pack_rows(self._h, t.ctypes.data if len(t) else None, len(t), o.ctypes.data, n_docs, ctypes.byref(spec),
                                            ctypes.byref(outs), rows, counts.ctypes.data))
-        return self._pack_result(spec, b, counts)
+        return self._rows_result("pack", spec, b, counts, n_docs)
 
     def pack_rows_device(self, d_ids: int, n_tokens: int, d_tok_offsets: int, n_docs: int, spec: RowsSpec, d_out_ids: int,
                          rows_capacity: int, d_positions: int = 0, d_cu_seqlens: int = 0, d_row_lengths: int = 0, d_seg_docs: int = 0,
@@ -654,29 +635,13 @@ class HipTokenizer:
         rows = rows_capacity if rows_capacity is not None else pack_rows_capacity_of(spec, int(offs[-1]) if len(offs) else 0, n_docs)
         if rows_capacity is None and cu_seqlens:
             rows = min(rows, ((1 << 31) - 1) // spec.seq_len)  # (cu_seqlens entries are int32)
-        b, outs = self._pack_buffers(spec, rows, n_docs, positions, cu_seqlens, lengths, docs)
-        counts = np.zeros(4, dtype=np.int64)
+        b, addr, counts = self._rows_buffers("pack", spec, rows, n_docs, positions, cu_seqlens, lengths, docs)
+        outs = PackOutputs(*addr)
         self._check(self._lib.td_encode_batch_pack_rows(self._h, buf.ctypes.data if len(buf) else None, offs.ctypes.data, n_docs, mode,
                                                         ctypes.byref(spec), ctypes.byref(outs), rows, counts.ctypes.data))
-        return self._pack_result(spec, b, counts)
+        return self._rows_result("pack", spec, b, counts, n_docs)
 
     # ---- window rows (TD_ROWS_WINDOWS) ------------------------------------------------------------------------
-    @staticmethod
-    def _window_buffers(spec: RowsSpec, rows: int, positions: bool, lengths: bool, docs: bool, starts: bool):
-        slots, nr = max(rows * spec.seq_len, 1), max(rows, 1)
-        b = [np.empty(slots, dtype=np.int32), np.empty(slots, dtype=np.int32) if positions else None,
-             np.empty(nr, dtype=np.int32) if lengths else None, np.empty(nr, dtype=np.int64) if docs else None,
-             np.empty(nr, dtype=np.int64) if starts else None]
-        return b, WindowOutputs(*[x.ctypes.data if x is not None else None for x in b])
-
-    @staticmethod
-    def _window_result(spec: RowsSpec, b, counts):
-        r, S = int(counts[0]), spec.seq_len
-        ids, pos, lens, docs, starts = b
-        return (ids[:r * S].reshape(r, S).copy(), pos[:r * S].reshape(r, S).copy() if pos is not None else None,
-                lens[:r].copy() if lens is not None else None, docs[:r].copy() if docs is not None else None,
-                starts[:r].copy() if starts is not None else None, counts)
-
     def window_rows(self, ids, tok_offsets, spec: RowsSpec, overlap: int = 0, positions: bool = False, lengths: bool = True,
                     docs: bool = True, starts: bool = True, rows_capacity: int | None = None):
         """td_window_rows -> (ids int32[rows, S], positions int32[rows, S] | None, row_lengths int32[rows] | None,
@@ -686,8 +651,8 @@ class HipTokenizer:
         o = np.ascontiguousarray(tok_offsets, dtype=np.int64)
         n_docs = len(o) - 1
         rows = rows_capacity if rows_capacity is not None else int(window_plan(o, spec, overlap)[0])
-        b, outs = self._window_buffers(spec, rows, positions, lengths, docs, starts)
-        counts = np.zeros(4, dtype=np.int64)
+        b, addr, counts = self._rows_buffers("windows", spec, rows, n_docs, positions, lengths, docs, starts)
+        outs = WindowOutputs(*addr)
         rc = self._lib.td_window_rows(self._h, t.ctypes.data if len(t) else None, len(t), o.ctypes.data, n_docs, ctypes.byref(spec), overlap,
                                       ctypes.byref(outs), rows, counts.ctypes.data)
         try:
@@ -695,7 +660,7 @@ class HipTokenizer:
         except TokenDaggerHipError as ex:
             ex.counts = counts  # (TD_E_CAPACITY: counts[0] = the rows needed)
             raise
-        return self._window_result(spec, b, counts)
+        return self._rows_result("windows", spec, b, counts, n_docs)
 
     def window_rows_device(self, d_ids: int, n_tokens: int, d_tok_offsets: int, n_docs: int, spec: RowsSpec, overlap: int, d_out_ids: int,
                            rows_capacity: int, d_positions: int = 0, d_row_lengths: int = 0, d_row_docs: int = 0, d_row_starts: int = 0,
@@ -715,11 +680,11 @@ class HipTokenizer:
         n_docs = len(offs) - 1
         step = spec.seq_len - (spec.bos_id >= 0) - (spec.eos_id >= 0) - overlap
         rows = rows_capacity if rows_capacity is not None else n_docs + (int(offs[-1]) if len(offs) else 0) // max(step, 1)
-        b, outs = self._window_buffers(spec, rows, positions, lengths, docs, starts)
-        counts = np.zeros(4, dtype=np.int64)
+        b, addr, counts = self._rows_buffers("windows", spec, rows, n_docs, positions, lengths, docs, starts)
+        outs = WindowOutputs(*addr)
         self._check(self._lib.td_encode_batch_window_rows(self._h, buf.ctypes.data if len(buf) else None, offs.ctypes.data, n_docs, mode,
                                                           ctypes.byref(spec), overlap, ctypes.byref(outs), rows, counts.ctypes.data))
-        return self._window_result(spec, b, counts)
+        return self._rows_result("windows", spec, b, counts, n_docs)
 
     def device_status_pos(self, stream: int = 0) -> tuple[int, int]:
         """td_device_status without raising: (code, err_pos)."""

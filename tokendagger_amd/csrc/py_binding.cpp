@@ -551,34 +551,46 @@ public:
         const int64_t t = n_ids + n_docs * ((sp.bos_id >= 0) + (sp.eos_id >= 0));
         return (sp.flags & TD_ROWS_DROP_LAST) ? t / sp.seq_len : (t + sp.seq_len - 1) / sp.seq_len;
     }
+    // What the rows calls of every layout share: ids and positions of rows_cap rows, counts; the call without the GIL; ids and
+    // positions cut to the rows made.  A further output of a layout: opt() before the call, cut() behind it.
+    struct RowsBufs {
+        int64_t S, slots;
+        py::array_t<int32_t> ids, pos;
+        py::array_t<int64_t> counts;
+        RowsBufs(const td_rows_spec& sp, int64_t rows_cap, bool positions)
+            : S(sp.seq_len > 0 ? sp.seq_len : 1), slots(std::max<int64_t>(rows_cap * S, 1)), ids(slots), pos(positions ? slots : 0), counts(4) {}
+        int64_t count(int i) const { return counts.data()[i]; }
+    };
+    template <class T>
+    static T* opt(py::array_t<T>& a, bool want) { return want ? a.mutable_data() : nullptr; }
+    template <class T>
+    static py::object cut(py::array_t<T>& a, bool want, int64_t n) {
+        if (!want) return py::none();
+        a.resize({(py::ssize_t)n}, false);
+        return a;
+    }
     template <class F>
-    py::tuple rows_call(const td_rows_spec& sp, int64_t rows_cap, int64_t n_docs, bool positions, bool aux, F&& call) {
-        const int64_t S = sp.seq_len > 0 ? sp.seq_len : 1, slots = std::max<int64_t>(rows_cap * S, 1);
-        const bool concat = sp.layout == TD_ROWS_CONCAT;
-        py::array_t<int32_t> ids(slots), pos(positions ? slots : 0), ax(aux ? std::max<int64_t>(concat ? n_docs + rows_cap + 1 : n_docs, 1) : 0);
-        py::array_t<int64_t> counts(4);
+    void rows_run(RowsBufs& b, F&& call) {  // call(counts) -> rc
         int rc;
         {
-            int32_t* ip = ids.mutable_data();
-            int32_t* pp = positions ? pos.mutable_data() : nullptr;
-            int32_t* ap = aux ? ax.mutable_data() : nullptr;
-            int64_t* cp = counts.mutable_data();
+            int64_t* cp = b.counts.mutable_data();
             py::gil_scoped_release rel;
-            rc = call(ip, pp, ap, cp);
+            rc = call(cp);
         }
         if (rc != TD_OK) fail();
-        const int64_t rows = counts.data()[0];
-        ids.resize({(py::ssize_t)(rows * S)}, false);
-        py::object p = py::none(), a = py::none();
-        if (positions) {
-            pos.resize({(py::ssize_t)(rows * S)}, false);
-            p = pos.attr("reshape")(rows, S);
-        }
-        if (aux) {
-            ax.resize({(py::ssize_t)(concat ? counts.data()[2] + 1 : n_docs)}, false);
-            a = ax;
-        }
-        return py::make_tuple(ids.attr("reshape")(rows, S), p, a, counts);
+    }
+    static py::object rows_2d(py::array_t<int32_t>& a, bool want, const RowsBufs& b) {
+        py::object o = cut(a, want, b.count(0) * b.S);
+        return want ? o.attr("reshape")(b.count(0), b.S) : o;
+    }
+    template <class F>
+    py::tuple rows_call(const td_rows_spec& sp, int64_t rows_cap, int64_t n_docs, bool positions, bool aux, F&& call) {
+        const bool concat = sp.layout == TD_ROWS_CONCAT;
+        RowsBufs b(sp, rows_cap, positions);
+        py::array_t<int32_t> ax(aux ? std::max<int64_t>(concat ? n_docs + rows_cap + 1 : n_docs, 1) : 0);
+        int32_t *ip = b.ids.mutable_data(), *pp = opt(b.pos, positions), *ap = opt(ax, aux);
+        rows_run(b, [&](int64_t* cp) { return call(ip, pp, ap, cp); });
+        return py::make_tuple(rows_2d(b.ids, true, b), rows_2d(b.pos, positions, b), cut(ax, aux, concat ? b.count(2) + 1 : n_docs), b.counts);
     }
     py::tuple encode_batch_numpy_rows(py::array_t<uint8_t, py::array::c_style | py::array::forcecast> text,
                                       py::array_t<int64_t, py::array::c_style | py::array::forcecast> offsets, int64_t seq_len, int layout,
@@ -614,30 +626,15 @@ public:
     //     counts int64[4]); an output not asked for is None
     template <class F>
     py::tuple pack_call(const td_rows_spec& sp, int64_t rows_cap, int64_t n_docs, bool positions, bool cu, bool lengths, bool docs, F&& call) {
-        const int64_t S = sp.seq_len > 0 ? sp.seq_len : 1, slots = std::max<int64_t>(rows_cap * S, 1);
         const int64_t nseg = std::max<int64_t>(n_docs + 2 * rows_cap + 1, 1);
-        py::array_t<int32_t> ids(slots), pos(positions ? slots : 0), cs(cu ? nseg : 0), ls(lengths ? std::max<int64_t>(rows_cap, 1) : 0);
-        py::array_t<int64_t> ds(docs ? nseg : 0), counts(4);
-        int rc;
-        {
-            td_pack_outputs o{ids.mutable_data(), positions ? pos.mutable_data() : nullptr, cu ? cs.mutable_data() : nullptr,
-                              lengths ? ls.mutable_data() : nullptr, docs ? ds.mutable_data() : nullptr};
-            int64_t* cp = counts.mutable_data();
-            py::gil_scoped_release rel;
-            rc = call(&o, cp);
-        }
-        if (rc != TD_OK) fail();
-        const int64_t rows = counts.data()[0], segs = counts.data()[2];
-        ids.resize({(py::ssize_t)(rows * S)}, false);
-        py::object p = py::none(), c = py::none(), l = py::none(), d = py::none();
-        if (positions) {
-            pos.resize({(py::ssize_t)(rows * S)}, false);
-            p = pos.attr("reshape")(rows, S);
-        }
-        if (cu) { cs.resize({(py::ssize_t)(segs + 1)}, false); c = cs; }
-        if (lengths) { ls.resize({(py::ssize_t)rows}, false); l = ls; }
-        if (docs) { ds.resize({(py::ssize_t)segs}, false); d = ds; }
-        return py::make_tuple(ids.attr("reshape")(rows, S), p, c, l, d, counts);
+        RowsBufs b(sp, rows_cap, positions);
+        py::array_t<int32_t> cs(cu ? nseg : 0), ls(lengths ? std::max<int64_t>(rows_cap, 1) : 0);
+        py::array_t<int64_t> ds(docs ? nseg : 0);
+        const td_pack_outputs o{b.ids.mutable_data(), opt(b.pos, positions), opt(cs, cu), opt(ls, lengths), opt(ds, docs)};
+        rows_run(b, [&](int64_t* cp) { return call(&o, cp); });
+        const int64_t rows = b.count(0), segs = b.count(2);
+        return py::make_tuple(rows_2d(b.ids, true, b), rows_2d(b.pos, positions, b), cut(cs, cu, segs + 1), cut(ls, lengths, rows),
+                              cut(ds, docs, segs), b.counts);
     }
     py::tuple ids_to_packed_rows(py::array_t<int32_t, py::array::c_style | py::array::forcecast> ids,
                                  py::array_t<int64_t, py::array::c_style | py::array::forcecast> tok_offsets, int64_t seq_len, int64_t bos,
@@ -678,29 +675,15 @@ public:
     //     counts int64[4]); an output not asked for is None
     template <class F>
     py::tuple window_call(const td_rows_spec& sp, int64_t rows_cap, bool positions, bool lengths, bool docs, bool starts, F&& call) {
-        const int64_t S = sp.seq_len > 0 ? sp.seq_len : 1, slots = std::max<int64_t>(rows_cap * S, 1), nr = std::max<int64_t>(rows_cap, 1);
-        py::array_t<int32_t> ids(slots), pos(positions ? slots : 0), ls(lengths ? nr : 0);
-        py::array_t<int64_t> ds(docs ? nr : 0), ss(starts ? nr : 0), counts(4);
-        int rc;
-        {
-            td_window_outputs o{ids.mutable_data(), positions ? pos.mutable_data() : nullptr, lengths ? ls.mutable_data() : nullptr,
-                                docs ? ds.mutable_data() : nullptr, starts ? ss.mutable_data() : nullptr};
-            int64_t* cp = counts.mutable_data();
-            py::gil_scoped_release rel;
-            rc = call(&o, cp);
-        }
-        if (rc != TD_OK) fail();
-        const int64_t rows = counts.data()[0];
-        ids.resize({(py::ssize_t)(rows * S)}, false);
-        py::object p = py::none(), l = py::none(), d = py::none(), st = py::none();
-        if (positions) {
-            pos.resize({(py::ssize_t)(rows * S)}, false);
-            p = pos.attr("reshape")(rows, S);
-        }
-        if (lengths) { ls.resize({(py::ssize_t)rows}, false); l = ls; }
-        if (docs) { ds.resize({(py::ssize_t)rows}, false); d = ds; }
-        if (starts) { ss.resize({(py::ssize_t)rows}, false); st = ss; }
-        return py::make_tuple(ids.attr("reshape")(rows, S), p, l, d, st, counts);
+        const int64_t nr = std::max<int64_t>(rows_cap, 1);
+        RowsBufs b(sp, rows_cap, positions);
+        py::array_t<int32_t> ls(lengths ? nr : 0);
+        py::array_t<int64_t> ds(docs ? nr : 0), ss(starts ? nr : 0);
+        const td_window_outputs o{b.ids.mutable_data(), opt(b.pos, positions), opt(ls, lengths), opt(ds, docs), opt(ss, starts)};
+        rows_run(b, [&](int64_t* cp) { return call(&o, cp); });
+        const int64_t rows = b.count(0);
+        return py::make_tuple(rows_2d(b.ids, true, b), rows_2d(b.pos, positions, b), cut(ls, lengths, rows), cut(ds, docs, rows),
+                              cut(ss, starts, rows), b.counts);
     }
     py::tuple ids_to_window_rows(py::array_t<int32_t, py::array::c_style | py::array::forcecast> ids,
                                  py::array_t<int64_t, py::array::c_style | py::array::forcecast> tok_offsets, int64_t seq_len, int64_t overlap,

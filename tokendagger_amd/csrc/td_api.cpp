@@ -12,6 +12,7 @@
 #include <memory>
 #include <mutex>
 #include <thread>
+#include <type_traits>
 #include <string>
 #include <vector>
 
@@ -889,22 +890,43 @@ int encode_starts_locked(td_tokenizer* t, const void* d_text, int64_t n, const v
     return order_after(t, stream);
 }
 
-// ---- training rows (td_rows.hip) -------------------------------------------------------------------------------------------
-// The checks of a spec that need no handle (nullptr: fine).  want_cu: CONCAT with cu_seqlens requested.
-const char* rows_spec_error(const td_rows_spec* sp, int64_t rows_capacity, bool want_cu) {
+// ---- training rows (td_rows.hip, td_pack.hip, td_windows.hip): what the layouts share ----------------------------------------
+enum RowsFamily { FAM_ROWS, FAM_BESTFIT, FAM_WINDOWS };  // the layouts an entry point takes: CONCAT / PAD, BESTFIT, WINDOWS
+
+// The checks of a spec that need no handle (nullptr: fine).  overlap: FAM_WINDOWS only; want_cu: cu_seqlens requested.
+const char* rows_spec_error(RowsFamily fam, const td_rows_spec* sp, int64_t overlap, int64_t rows_capacity, bool want_cu) {
     if (!sp) return "null td_rows_spec";
-    if (sp->layout != TD_ROWS_CONCAT && sp->layout != TD_ROWS_PAD) return "layout must be TD_ROWS_CONCAT or TD_ROWS_PAD";
+    if (fam == FAM_ROWS && sp->layout != TD_ROWS_CONCAT && sp->layout != TD_ROWS_PAD) return "layout must be TD_ROWS_CONCAT or TD_ROWS_PAD";
+    if (fam == FAM_BESTFIT && sp->layout != TD_ROWS_BESTFIT) return "layout must be TD_ROWS_BESTFIT";
+    if (fam == FAM_WINDOWS && sp->layout != TD_ROWS_WINDOWS) return "layout must be TD_ROWS_WINDOWS";
     if (sp->seq_len < 1 || sp->seq_len > INT32_MAX) return "seq_len must be in 1 .. 2^31 - 1";
-    if (sp->flags & ~(int64_t)TD_ROWS_DROP_LAST) return "unknown td_rows_spec flags";
-    if ((sp->flags & TD_ROWS_DROP_LAST) && sp->layout != TD_ROWS_CONCAT) return "TD_ROWS_DROP_LAST is for TD_ROWS_CONCAT only";
+    if (fam == FAM_ROWS && (sp->flags & ~(int64_t)TD_ROWS_DROP_LAST)) return "unknown td_rows_spec flags";
+    if (fam == FAM_ROWS && (sp->flags & TD_ROWS_DROP_LAST) && sp->layout != TD_ROWS_CONCAT) return "TD_ROWS_DROP_LAST is for TD_ROWS_CONCAT only";
+    if (fam == FAM_BESTFIT && (sp->flags & ~(int64_t)TD_ROWS_TRUNCATE)) return "flags must be 0 or TD_ROWS_TRUNCATE";
+    if (fam == FAM_WINDOWS && sp->flags != 0) return "flags must be 0";
     if (sp->pad_id < INT32_MIN || sp->pad_id > INT32_MAX) return "pad_id must be an int32";
-    const int64_t k = (sp->bos_id >= 0) + (sp->eos_id >= 0);
-    if (sp->layout == TD_ROWS_PAD && sp->seq_len < k) return "TD_ROWS_PAD needs seq_len >= the BOS and EOS slots";
+    const int64_t C = sp->seq_len - (sp->bos_id >= 0) - (sp->eos_id >= 0);  // body room
+    if (sp->layout == TD_ROWS_PAD && C < 0) return "TD_ROWS_PAD needs seq_len >= the BOS and EOS slots";
+    if (fam == FAM_BESTFIT && (sp->flags & TD_ROWS_TRUNCATE) && C < 0) return "TD_ROWS_TRUNCATE needs seq_len >= the BOS and EOS slots";
+    if (fam == FAM_WINDOWS && C < 1) return "seq_len must leave room for one id beside BOS and EOS";
+    if (fam == FAM_WINDOWS && (overlap < 0 || overlap >= C)) return "overlap must be in 0 .. seq_len - BOS - EOS - 1";
     if (rows_capacity < 0) return "rows_capacity must be >= 0";
     if (rows_capacity > ((int64_t)1 << 62) / sp->seq_len) return "rows_capacity * seq_len is too large";
     if (want_cu && rows_capacity * sp->seq_len >= ((int64_t)1 << 31))
         return "cu_seqlens entries are int32: rows_capacity * seq_len must stay below 2^31";
     return nullptr;
+}
+
+// The outputs struct of a BESTFIT (td_pack_outputs) or WINDOWS (td_window_outputs) entry point, then its spec.
+template <class O>
+const char* rows_args_error(const td_rows_spec* sp, int64_t overlap, int64_t n_docs, int64_t rows_capacity, const O* o) {
+    constexpr bool pack = std::is_same<O, td_pack_outputs>::value;
+    if (!o) return pack ? "null td_pack_outputs" : "null td_window_outputs";
+    if (n_docs > INT32_MAX) return pack ? "n_docs must be below 2^31" : "n_docs must stay below 2^31";
+    if (rows_capacity > 0 && !o->ids) return "null ids output";
+    bool want_cu = false;
+    if constexpr (pack) want_cu = o->cu_seqlens != nullptr;
+    return rows_spec_error(pack ? FAM_BESTFIT : FAM_WINDOWS, sp, overlap, rows_capacity, want_cu);
 }
 
 // bos_id / eos_id: -1, or an id of the vocabulary (ordinary or special)
@@ -915,6 +937,12 @@ int rows_check_ids(td_tokenizer* t, const td_rows_spec* sp) {
             return fail_unlocked(t, TD_E_BAD_TOKEN, "td_rows_spec: bos_id / eos_id " + std::to_string(id) + " is not in the vocabulary");
     }
     return TD_OK;
+}
+
+// The entry points' step between their null tests and the lock: a spec or outputs error `m` as "<fn>: <m>", then the ids' check.
+int rows_spec_fail(td_tokenizer* t, const char* fn, const char* m, const td_rows_spec* sp) {
+    if (m) return fail_unlocked(t, TD_E_INVALID, std::string(fn) + ": " + m);
+    return rows_check_ids(t, sp);
 }
 
 int64_t rows_needed(const td_rows_spec* sp, int64_t n_ids, int64_t n_docs) {
@@ -928,26 +956,32 @@ int rows_funnel_src() {  // TD_ROWS_FUNNEL=1 in the environment: misaligned ids 
     return v;
 }
 
+// Zeroes a RowsArgs / PackArgs / WindowArgs and fills the fields they share: the input and the spec's framing.
+template <class A>
+void rows_fill_args(A& a, const void* d_ids, int64_t n_tokens, const void* d_toff, int64_t n_docs, const td_rows_spec* sp) {
+    memset(&a, 0, sizeof a);
+    a.ids = (const int32_t*)d_ids;
+    a.n_tokens = n_tokens;
+    a.tok_off = (const int64_t*)d_toff;
+    a.n_docs = n_docs;
+    a.S = sp->seq_len;
+    a.b = sp->bos_id >= 0;
+    a.e = sp->eos_id >= 0;
+    a.bos = a.b ? (int32_t)sp->bos_id : 0;
+    a.eos = a.e ? (int32_t)sp->eos_id : 0;
+    a.pad = (int32_t)sp->pad_id;
+}
+
 int rows_launch_locked(td_tokenizer* t, const void* d_ids, int64_t n_tokens, const void* d_toff, int64_t n_docs, const td_rows_spec* sp,
                        void* d_out, int64_t cap, void* d_pos, void* d_aux, void* d_counts, hipStream_t s) {
     int rc;
     if ((rc = order_before(t, s))) return rc;
     t->rows_last = true;
     RowsArgs a;
-    memset(&a, 0, sizeof a);
-    a.ids = (const int32_t*)d_ids;
-    a.n_tokens = n_tokens;
-    a.tok_off = (const int64_t*)d_toff;
-    a.n_docs = n_docs;
+    rows_fill_args(a, d_ids, n_tokens, d_toff, n_docs, sp);
     a.layout = (int)sp->layout;
     a.drop_last = (sp->flags & TD_ROWS_DROP_LAST) ? 1 : 0;
-    a.S = sp->seq_len;
     a.s_magic = ~0ull / (unsigned long long)sp->seq_len;
-    a.b = sp->bos_id >= 0;
-    a.e = sp->eos_id >= 0;
-    a.bos = a.b ? (int32_t)sp->bos_id : 0;
-    a.eos = a.e ? (int32_t)sp->eos_id : 0;
-    a.pad = (int32_t)sp->pad_id;
     a.funnel_src = rows_funnel_src();
     a.out = (int32_t*)d_out;
     a.rows_cap = cap;
@@ -969,27 +1003,47 @@ int rows_launch_locked(td_tokenizer* t, const void* d_ids, int64_t n_tokens, con
     return order_after(t, s);
 }
 
+// One output of a host-bound form: made on the device in the handle's buffer `dev`, then copied to the caller's `host`.
+struct RowsOut {
+    bool want;
+    void* host;
+    DevBuf* dev;
+    size_t elem;              // bytes an element
+    int64_t n_alloc, n_copy;  // elements the kernels may write, elements the caller gets
+    void* p() const { return want ? dev->p : nullptr; }
+};
+
+int rows_out_ensure(td_tokenizer* t, const RowsOut* o, int n) {
+    int rc;
+    for (int i = 0; i < n; ++i)
+        if (o[i].want && (rc = ensure(t, *o[i].dev, (size_t)std::max<int64_t>(o[i].n_alloc, 1) * o[i].elem))) return rc;
+    return TD_OK;
+}
+
+int rows_out_copy(td_tokenizer* t, const RowsOut* o, int n, hipStream_t s) {
+    int rc;
+    for (int i = 0; i < n; ++i)
+        if (o[i].want && (rc = copy_wait(t, o[i].host, o[i].dev->p, (size_t)o[i].n_copy * o[i].elem, hipMemcpyDeviceToHost, s))) return rc;
+    return TD_OK;
+}
+
 // Host entry points: rows (known on the host, checked against the capacity by the caller) from ids already on the device, into
 // the handle's buffers, then to the caller's.
 int rows_to_host(td_tokenizer* t, const void* d_ids, int64_t n_ids, const void* d_toff, int64_t n_docs, const td_rows_spec* sp, int64_t rows,
                  int32_t* out_ids, int32_t* out_pos, int32_t* out_aux, int64_t* counts, hipStream_t s) {
     int rc;
     const bool concat = sp->layout == TD_ROWS_CONCAT;
-    const int64_t slots = rows * sp->seq_len, aux_n = concat ? n_docs + rows + 1 : n_docs;
-    if ((rc = ensure(t, t->rows_out, (size_t)std::max<int64_t>(slots, 1) * 4))) return rc;
-    if (out_pos && (rc = ensure(t, t->rows_pos, (size_t)std::max<int64_t>(slots, 1) * 4))) return rc;
-    if (out_aux && (rc = ensure(t, t->rows_aux, (size_t)std::max<int64_t>(aux_n, 1) * 4))) return rc;
+    const int64_t slots = rows * sp->seq_len;
+    RowsOut o[] = {{true, out_ids, &t->rows_out, 4, slots, slots},
+                   {out_pos != nullptr, out_pos, &t->rows_pos, 4, slots, slots},
+                   {out_aux != nullptr, out_aux, &t->rows_aux, 4, concat ? n_docs + rows + 1 : n_docs, n_docs}};
+    if ((rc = rows_out_ensure(t, o, 3))) return rc;
     if ((rc = ensure(t, t->rows_counts, 4 * sizeof(int64_t)))) return rc;
-    if ((rc = rows_launch_locked(t, d_ids, n_ids, d_toff, n_docs, sp, t->rows_out.p, rows, out_pos ? t->rows_pos.p : nullptr,
-                                 out_aux ? t->rows_aux.p : nullptr, t->rows_counts.p, s)))
-        return rc;
+    if ((rc = rows_launch_locked(t, d_ids, n_ids, d_toff, n_docs, sp, o[0].p(), rows, o[1].p(), o[2].p(), t->rows_counts.p, s))) return rc;
     if ((rc = device_status_locked(t, s, nullptr))) return rc;
     if ((rc = copy_wait(t, counts, t->rows_counts.p, 4 * sizeof(int64_t), hipMemcpyDeviceToHost, s))) return rc;
-    if ((rc = copy_wait(t, out_ids, t->rows_out.p, (size_t)slots * 4, hipMemcpyDeviceToHost, s))) return rc;
-    if (out_pos && (rc = copy_wait(t, out_pos, t->rows_pos.p, (size_t)slots * 4, hipMemcpyDeviceToHost, s))) return rc;
-    if (out_aux && (rc = copy_wait(t, out_aux, t->rows_aux.p, (size_t)(concat ? counts[2] + 1 : n_docs) * 4, hipMemcpyDeviceToHost, s)))
-        return rc;
-    return TD_OK;
+    if (concat) o[2].n_copy = counts[2] + 1;  // (cu_seqlens: the segments and the end)
+    return rows_out_copy(t, o, 3, s);
 }
 
 int rows_capacity_fail(td_tokenizer* t, int64_t rows, int64_t* counts) {
@@ -999,29 +1053,56 @@ int rows_capacity_fail(td_tokenizer* t, int64_t rows, int64_t* counts) {
     return TD_E_CAPACITY;
 }
 
+int check_offsets(td_tokenizer* t, const char* what, const int64_t* offs, int64_t n_docs, const void* payload);
+
+// td_make_rows, td_pack_rows, td_window_rows: the checks of the caller's ids and offsets (nothing allocated, nothing enqueued) ...
+int rows_check_host_ids(td_tokenizer* t, const int32_t* ids, int64_t n_tokens, const int64_t* tok_offsets, int64_t n_docs) {
+    int rc;
+    if ((rc = check_offsets(t, "tok_offsets", tok_offsets, n_docs, ids))) return rc;
+    if (tok_offsets[n_docs] > n_tokens) { t->err = "tok_offsets[n_docs] exceeds n_tokens"; return TD_E_INVALID; }
+    return TD_OK;
+}
+
+// ... and their upload into dec_tokens / d_offsets on the handle's own stream `s`.
+int rows_stage_host_ids(td_tokenizer* t, const int32_t* ids, const int64_t* tok_offsets, int64_t n_docs, hipStream_t& s) {
+    int rc;
+    const int64_t total = tok_offsets[n_docs];
+    if ((rc = ensure(t, t->dec_tokens, (size_t)std::max<int64_t>(total, 1) * 4))) return rc;
+    if ((rc = ensure(t, t->d_offsets, (size_t)(n_docs + 1) * 8))) return rc;
+    if ((rc = own_streams(t))) return rc;
+    s = t->s_own;
+    if ((rc = order_before(t, s))) return rc;
+    if (total > 0) HIP_TRY(t, hipMemcpyAsync(t->dec_tokens.p, ids, (size_t)total * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(t, hipMemcpyAsync(t->d_offsets.p, tok_offsets, (size_t)(n_docs + 1) * 8, hipMemcpyHostToDevice, s));
+    return TD_OK;
+}
+
+// td_encode_batch_rows, _pack_rows, _window_rows: the documents encoded on the handle's own stream `s` into d_tokens (room for
+// dev_cap ids) / d_offsets, and the encode's errors returned as such, before the rows read its ids.
+int rows_encode_locked(td_tokenizer* t, const uint8_t* text, const int64_t* doc_offsets, int64_t n_docs, int mode, int64_t& dev_cap,
+                       hipStream_t& s) {
+    int rc;
+    if ((rc = check_offsets(t, "doc_offsets", doc_offsets, n_docs, text))) return rc;
+    const int64_t n = doc_offsets[n_docs];
+    dev_cap = std::max<int64_t>(n, 1);  // (at most one id per byte)
+    if ((rc = ensure(t, t->h2d_text, (size_t)n + 64))) return rc;
+    if ((rc = ensure(t, t->h2d_offs, (size_t)(n_docs + 1) * 8))) return rc;
+    if ((rc = ensure(t, t->d_offsets, (size_t)(n_docs + 1) * 8))) return rc;
+    if ((rc = ensure(t, t->d_tokens, (size_t)dev_cap * 4))) return rc;
+    if ((rc = own_streams(t))) return rc;
+    s = t->s_own;
+    if ((rc = order_before(t, s))) return rc;
+    if (n > 0) {
+        HIP_TRY(t, hipMemcpyAsync(t->h2d_text.p, text, (size_t)n, hipMemcpyHostToDevice, s));
+        HIP_TRY(t, hipMemcpyAsync(t->h2d_offs.p, doc_offsets, (size_t)(n_docs + 1) * 8, hipMemcpyHostToDevice, s));
+        if ((rc = encode_device_locked(t, t->h2d_text.p, n, t->h2d_offs.p, n_docs, mode, t->d_tokens.p, dev_cap, t->d_offsets.p, s))) return rc;
+    } else {  // (nothing but empty documents: no encode)
+        HIP_TRY(t, hipMemsetAsync(t->d_offsets.p, 0, (size_t)(n_docs + 1) * 8, s));
+    }
+    return device_status_locked(t, s, nullptr);
+}
+
 // ---- window rows (td_windows.hip) ---------------------------------------------------------------------------------------------
-// The checks of a TD_ROWS_WINDOWS spec that need no handle.
-const char* window_spec_error(const td_rows_spec* sp, int64_t overlap, int64_t rows_capacity) {
-    if (!sp) return "null td_rows_spec";
-    if (sp->layout != TD_ROWS_WINDOWS) return "layout must be TD_ROWS_WINDOWS";
-    if (sp->seq_len < 1 || sp->seq_len > INT32_MAX) return "seq_len must be in 1 .. 2^31 - 1";
-    if (sp->flags != 0) return "flags must be 0";
-    if (sp->pad_id < INT32_MIN || sp->pad_id > INT32_MAX) return "pad_id must be an int32";
-    const int64_t C = sp->seq_len - (sp->bos_id >= 0) - (sp->eos_id >= 0);
-    if (C < 1) return "seq_len must leave room for one id beside BOS and EOS";
-    if (overlap < 0 || overlap >= C) return "overlap must be in 0 .. seq_len - BOS - EOS - 1";
-    if (rows_capacity < 0) return "rows_capacity must be >= 0";
-    if (rows_capacity > ((int64_t)1 << 62) / sp->seq_len) return "rows_capacity * seq_len is too large";
-    return nullptr;
-}
-
-const char* window_args_error(const td_rows_spec* sp, int64_t overlap, int64_t n_docs, int64_t rows_capacity, const td_window_outputs* o) {
-    if (!o) return "null td_window_outputs";
-    if (n_docs > INT32_MAX) return "n_docs must stay below 2^31";
-    if (rows_capacity > 0 && !o->ids) return "null ids output";
-    return window_spec_error(sp, overlap, rows_capacity);
-}
-
 // w_d = max(1, ceil((L - overlap) / step))
 int64_t window_count(int64_t L, int64_t C, int64_t overlap) { return L <= C ? 1 : (L - overlap + (C - overlap) - 1) / (C - overlap); }
 
@@ -1032,22 +1113,12 @@ int window_launch_locked(td_tokenizer* t, const void* d_ids, int64_t n_tokens, c
     if ((rc = order_before(t, s))) return rc;
     t->rows_last = true;
     WindowArgs a;
-    memset(&a, 0, sizeof a);
-    a.ids = (const int32_t*)d_ids;
-    a.n_tokens = n_tokens;
-    a.tok_off = (const int64_t*)d_toff;
-    a.n_docs = n_docs;
-    a.b = sp->bos_id >= 0;
-    a.e = sp->eos_id >= 0;
-    a.S = sp->seq_len;
+    rows_fill_args(a, d_ids, n_tokens, d_toff, n_docs, sp);
     a.C = a.S - a.b - a.e;
     a.overlap = overlap;
     a.step = a.C - overlap;
     a.s_magic = ~0ull / (unsigned long long)a.S;
     a.step_magic = ~0ull / (unsigned long long)a.step;
-    a.bos = a.b ? (int32_t)sp->bos_id : 0;
-    a.eos = a.e ? (int32_t)sp->eos_id : 0;
-    a.pad = (int32_t)sp->pad_id;
     a.out = o.ids;
     a.rows_cap = cap;
     a.pos = o.positions;
@@ -1073,51 +1144,22 @@ int window_launch_locked(td_tokenizer* t, const void* d_ids, int64_t n_tokens, c
 int window_to_host(td_tokenizer* t, const void* d_ids, int64_t n_ids, const void* d_toff, int64_t n_docs, const td_rows_spec* sp,
                    int64_t overlap, const td_window_outputs& ho, int64_t rows, int64_t* counts, hipStream_t s) {
     int rc;
-    const size_t slots = (size_t)std::max<int64_t>(rows * sp->seq_len, 1), nr = (size_t)std::max<int64_t>(rows, 1);
-    td_window_outputs d{};
-    if ((rc = ensure(t, t->rows_out, slots * 4))) return rc;
-    d.ids = (int32_t*)t->rows_out.p;
-    if (ho.positions) { if ((rc = ensure(t, t->rows_pos, slots * 4))) return rc; d.positions = (int32_t*)t->rows_pos.p; }
-    if (ho.row_lengths) { if ((rc = ensure(t, t->win_len, nr * 4))) return rc; d.row_lengths = (int32_t*)t->win_len.p; }
-    if (ho.row_docs) { if ((rc = ensure(t, t->win_docs, nr * 8))) return rc; d.row_docs = (int64_t*)t->win_docs.p; }
-    if (ho.row_starts) { if ((rc = ensure(t, t->win_starts, nr * 8))) return rc; d.row_starts = (int64_t*)t->win_starts.p; }
+    const int64_t slots = rows * sp->seq_len;
+    RowsOut o[] = {{true, ho.ids, &t->rows_out, 4, slots, slots},
+                   {ho.positions != nullptr, ho.positions, &t->rows_pos, 4, slots, slots},
+                   {ho.row_lengths != nullptr, ho.row_lengths, &t->win_len, 4, rows, rows},
+                   {ho.row_docs != nullptr, ho.row_docs, &t->win_docs, 8, rows, rows},
+                   {ho.row_starts != nullptr, ho.row_starts, &t->win_starts, 8, rows, rows}};
+    if ((rc = rows_out_ensure(t, o, 5))) return rc;
     if ((rc = ensure(t, t->rows_counts, 4 * sizeof(int64_t)))) return rc;
+    const td_window_outputs d{(int32_t*)o[0].p(), (int32_t*)o[1].p(), (int32_t*)o[2].p(), (int64_t*)o[3].p(), (int64_t*)o[4].p()};
     if ((rc = window_launch_locked(t, d_ids, n_ids, d_toff, n_docs, sp, overlap, d, rows, t->rows_counts.p, s))) return rc;
     if ((rc = device_status_locked(t, s, nullptr))) return rc;
     if ((rc = copy_wait(t, counts, t->rows_counts.p, 4 * sizeof(int64_t), hipMemcpyDeviceToHost, s))) return rc;
-    const size_t n_slots = (size_t)(rows * sp->seq_len);
-    if ((rc = copy_wait(t, ho.ids, d.ids, n_slots * 4, hipMemcpyDeviceToHost, s))) return rc;
-    if (ho.positions && (rc = copy_wait(t, ho.positions, d.positions, n_slots * 4, hipMemcpyDeviceToHost, s))) return rc;
-    if (ho.row_lengths && (rc = copy_wait(t, ho.row_lengths, d.row_lengths, (size_t)rows * 4, hipMemcpyDeviceToHost, s))) return rc;
-    if (ho.row_docs && (rc = copy_wait(t, ho.row_docs, d.row_docs, (size_t)rows * 8, hipMemcpyDeviceToHost, s))) return rc;
-    if (ho.row_starts && (rc = copy_wait(t, ho.row_starts, d.row_starts, (size_t)rows * 8, hipMemcpyDeviceToHost, s))) return rc;
-    return TD_OK;
+    return rows_out_copy(t, o, 5, s);
 }
 
 // ---- best-fit packing (td_pack.hip) ------------------------------------------------------------------------------------------
-// The checks of a TD_ROWS_BESTFIT spec that need no handle.  want_cu: cu_seqlens requested.
-const char* pack_spec_error(const td_rows_spec* sp, int64_t rows_capacity, bool want_cu) {
-    if (!sp) return "null td_rows_spec";
-    if (sp->layout != TD_ROWS_BESTFIT) return "layout must be TD_ROWS_BESTFIT";
-    if (sp->seq_len < 1 || sp->seq_len > INT32_MAX) return "seq_len must be in 1 .. 2^31 - 1";
-    if (sp->flags & ~(int64_t)TD_ROWS_TRUNCATE) return "flags must be 0 or TD_ROWS_TRUNCATE";
-    if (sp->pad_id < INT32_MIN || sp->pad_id > INT32_MAX) return "pad_id must be an int32";
-    const int64_t k = (sp->bos_id >= 0) + (sp->eos_id >= 0);
-    if ((sp->flags & TD_ROWS_TRUNCATE) && sp->seq_len < k) return "TD_ROWS_TRUNCATE needs seq_len >= the BOS and EOS slots";
-    if (rows_capacity < 0) return "rows_capacity must be >= 0";
-    if (rows_capacity > ((int64_t)1 << 62) / sp->seq_len) return "rows_capacity * seq_len is too large";
-    if (want_cu && rows_capacity * sp->seq_len >= ((int64_t)1 << 31))
-        return "cu_seqlens entries are int32: rows_capacity * seq_len must stay below 2^31";
-    return nullptr;
-}
-
-const char* pack_args_error(const td_rows_spec* sp, int64_t n_docs, int64_t rows_capacity, const td_pack_outputs* o) {
-    if (!o) return "null td_pack_outputs";
-    if (n_docs > INT32_MAX) return "n_docs must be below 2^31";
-    if (rows_capacity > 0 && !o->ids) return "null ids output";
-    return pack_spec_error(sp, rows_capacity, o->cu_seqlens != nullptr);
-}
-
 // A document's slots after truncation, its full chunks and its remainder (the one item that is not a full row).
 struct PackDoc {
     int64_t n, full, rem;
@@ -1154,18 +1196,8 @@ int pack_prepare(td_tokenizer* t, const void* d_ids, int64_t n_tokens, const voi
                  hipStream_t s, PackArgs& a, PackPlan& plan, int64_t* counts) {
     int rc;
     if ((rc = order_before(t, s))) return rc;
-    memset(&a, 0, sizeof a);
-    a.ids = (const int32_t*)d_ids;
-    a.n_tokens = n_tokens;
-    a.tok_off = (const int64_t*)d_toff;
-    a.n_docs = n_docs;
-    a.S = sp->seq_len;
-    a.b = sp->bos_id >= 0;
-    a.e = sp->eos_id >= 0;
+    rows_fill_args(a, d_ids, n_tokens, d_toff, n_docs, sp);
     a.truncate = (sp->flags & TD_ROWS_TRUNCATE) ? 1 : 0;
-    a.bos = a.b ? (int32_t)sp->bos_id : 0;
-    a.eos = a.e ? (int32_t)sp->eos_id : 0;
-    a.pad = (int32_t)sp->pad_id;
     const size_t nd = (size_t)std::max<int64_t>(n_docs, 1);
     for (DevBuf* b : {&t->pack_key, &t->pack_val, &t->pack_key2, &t->pack_val2})
         if ((rc = ensure(t, *b, nd * 4))) return rc;
@@ -1269,21 +1301,16 @@ int pack_to_host(td_tokenizer* t, const void* d_ids, int64_t n_ids, const void* 
     PackPlan plan;
     if ((rc = pack_prepare(t, d_ids, n_ids, d_toff, n_docs, sp, s, a, plan, counts))) return rc;
     if (plan.rows > cap) return rows_capacity_fail(t, plan.rows, counts);
-    const size_t slots = (size_t)std::max<int64_t>(plan.rows * sp->seq_len, 1), ns = (size_t)plan.segs + 1;
-    td_pack_outputs d{};
-    if ((rc = ensure(t, t->rows_out, slots * 4))) return rc;
-    d.ids = (int32_t*)t->rows_out.p;
-    if (ho.positions) { if ((rc = ensure(t, t->rows_pos, slots * 4))) return rc; d.positions = (int32_t*)t->rows_pos.p; }
-    if (ho.cu_seqlens) { if ((rc = ensure(t, t->rows_aux, ns * 4))) return rc; d.cu_seqlens = (int32_t*)t->rows_aux.p; }
-    if (ho.row_lengths) { if ((rc = ensure(t, t->pack_len, (size_t)std::max<int64_t>(plan.rows, 1) * 4))) return rc; d.row_lengths = (int32_t*)t->pack_len.p; }
-    if (ho.seg_docs) { if ((rc = ensure(t, t->pack_docs, ns * 8))) return rc; d.seg_docs = (int64_t*)t->pack_docs.p; }
+    const int64_t slots = plan.rows * sp->seq_len;
+    const RowsOut o[] = {{true, ho.ids, &t->rows_out, 4, slots, slots},
+                         {ho.positions != nullptr, ho.positions, &t->rows_pos, 4, slots, slots},
+                         {ho.cu_seqlens != nullptr, ho.cu_seqlens, &t->rows_aux, 4, plan.segs + 1, plan.segs + 1},
+                         {ho.row_lengths != nullptr, ho.row_lengths, &t->pack_len, 4, plan.rows, plan.rows},
+                         {ho.seg_docs != nullptr, ho.seg_docs, &t->pack_docs, 8, plan.segs + 1, plan.segs}};
+    if ((rc = rows_out_ensure(t, o, 5))) return rc;
+    const td_pack_outputs d{(int32_t*)o[0].p(), (int32_t*)o[1].p(), (int32_t*)o[2].p(), (int32_t*)o[3].p(), (int64_t*)o[4].p()};
     if ((rc = pack_emit(t, a, plan, d, s))) return rc;
-    const size_t n_slots = (size_t)(plan.rows * sp->seq_len);
-    if ((rc = copy_wait(t, ho.ids, d.ids, n_slots * 4, hipMemcpyDeviceToHost, s))) return rc;
-    if (ho.positions && (rc = copy_wait(t, ho.positions, d.positions, n_slots * 4, hipMemcpyDeviceToHost, s))) return rc;
-    if (ho.cu_seqlens && (rc = copy_wait(t, ho.cu_seqlens, d.cu_seqlens, ns * 4, hipMemcpyDeviceToHost, s))) return rc;
-    if (ho.row_lengths && (rc = copy_wait(t, ho.row_lengths, d.row_lengths, (size_t)plan.rows * 4, hipMemcpyDeviceToHost, s))) return rc;
-    if (ho.seg_docs && (rc = copy_wait(t, ho.seg_docs, d.seg_docs, (size_t)plan.segs * 8, hipMemcpyDeviceToHost, s))) return rc;
+    if ((rc = rows_out_copy(t, o, 5, s))) return rc;
     HIP_TRY(t, hipStreamSynchronize(s));  // (nothing copied at all: the kernels are still done when the call returns)
     return TD_OK;
 }
@@ -2730,10 +2757,8 @@ int td_make_rows_device(td_tokenizer* t, const void* d_ids, int64_t n_tokens, co
     if (!t || !spec || n_tokens < 0 || n_docs < 0 || !d_tok_offsets || (n_tokens > 0 && !d_ids) || !d_counts ||
         (rows_capacity > 0 && !d_out_ids))
         return TD_E_INVALID;
-    if (const char* m = rows_spec_error(spec, rows_capacity, spec->layout == TD_ROWS_CONCAT && d_aux))
-        return fail_unlocked(t, TD_E_INVALID, std::string("td_make_rows_device: ") + m);
-    int rc;
-    if ((rc = rows_check_ids(t, spec))) return rc;
+    if (int rc = rows_spec_fail(t, "td_make_rows_device",
+                                rows_spec_error(FAM_ROWS, spec, 0, rows_capacity, spec->layout == TD_ROWS_CONCAT && d_aux), spec)) return rc;
     return locked(t, [&] {
         return rows_launch_locked(t, d_ids, n_tokens, d_tok_offsets, n_docs, spec, d_out_ids, rows_capacity, d_positions, d_aux, d_counts,
                                   (hipStream_t)hip_stream);
@@ -2744,24 +2769,16 @@ int td_make_rows(td_tokenizer* t, const int32_t* ids, int64_t n_tokens, const in
                  const td_rows_spec* spec, int32_t* out_ids, int64_t rows_capacity, int32_t* out_positions, int32_t* out_aux,
                  int64_t* counts) {
     if (!t || !spec || n_tokens < 0 || n_docs < 0 || !tok_offsets || !counts || (rows_capacity > 0 && !out_ids)) return TD_E_INVALID;
-    if (const char* m = rows_spec_error(spec, rows_capacity, spec->layout == TD_ROWS_CONCAT && out_aux))
-        return fail_unlocked(t, TD_E_INVALID, std::string("td_make_rows: ") + m);
-    int rc;
-    if ((rc = rows_check_ids(t, spec))) return rc;
+    if (int rc = rows_spec_fail(t, "td_make_rows",
+                                rows_spec_error(FAM_ROWS, spec, 0, rows_capacity, spec->layout == TD_ROWS_CONCAT && out_aux), spec)) return rc;
     return locked(t, [&] {
         int rc2;
-        if ((rc2 = check_offsets(t, "tok_offsets", tok_offsets, n_docs, ids))) return rc2;
+        if ((rc2 = rows_check_host_ids(t, ids, n_tokens, tok_offsets, n_docs))) return rc2;
         const int64_t total = tok_offsets[n_docs];
-        if (total > n_tokens) { t->err = "tok_offsets[n_docs] exceeds n_tokens"; return (int)TD_E_INVALID; }
         const int64_t rows = rows_needed(spec, total, n_docs);
         if (rows > rows_capacity) return rows_capacity_fail(t, rows, counts);
-        if ((rc2 = ensure(t, t->dec_tokens, (size_t)std::max<int64_t>(total, 1) * 4))) return rc2;
-        if ((rc2 = ensure(t, t->d_offsets, (size_t)(n_docs + 1) * 8))) return rc2;
-        if ((rc2 = own_streams(t))) return rc2;
-        hipStream_t s = t->s_own;
-        if ((rc2 = order_before(t, s))) return rc2;
-        if (total > 0) HIP_TRY(t, hipMemcpyAsync(t->dec_tokens.p, ids, (size_t)total * 4, hipMemcpyHostToDevice, s));
-        HIP_TRY(t, hipMemcpyAsync(t->d_offsets.p, tok_offsets, (size_t)(n_docs + 1) * 8, hipMemcpyHostToDevice, s));
+        hipStream_t s;
+        if ((rc2 = rows_stage_host_ids(t, ids, tok_offsets, n_docs, s))) return rc2;
         return rows_to_host(t, t->dec_tokens.p, total, t->d_offsets.p, n_docs, spec, rows, out_ids, out_positions, out_aux, counts, s);
     });
 }
@@ -2772,31 +2789,13 @@ int td_encode_batch_rows(td_tokenizer* t, const uint8_t* text, const int64_t* do
     if (!t || !spec || !doc_offsets || n_docs < 0 || !counts || (rows_capacity > 0 && !out_ids) ||
         (mode != TD_MODE_ENCODE && mode != TD_MODE_ORDINARY))
         return TD_E_INVALID;
-    if (const char* m = rows_spec_error(spec, rows_capacity, spec->layout == TD_ROWS_CONCAT && out_aux))
-        return fail_unlocked(t, TD_E_INVALID, std::string("td_encode_batch_rows: ") + m);
-    int rc;
-    if ((rc = rows_check_ids(t, spec))) return rc;
+    if (int rc = rows_spec_fail(t, "td_encode_batch_rows",
+                                rows_spec_error(FAM_ROWS, spec, 0, rows_capacity, spec->layout == TD_ROWS_CONCAT && out_aux), spec)) return rc;
     return locked(t, [&] {
         int rc2;
-        if ((rc2 = check_offsets(t, "doc_offsets", doc_offsets, n_docs, text))) return rc2;
-        const int64_t n = doc_offsets[n_docs];
-        const int64_t dev_cap = std::max<int64_t>(n, 1);  // (at most one id per byte)
-        if ((rc2 = ensure(t, t->h2d_text, (size_t)n + 64))) return rc2;
-        if ((rc2 = ensure(t, t->h2d_offs, (size_t)(n_docs + 1) * 8))) return rc2;
-        if ((rc2 = ensure(t, t->d_offsets, (size_t)(n_docs + 1) * 8))) return rc2;
-        if ((rc2 = ensure(t, t->d_tokens, (size_t)dev_cap * 4))) return rc2;
-        if ((rc2 = own_streams(t))) return rc2;
-        hipStream_t s = t->s_own;
-        if ((rc2 = order_before(t, s))) return rc2;
-        if (n > 0) {
-            HIP_TRY(t, hipMemcpyAsync(t->h2d_text.p, text, (size_t)n, hipMemcpyHostToDevice, s));
-            HIP_TRY(t, hipMemcpyAsync(t->h2d_offs.p, doc_offsets, (size_t)(n_docs + 1) * 8, hipMemcpyHostToDevice, s));
-            if ((rc2 = encode_device_locked(t, t->h2d_text.p, n, t->h2d_offs.p, n_docs, mode, t->d_tokens.p, dev_cap, t->d_offsets.p, s)))
-                return rc2;
-        } else {  // (nothing but empty documents: no encode)
-            HIP_TRY(t, hipMemsetAsync(t->d_offsets.p, 0, (size_t)(n_docs + 1) * 8, s));
-        }
-        if ((rc2 = device_status_locked(t, s, nullptr))) return rc2;  // (the encode's errors as such, before the rows read its ids)
+        int64_t dev_cap;
+        hipStream_t s;
+        if ((rc2 = rows_encode_locked(t, text, doc_offsets, n_docs, mode, dev_cap, s))) return rc2;
         int64_t total = 0;
         if ((rc2 = copy_wait(t, &total, (const int64_t*)t->d_offsets.p + n_docs, 8, hipMemcpyDeviceToHost, s))) return rc2;
         const int64_t rows = rows_needed(spec, total, n_docs);
@@ -2807,7 +2806,7 @@ int td_encode_batch_rows(td_tokenizer* t, const uint8_t* text, const int64_t* do
 
 int td_pack_plan(const int64_t* tok_offsets, int64_t n_docs, const td_rows_spec* spec, int64_t* counts, int64_t* doc_row,
                  int64_t* doc_slot) {
-    if (!tok_offsets || n_docs < 0 || n_docs > INT32_MAX || !counts || pack_spec_error(spec, 0, false)) return TD_E_INVALID;
+    if (!tok_offsets || n_docs < 0 || n_docs > INT32_MAX || !counts || rows_spec_error(FAM_BESTFIT, spec, 0, 0, false)) return TD_E_INVALID;
     if (tok_offsets[0] != 0) return TD_E_INVALID;
     for (int64_t d = 0; d < n_docs; ++d)
         if (tok_offsets[d + 1] < tok_offsets[d]) return TD_E_INVALID;
@@ -2849,22 +2848,13 @@ int td_pack_plan(const int64_t* tok_offsets, int64_t n_docs, const td_rows_spec*
 int td_pack_rows(td_tokenizer* t, const int32_t* ids, int64_t n_tokens, const int64_t* tok_offsets, int64_t n_docs,
                  const td_rows_spec* spec, const td_pack_outputs* host_out, int64_t rows_capacity, int64_t* counts) {
     if (!t || !spec || !host_out || n_tokens < 0 || n_docs < 0 || !tok_offsets || !counts) return TD_E_INVALID;
-    if (const char* m = pack_args_error(spec, n_docs, rows_capacity, host_out))
-        return fail_unlocked(t, TD_E_INVALID, std::string("td_pack_rows: ") + m);
-    int rc;
-    if ((rc = rows_check_ids(t, spec))) return rc;
+    if (int rc = rows_spec_fail(t, "td_pack_rows", rows_args_error(spec, 0, n_docs, rows_capacity, host_out), spec)) return rc;
     return locked(t, [&] {
         int rc2;
-        if ((rc2 = check_offsets(t, "tok_offsets", tok_offsets, n_docs, ids))) return rc2;
+        if ((rc2 = rows_check_host_ids(t, ids, n_tokens, tok_offsets, n_docs))) return rc2;
         const int64_t total = tok_offsets[n_docs];
-        if (total > n_tokens) { t->err = "tok_offsets[n_docs] exceeds n_tokens"; return (int)TD_E_INVALID; }
-        if ((rc2 = ensure(t, t->dec_tokens, (size_t)std::max<int64_t>(total, 1) * 4))) return rc2;
-        if ((rc2 = ensure(t, t->d_offsets, (size_t)(n_docs + 1) * 8))) return rc2;
-        if ((rc2 = own_streams(t))) return rc2;
-        hipStream_t s = t->s_own;
-        if ((rc2 = order_before(t, s))) return rc2;
-        if (total > 0) HIP_TRY(t, hipMemcpyAsync(t->dec_tokens.p, ids, (size_t)total * 4, hipMemcpyHostToDevice, s));
-        HIP_TRY(t, hipMemcpyAsync(t->d_offsets.p, tok_offsets, (size_t)(n_docs + 1) * 8, hipMemcpyHostToDevice, s));
+        hipStream_t s;
+        if ((rc2 = rows_stage_host_ids(t, ids, tok_offsets, n_docs, s))) return rc2;
         return pack_to_host(t, t->dec_tokens.p, total, t->d_offsets.p, n_docs, spec, *host_out, rows_capacity, counts, s);
     });
 }
@@ -2874,10 +2864,7 @@ int td_pack_rows_device(td_tokenizer* t, const void* d_ids, int64_t n_tokens, co
                         void* hip_stream) {
     if (!t || !spec || !dev_out || n_tokens < 0 || n_docs < 0 || !d_tok_offsets || (n_tokens > 0 && !d_ids) || !counts)
         return TD_E_INVALID;
-    if (const char* m = pack_args_error(spec, n_docs, rows_capacity, dev_out))
-        return fail_unlocked(t, TD_E_INVALID, std::string("td_pack_rows_device: ") + m);
-    int rc;
-    if ((rc = rows_check_ids(t, spec))) return rc;
+    if (int rc = rows_spec_fail(t, "td_pack_rows_device", rows_args_error(spec, 0, n_docs, rows_capacity, dev_out), spec)) return rc;
     return locked(t, [&] {
         hipStream_t s = (hipStream_t)hip_stream;
         PackArgs a;
@@ -2893,38 +2880,19 @@ int td_encode_batch_pack_rows(td_tokenizer* t, const uint8_t* text, const int64_
                               const td_rows_spec* spec, const td_pack_outputs* host_out, int64_t rows_capacity, int64_t* counts) {
     if (!t || !spec || !host_out || !doc_offsets || n_docs < 0 || !counts || (mode != TD_MODE_ENCODE && mode != TD_MODE_ORDINARY))
         return TD_E_INVALID;
-    if (const char* m = pack_args_error(spec, n_docs, rows_capacity, host_out))
-        return fail_unlocked(t, TD_E_INVALID, std::string("td_encode_batch_pack_rows: ") + m);
-    int rc;
-    if ((rc = rows_check_ids(t, spec))) return rc;
+    if (int rc = rows_spec_fail(t, "td_encode_batch_pack_rows", rows_args_error(spec, 0, n_docs, rows_capacity, host_out), spec)) return rc;
     return locked(t, [&] {
         int rc2;
-        if ((rc2 = check_offsets(t, "doc_offsets", doc_offsets, n_docs, text))) return rc2;
-        const int64_t n = doc_offsets[n_docs];
-        const int64_t dev_cap = std::max<int64_t>(n, 1);  // (at most one id per byte)
-        if ((rc2 = ensure(t, t->h2d_text, (size_t)n + 64))) return rc2;
-        if ((rc2 = ensure(t, t->h2d_offs, (size_t)(n_docs + 1) * 8))) return rc2;
-        if ((rc2 = ensure(t, t->d_offsets, (size_t)(n_docs + 1) * 8))) return rc2;
-        if ((rc2 = ensure(t, t->d_tokens, (size_t)dev_cap * 4))) return rc2;
-        if ((rc2 = own_streams(t))) return rc2;
-        hipStream_t s = t->s_own;
-        if ((rc2 = order_before(t, s))) return rc2;
-        if (n > 0) {
-            HIP_TRY(t, hipMemcpyAsync(t->h2d_text.p, text, (size_t)n, hipMemcpyHostToDevice, s));
-            HIP_TRY(t, hipMemcpyAsync(t->h2d_offs.p, doc_offsets, (size_t)(n_docs + 1) * 8, hipMemcpyHostToDevice, s));
-            if ((rc2 = encode_device_locked(t, t->h2d_text.p, n, t->h2d_offs.p, n_docs, mode, t->d_tokens.p, dev_cap, t->d_offsets.p, s)))
-                return rc2;
-        } else {  // (nothing but empty documents: no encode)
-            HIP_TRY(t, hipMemsetAsync(t->d_offsets.p, 0, (size_t)(n_docs + 1) * 8, s));
-        }
-        if ((rc2 = device_status_locked(t, s, nullptr))) return rc2;  // (the encode's errors as such, before the packing reads its ids)
+        int64_t dev_cap;
+        hipStream_t s;
+        if ((rc2 = rows_encode_locked(t, text, doc_offsets, n_docs, mode, dev_cap, s))) return rc2;
         return pack_to_host(t, t->d_tokens.p, dev_cap, t->d_offsets.p, n_docs, spec, *host_out, rows_capacity, counts, s);
     });
 }
 
 int td_window_plan(const int64_t* tok_offsets, int64_t n_docs, const td_rows_spec* spec, int64_t overlap, int64_t* counts,
                    int64_t* first_row) {
-    if (!tok_offsets || n_docs < 0 || n_docs > INT32_MAX || !counts || window_spec_error(spec, overlap, 0)) return TD_E_INVALID;
+    if (!tok_offsets || n_docs < 0 || n_docs > INT32_MAX || !counts || rows_spec_error(FAM_WINDOWS, spec, overlap, 0, false)) return TD_E_INVALID;
     if (tok_offsets[0] != 0) return TD_E_INVALID;
     const int64_t k = (spec->bos_id >= 0) + (spec->eos_id >= 0), C = spec->seq_len - k;
     int64_t rows = 0, R = 0, multi = 0, mx = 0;
@@ -2951,10 +2919,7 @@ int td_window_rows_device(td_tokenizer* t, const void* d_ids, int64_t n_tokens, 
                           void* d_counts, void* hip_stream) {
     if (!t || !spec || !dev_out || n_tokens < 0 || n_docs < 0 || !d_tok_offsets || (n_tokens > 0 && !d_ids) || !d_counts)
         return TD_E_INVALID;
-    if (const char* m = window_args_error(spec, overlap, n_docs, rows_capacity, dev_out))
-        return fail_unlocked(t, TD_E_INVALID, std::string("td_window_rows_device: ") + m);
-    int rc;
-    if ((rc = rows_check_ids(t, spec))) return rc;
+    if (int rc = rows_spec_fail(t, "td_window_rows_device", rows_args_error(spec, overlap, n_docs, rows_capacity, dev_out), spec)) return rc;
     return locked(t, [&] {
         return window_launch_locked(t, d_ids, n_tokens, d_tok_offsets, n_docs, spec, overlap, *dev_out, rows_capacity, d_counts,
                                     (hipStream_t)hip_stream);
@@ -2964,25 +2929,16 @@ int td_window_rows_device(td_tokenizer* t, const void* d_ids, int64_t n_tokens, 
 int td_window_rows(td_tokenizer* t, const int32_t* ids, int64_t n_tokens, const int64_t* tok_offsets, int64_t n_docs,
                    const td_rows_spec* spec, int64_t overlap, const td_window_outputs* host_out, int64_t rows_capacity, int64_t* counts) {
     if (!t || !spec || !host_out || n_tokens < 0 || n_docs < 0 || !tok_offsets || !counts) return TD_E_INVALID;
-    if (const char* m = window_args_error(spec, overlap, n_docs, rows_capacity, host_out))
-        return fail_unlocked(t, TD_E_INVALID, std::string("td_window_rows: ") + m);
-    int rc;
-    if ((rc = rows_check_ids(t, spec))) return rc;
+    if (int rc = rows_spec_fail(t, "td_window_rows", rows_args_error(spec, overlap, n_docs, rows_capacity, host_out), spec)) return rc;
     return locked(t, [&] {
         int rc2;
-        if ((rc2 = check_offsets(t, "tok_offsets", tok_offsets, n_docs, ids))) return rc2;
+        if ((rc2 = rows_check_host_ids(t, ids, n_tokens, tok_offsets, n_docs))) return rc2;
         const int64_t total = tok_offsets[n_docs];
-        if (total > n_tokens) { t->err = "tok_offsets[n_docs] exceeds n_tokens"; return (int)TD_E_INVALID; }
         int64_t plan[4];
         if (td_window_plan(tok_offsets, n_docs, spec, overlap, plan, nullptr) != TD_OK) { t->err = "invalid tok_offsets"; return (int)TD_E_INVALID; }
         if (plan[0] > rows_capacity) return rows_capacity_fail(t, plan[0], counts);
-        if ((rc2 = ensure(t, t->dec_tokens, (size_t)std::max<int64_t>(total, 1) * 4))) return rc2;
-        if ((rc2 = ensure(t, t->d_offsets, (size_t)(n_docs + 1) * 8))) return rc2;
-        if ((rc2 = own_streams(t))) return rc2;
-        hipStream_t s = t->s_own;
-        if ((rc2 = order_before(t, s))) return rc2;
-        if (total > 0) HIP_TRY(t, hipMemcpyAsync(t->dec_tokens.p, ids, (size_t)total * 4, hipMemcpyHostToDevice, s));
-        HIP_TRY(t, hipMemcpyAsync(t->d_offsets.p, tok_offsets, (size_t)(n_docs + 1) * 8, hipMemcpyHostToDevice, s));
+        hipStream_t s;
+        if ((rc2 = rows_stage_host_ids(t, ids, tok_offsets, n_docs, s))) return rc2;
         return window_to_host(t, t->dec_tokens.p, total, t->d_offsets.p, n_docs, spec, overlap, *host_out, plan[0], counts, s);
     });
 }
@@ -2992,31 +2948,12 @@ int td_encode_batch_window_rows(td_tokenizer* t, const uint8_t* text, const int6
                                 int64_t* counts) {
     if (!t || !spec || !host_out || !doc_offsets || n_docs < 0 || !counts || (mode != TD_MODE_ENCODE && mode != TD_MODE_ORDINARY))
         return TD_E_INVALID;
-    if (const char* m = window_args_error(spec, overlap, n_docs, rows_capacity, host_out))
-        return fail_unlocked(t, TD_E_INVALID, std::string("td_encode_batch_window_rows: ") + m);
-    int rc;
-    if ((rc = rows_check_ids(t, spec))) return rc;
+    if (int rc = rows_spec_fail(t, "td_encode_batch_window_rows", rows_args_error(spec, overlap, n_docs, rows_capacity, host_out), spec)) return rc;
     return locked(t, [&] {
         int rc2;
-        if ((rc2 = check_offsets(t, "doc_offsets", doc_offsets, n_docs, text))) return rc2;
-        const int64_t n = doc_offsets[n_docs];
-        const int64_t dev_cap = std::max<int64_t>(n, 1);  // (at most one id per byte)
-        if ((rc2 = ensure(t, t->h2d_text, (size_t)n + 64))) return rc2;
-        if ((rc2 = ensure(t, t->h2d_offs, (size_t)(n_docs + 1) * 8))) return rc2;
-        if ((rc2 = ensure(t, t->d_offsets, (size_t)(n_docs + 1) * 8))) return rc2;
-        if ((rc2 = ensure(t, t->d_tokens, (size_t)dev_cap * 4))) return rc2;
-        if ((rc2 = own_streams(t))) return rc2;
-        hipStream_t s = t->s_own;
-        if ((rc2 = order_before(t, s))) return rc2;
-        if (n > 0) {
-            HIP_TRY(t, hipMemcpyAsync(t->h2d_text.p, text, (size_t)n, hipMemcpyHostToDevice, s));
-            HIP_TRY(t, hipMemcpyAsync(t->h2d_offs.p, doc_offsets, (size_t)(n_docs + 1) * 8, hipMemcpyHostToDevice, s));
-            if ((rc2 = encode_device_locked(t, t->h2d_text.p, n, t->h2d_offs.p, n_docs, mode, t->d_tokens.p, dev_cap, t->d_offsets.p, s)))
-                return rc2;
-        } else {  // (nothing but empty documents: no encode)
-            HIP_TRY(t, hipMemsetAsync(t->d_offsets.p, 0, (size_t)(n_docs + 1) * 8, s));
-        }
-        if ((rc2 = device_status_locked(t, s, nullptr))) return rc2;  // (the encode's errors as such, before the windows read its ids)
+        int64_t dev_cap;
+        hipStream_t s;
+        if ((rc2 = rows_encode_locked(t, text, doc_offsets, n_docs, mode, dev_cap, s))) return rc2;
         // the rows are known from the token offsets: they come back (8 bytes a document) and are planned on the host
         std::vector<int64_t> toff((size_t)n_docs + 1);
         if ((rc2 = copy_wait(t, toff.data(), t->d_offsets.p, (size_t)(n_docs + 1) * 8, hipMemcpyDeviceToHost, s))) return rc2;

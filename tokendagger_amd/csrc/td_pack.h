@@ -1,6 +1,7 @@
 // Whole documents packed into rows by best-fit decreasing (td_pack.hip): the contract is in include/tokendagger_hip.h
 // (TD_ROWS_BESTFIT, td_pack_rows).  The placement is sequential by nature, so it is planned on the host over RUNS of equal-length
-// items (pack_plan_runs); every per-document and per-slot step runs on the device.
+// items (pack_plan_runs); every per-document and per-slot step runs on the device.  The workgroup size, the tile and the grid cap,
+// and the device helpers shared with the other layouts, are in td_rows_common.h.
 #pragma once
 #include <hip/hip_runtime_api.h>
 #include <stdint.h>
@@ -9,9 +10,6 @@
 
 namespace td {
 
-constexpr int PACK_THREADS = 256;
-constexpr int PACK_TILE = 4096;       // output slots a workgroup writes per tile (four int4 stores a lane)
-constexpr int PACK_MAX_GRID = 2048;   // the slot kernel strides over tiles with at most this many workgroups
 constexpr int PACK_HDR = 8;           // int64 words of the header the host reads back (PackHdr)
 constexpr int64_t PACK_RUNS_FIRST = 8192;  // runs read back with the header; more (S > 8192) take a second copy
 

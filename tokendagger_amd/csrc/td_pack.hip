@@ -25,8 +25,8 @@
 #include <map>
 #include <queue>
 
-#include "td_common.h"
 #include "td_pack.h"
+#include "td_rows_common.h"
 
 namespace td {
 
@@ -83,25 +83,7 @@ void pack_plan_runs(int64_t S, int64_t full, int64_t real, const int64_t* lens, 
 
 namespace {
 
-__device__ __forceinline__ long long pack_block_sum(long long v, long long* s_red) {
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
-    if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    long long r = 0;
-    for (int w = 0; w < PACK_THREADS / 64; ++w) r += s_red[w];
-    __syncthreads();
-    return r;
-}
-
-__device__ __forceinline__ long long pack_block_max(long long v, long long* s_red) {
-    for (int d = 32; d >= 1; d >>= 1) v = max(v, (long long)__shfl_xor(v, d));
-    if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    long long r = 0;
-    for (int w = 0; w < PACK_THREADS / 64; ++w) r = max(r, s_red[w]);
-    __syncthreads();
-    return r;
-}
+constexpr int PACK_THREADS = RC_THREADS, PACK_TILE = RC_TILE, PACK_MAX_GRID = RC_MAX_GRID;
 
 // body ids of document d after truncation
 __device__ __forceinline__ int64_t pack_body(const PackArgs& a, int64_t L) {
@@ -136,11 +118,11 @@ __global__ __launch_bounds__(PACK_THREADS) void td_pack_items(const PackArgs a) 
         a.val[d] = (uint32_t)d;
         a.full[d] = fl;
     }
-    F = pack_block_sum(F, s_red);
-    R = pack_block_sum(R, s_red);
-    cut = pack_block_sum(cut, s_red);
-    items = pack_block_sum(items, s_red);
-    bad = pack_block_max(bad, s_red);
+    F = block_sum(F, s_red);
+    R = block_sum(R, s_red);
+    cut = block_sum(cut, s_red);
+    items = block_sum(items, s_red);
+    bad = block_max(bad, s_red);
     if (threadIdx.x == 0) {
         unsigned long long* h = (unsigned long long*)a.hdr;
         if (F) atomicAdd(h + PH_FULL, (unsigned long long)F);
@@ -204,16 +186,6 @@ __global__ __launch_bounds__(PACK_THREADS) void td_pack_segments(const PackArgs 
         }
         x -= a.n_mixed;
         if (a.lengths) a.lengths[x] = (int32_t)(x < F ? S : a.fill[x - F]);
-    }
-}
-
-// slots [j0, j0 + 4) below `end`; int4 when aligned (j0 is a multiple of 4)
-__device__ __forceinline__ void pack_put4(int32_t* p, int64_t j0, int64_t end, const int32_t v[4]) {
-    if (j0 + 4 <= end && (((uintptr_t)p) & 15) == 0) {
-        *reinterpret_cast<int4*>(p + j0) = make_int4(v[0], v[1], v[2], v[3]);
-    } else {
-        for (int q = 0; q < 4; ++q)
-            if (j0 + q < end) p[j0 + q] = v[q];
     }
 }
 
@@ -282,8 +254,8 @@ __global__ __launch_bounds__(PACK_THREADS) void td_pack_slots(const PackArgs a) 
                     v[q] = src >= 0 && src < a.n_tokens ? a.ids[src] : a.pad;  // (always inside: the items kernel checked the offsets)
                 }
             }
-            pack_put4(a.out, j0, t1, v);
-            if (a.pos) pack_put4(a.pos, j0, t1, ps);
+            rows_put4(a.out, j0, t1, v);
+            if (a.pos) rows_put4(a.pos, j0, t1, ps);
         }
     }
 }

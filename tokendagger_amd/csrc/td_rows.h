@@ -1,16 +1,14 @@
 // Training rows from encoded documents (td_rows.hip): ids + per-document token offsets -> fixed-length rows of S slots, with
 // BOS / EOS framing and padding, position ids and cu_seqlens (CONCAT) or lengths (PAD).  The contract is in
-// include/tokendagger_hip.h (td_make_rows).  Kept apart from EncodeArgs / Tables: nothing of the encode is touched.
+// include/tokendagger_hip.h (td_make_rows).  Kept apart from EncodeArgs / Tables: nothing of the encode is touched.  The workgroup
+// size, the tile and the grid cap, and the device helpers shared with the other layouts, are in td_rows_common.h.
 #pragma once
 #include <hip/hip_runtime_api.h>
 #include <stdint.h>
 
 namespace td {
 
-constexpr int ROWS_THREADS = 256;
-constexpr int ROWS_TILE = 4096;       // output slots a workgroup writes per tile (four int4 stores a lane)
 constexpr int ROWS_LDS_DOCS = 4352;   // relative document bases a CONCAT tile keeps in LDS (more: the tile searches global memory)
-constexpr int ROWS_MAX_GRID = 2048;   // slot kernels stride over tiles with at most this many workgroups
 constexpr int ROWS_SCAN_DOCS = 1024;  // documents per workgroup of the cu_seqlens scan (four a lane)
 
 struct RowsArgs {
@@ -21,7 +19,7 @@ struct RowsArgs {
     int layout;               // TD_ROWS_CONCAT / TD_ROWS_PAD
     int drop_last;            // CONCAT: the partial last row is dropped
     int64_t S;                // seq_len
-    unsigned long long s_magic; // floor((2^64 - 1) / S): x / S without a 64-bit division (div_s)
+    unsigned long long s_magic; // floor((2^64 - 1) / S): x / S without a 64-bit division (div_magic)
     int32_t bos, eos, pad;
     int b, e;                 // bos / eos present
     int funnel_src;           // 1: misaligned sources read as two aligned int4 and a funnel instead of four dwords (A/B)

@@ -17,8 +17,8 @@
 //   td_rows_cu                     cu_seqlens
 #include <hip/hip_runtime.h>
 
-#include "td_common.h"
 #include "td_rows.h"
+#include "td_rows_common.h"
 
 namespace td {
 
@@ -26,10 +26,7 @@ namespace {
 
 constexpr unsigned long long RS_AGG = 1ull << 62, RS_PRE = 2ull << 62, RS_VAL = (1ull << 62) - 1;
 constexpr int ROWS_SPIN = 1 << 14;  // polls of a predecessor's status before the waiting wave sums that chunk itself
-
-__device__ __forceinline__ void rows_raise(const RowsArgs& a, int code, int64_t pos) {
-    if (atomicCAS(a.err, 0, code) == 0) *a.err_pos = pos;
-}
+constexpr int ROWS_THREADS = RC_THREADS, ROWS_TILE = RC_TILE, ROWS_MAX_GRID = RC_MAX_GRID;
 
 struct Plan {
     int64_t rows, total, R;  // rows, slots written (rows * S), real slots (CONCAT)
@@ -64,15 +61,6 @@ __device__ Plan rows_plan(const RowsArgs& a, bool report) {
     return p;
 }
 
-// x / S by the multiplier the host computed (s_magic = floor((2^64 - 1) / S): the estimate is low by at most one)
-__device__ __forceinline__ int64_t div_s(const RowsArgs& a, int64_t x) {
-    const unsigned long long S = (unsigned long long)a.S;
-    unsigned long long q = __umul64hi((unsigned long long)x, a.s_magic);
-    unsigned long long r = (unsigned long long)x - q * S;
-    for (int f = 0; f < 2 && r >= S; ++f) { ++q; r -= S; }
-    return (int64_t)q;
-}
-
 __device__ __forceinline__ int64_t doc_base(const RowsArgs& a, int64_t d, int64_t k) { return a.tok_off[d] + d * k; }
 
 // ids[src .. src + 3], 0 <= src and src + 4 <= n_tokens
@@ -91,32 +79,6 @@ __device__ __forceinline__ int4 rows_load4(const RowsArgs& a, int64_t src) {
         }
     }
     return make_int4(p[src], p[src + 1], p[src + 2], p[src + 3]);
-}
-
-__device__ __forceinline__ int32_t rows_load1(const RowsArgs& a, int64_t src) {
-    if (src >= 0 && src < a.n_tokens) return a.ids[src];
-    rows_raise(a, TD_E_INVALID, src);  // (offsets that are not non-decreasing: nothing outside the buffer is read)
-    return a.pad;
-}
-
-// slots [j0, j0 + 4) below `end`; int4 when aligned (j0 is a multiple of 4)
-__device__ __forceinline__ void rows_put4(int32_t* p, int64_t j0, int64_t end, const int32_t v[4]) {
-    if (j0 + 4 <= end && (((uintptr_t)p) & 15) == 0) {
-        *reinterpret_cast<int4*>(p + j0) = make_int4(v[0], v[1], v[2], v[3]);
-    } else {
-        for (int q = 0; q < 4; ++q)
-            if (j0 + q < end) p[j0 + q] = v[q];
-    }
-}
-
-__device__ __forceinline__ long long block_sum(long long v, long long* s_red) {
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
-    if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    long long r = 0;
-    for (int w = 0; w < ROWS_THREADS / 64; ++w) r += s_red[w];
-    __syncthreads();
-    return r;
 }
 
 // last d in [lo, n_docs) with base_d <= j (base_lo <= j)
@@ -175,12 +137,12 @@ __global__ __launch_bounds__(ROWS_THREADS) void td_rows_concat(const RowsArgs a)
             // segments: the row starts in [s0, r1), and the starts of non-empty documents there that are not row starts
             {  // (lane 0 counts the row starts; in vector registers, the scalar ones are taken by the tile's bounds)
                 const int64_t x0 = tid == 0 ? s0 + S - 1 : 0, x1 = tid == 0 ? r1 + S - 1 : 0;
-                segs += div_s(a, x1) - div_s(a, x0);
+                segs += div_magic(x1, a.S, a.s_magic) - div_magic(x0, a.S, a.s_magic);
             }
             if (!over) {
                 for (int i = tid; i < nl; i += ROWS_THREADS) {
                     const int32_t r = s_lb[i];
-                    if (r >= 0 && s_lb[i + 1] > r && s0 + r != div_s(a, s0 + r) * S) ++segs;
+                    if (r >= 0 && s_lb[i + 1] > r && s0 + r != div_magic(s0 + r, a.S, a.s_magic) * S) ++segs;
                 }
             } else {
                 for (int64_t c0 = 0;; c0 += ROWS_THREADS) {
@@ -189,7 +151,7 @@ __global__ __launch_bounds__(ROWS_THREADS) void td_rows_concat(const RowsArgs a)
                     if (d < a.n_docs) {
                         const int64_t bs = doc_base(a, d, k);
                         in = bs < r1;
-                        if (in && bs >= s0 && doc_base(a, d + 1, k) > bs && bs != div_s(a, bs) * S) ++segs;
+                        if (in && bs >= s0 && doc_base(a, d + 1, k) > bs && bs != div_magic(bs, a.S, a.s_magic) * S) ++segs;
                     }
                     if (__syncthreads_count(in) < ROWS_THREADS) break;
                 }
@@ -233,7 +195,7 @@ __global__ __launch_bounds__(ROWS_THREADS) void td_rows_concat(const RowsArgs a)
                     fast = true;
                 }
             }
-            int64_t rs = div_s(a, j0) * S;  // row start
+            int64_t rs = div_magic(j0, a.S, a.s_magic) * S;  // row start
             for (int q = 0; q < 4; ++q) {
                 const int64_t j = j0 + q;
                 while (j >= rs + S) rs += S;
@@ -278,7 +240,7 @@ __global__ __launch_bounds__(ROWS_THREADS) void td_rows_pad(const RowsArgs a) {
         for (int it = 0; it < ROWS_TILE / (4 * ROWS_THREADS); ++it) {
             const int64_t j0 = s0 + (int64_t)it * 4 * ROWS_THREADS + 4 * tid;
             if (j0 >= s1) break;
-            int64_t d = div_s(a, j0), o = j0 - d * S, lo = 0, L = 0, body = 0, len = 0;
+            int64_t d = div_magic(j0, a.S, a.s_magic), o = j0 - d * S, lo = 0, L = 0, body = 0, len = 0;
             auto load_doc = [&] {
                 lo = a.tok_off[d];
                 L = a.tok_off[d + 1] - lo;
@@ -334,7 +296,7 @@ __device__ __forceinline__ long long doc_cuts(const RowsArgs& a, int64_t d, int6
     const int64_t n = a.tok_off[d + 1] - a.tok_off[d] + k;
     if (n <= 0 || base >= R) return 0;
     const int64_t end = base + n < R ? base + n : R;
-    return 1 + div_s(a, end - 1) - div_s(a, base);
+    return 1 + div_magic(end - 1, a.S, a.s_magic) - div_magic(base, a.S, a.s_magic);
 }
 
 __device__ __forceinline__ unsigned long long wave_u64(unsigned long long w) {  // (the same word in every lane: wave-uniform branches)
@@ -429,7 +391,7 @@ __global__ __launch_bounds__(ROWS_THREADS) void td_rows_cu(const RowsArgs a) {
             else hi = mid;
         }
         const long long m = q - s_w[lo], base = s_base[lo];
-        const long long val = m == 0 ? base : (div_s(a, base) + m) * a.S;
+        const long long val = m == 0 ? base : (div_magic(base, a.S, a.s_magic) + m) * a.S;
         if (ex + q < a.aux_cap) a.aux[ex + q] = (int32_t)val;
         else rows_raise(a, TD_E_INVALID, ex + q);
     }

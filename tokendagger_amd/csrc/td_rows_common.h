@@ -1,0 +1,71 @@
+// Device helpers and launch constants the row layouts share (td_rows.hip, td_pack.hip, td_windows.hip): each of the three
+// finds a slot's document in its own way, and all of them store, sum, divide and raise errors the same way.  Device code only:
+// the host library sees td_rows.h, td_pack.h and td_windows.h.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "td_common.h"
+
+namespace td {
+
+constexpr int RC_THREADS = 256;    // lanes of a workgroup, in every kernel of the three files
+constexpr int RC_TILE = 4096;      // output slots a workgroup writes per tile (four int4 stores a lane)
+constexpr int RC_MAX_GRID = 2048;  // slot kernels stride over tiles with at most this many workgroups
+
+// The first error of a call wins.  A: RowsArgs or WindowArgs (err, err_pos in the handle's control block).
+template <class A>
+__device__ __forceinline__ void rows_raise(const A& a, int code, int64_t pos) {
+    if (atomicCAS(a.err, 0, code) == 0) *a.err_pos = pos;
+}
+
+// ids[src] with 0 <= src < n_tokens checked: offsets that are not non-decreasing (CONCAT, PAD) raise here, and nothing outside
+// the buffer is read; td_win_slots runs on checked offsets only, there this is a second fence, not a path.
+template <class A>
+__device__ __forceinline__ int32_t rows_load1(const A& a, int64_t src) {
+    if (src >= 0 && src < a.n_tokens) return a.ids[src];
+    rows_raise(a, TD_E_INVALID, src);
+    return a.pad;
+}
+
+// slots [j0, j0 + 4) below `end`; int4 when aligned (j0 is a multiple of 4)
+__device__ __forceinline__ void rows_put4(int32_t* p, int64_t j0, int64_t end, const int32_t v[4]) {
+    if (j0 + 4 <= end && (((uintptr_t)p) & 15) == 0) {
+        *reinterpret_cast<int4*>(p + j0) = make_int4(v[0], v[1], v[2], v[3]);
+    } else {
+        for (int q = 0; q < 4; ++q)
+            if (j0 + q < end) p[j0 + q] = v[q];
+    }
+}
+
+// x / d for 0 <= x < 2^63 by the multiplier the host computed, magic = floor((2^64 - 1) / d): the estimate is low by at most one
+__device__ __forceinline__ int64_t div_magic(int64_t x, int64_t d, unsigned long long magic) {
+    const unsigned long long D = (unsigned long long)d;
+    unsigned long long q = __umul64hi((unsigned long long)x, magic);
+    unsigned long long r = (unsigned long long)x - q * D;
+    for (int f = 0; f < 2 && r >= D; ++f) { ++q; r -= D; }
+    return (int64_t)q;
+}
+
+// The sum (the maximum, of values >= 0) over the workgroup's RC_THREADS lanes, in every lane; s_red: RC_THREADS / 64 words of LDS.
+__device__ __forceinline__ long long block_sum(long long v, long long* s_red) {
+    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
+    if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    long long r = 0;
+    for (int w = 0; w < RC_THREADS / 64; ++w) r += s_red[w];
+    __syncthreads();
+    return r;
+}
+
+__device__ __forceinline__ long long block_max(long long v, long long* s_red) {
+    for (int d = 32; d >= 1; d >>= 1) v = max(v, (long long)__shfl_xor(v, d));
+    if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    long long r = 0;
+    for (int w = 0; w < RC_THREADS / 64; ++w) r = max(r, s_red[w]);
+    __syncthreads();
+    return r;
+}
+
+}  // namespace td

@@ -1,17 +1,15 @@
 // Overlapping window rows (td_windows.hip): one document per row, a document longer than the row's body room continues in
 // further rows of its own, each repeating the last `overlap` ids of the row before.  The contract is in
 // include/tokendagger_hip.h (TD_ROWS_WINDOWS).  Kept apart from EncodeArgs / Tables and from RowsArgs: nothing of the encode
-// or of the other layouts is touched.
+// or of the other layouts is touched.  The workgroup size, the tile and the grid cap, and the device helpers shared with the
+// other layouts, are in td_rows_common.h.
 #pragma once
 #include <hip/hip_runtime_api.h>
 #include <stdint.h>
 
 namespace td {
 
-constexpr int WIN_THREADS = 256;
-constexpr int WIN_TILE = 4096;        // output slots a workgroup writes per tile (four int4 stores a lane)
 constexpr int WIN_LDS_DOCS = 4352;    // first rows of a tile's documents kept in LDS (a tile has at most WIN_TILE + 1 rows)
-constexpr int WIN_MAX_GRID = 2048;    // the slot kernel strides over tiles with at most this many workgroups
 constexpr int WIN_SCAN_DOCS = 1024;   // documents per workgroup of the window-count scan (four a lane)
 constexpr int WIN_SCAN_HEAD = 4;      // scan words in front of the chunk sums: real slots, split documents, largest w_d, bad offsets
 

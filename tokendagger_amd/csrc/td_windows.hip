@@ -22,25 +22,14 @@
 // leaves without a store.
 #include <hip/hip_runtime.h>
 
-#include "td_common.h"
+#include "td_rows_common.h"
 #include "td_windows.h"
 
 namespace td {
 
 namespace {
 
-__device__ __forceinline__ void win_raise(const WindowArgs& a, int code, int64_t pos) {
-    if (atomicCAS(a.err, 0, code) == 0) *a.err_pos = pos;
-}
-
-// x / d for 0 <= x < 2^63 by magic = floor((2^64 - 1) / d): the estimate is low by at most one
-__device__ __forceinline__ int64_t div_magic(int64_t x, int64_t d, unsigned long long magic) {
-    const unsigned long long D = (unsigned long long)d;
-    unsigned long long q = __umul64hi((unsigned long long)x, magic);
-    unsigned long long r = (unsigned long long)x - q * D;
-    for (int f = 0; f < 2 && r >= D; ++f) { ++q; r -= D; }
-    return (int64_t)q;
-}
+constexpr int WIN_THREADS = RC_THREADS, WIN_TILE = RC_TILE, WIN_MAX_GRID = RC_MAX_GRID;
 
 // L_d; 0 with `bad` set unless 0 <= tok_off[d] <= tok_off[d + 1] <= n_tokens
 __device__ __forceinline__ int64_t win_len(const WindowArgs& a, int64_t d, bool& bad) {
@@ -116,7 +105,7 @@ __global__ __launch_bounds__(WIN_THREADS) void td_win_count(const WindowArgs a) 
     }
     __syncthreads();
     if (bad) {
-        win_raise(a, TD_E_INVALID, bad_at);
+        rows_raise(a, TD_E_INVALID, bad_at);
         s_bad = 1;
     }
     __syncthreads();
@@ -162,7 +151,7 @@ __global__ __launch_bounds__(WIN_THREADS) void td_win_chunks(const WindowArgs a,
         const int64_t rows = a.n_docs > 0 ? carry : 0;
         a.first_row[a.n_docs] = bad ? -1 : rows;
         const bool fits = !bad && rows <= a.rows_cap;
-        if (!bad && !fits) win_raise(a, TD_E_CAPACITY, rows);
+        if (!bad && !fits) rows_raise(a, TD_E_CAPACITY, rows);
         a.counts[0] = bad ? 0 : rows;
         a.counts[1] = fits ? (long long)a.scan[0] : 0;
         a.counts[2] = fits ? (long long)a.scan[1] : 0;
@@ -186,23 +175,6 @@ __global__ __launch_bounds__(WIN_THREADS) void td_win_first(const WindowArgs a) 
         const int64_t d = (int64_t)blockIdx.x * WIN_SCAN_DOCS + tid * 4 + q;
         if (d < a.n_docs) a.first_row[d] = run;
         run += v[q];
-    }
-}
-
-// ids[src] with 0 <= src < n_tokens checked (td_win_slots runs on checked offsets only: this is a second fence, not a path)
-__device__ __forceinline__ int32_t win_load1(const WindowArgs& a, int64_t src) {
-    if (src >= 0 && src < a.n_tokens) return a.ids[src];
-    win_raise(a, TD_E_INVALID, src);
-    return a.pad;
-}
-
-// slots [j0, j0 + 4) below `end`; int4 when aligned (j0 is a multiple of 4)
-__device__ __forceinline__ void win_put4(int32_t* p, int64_t j0, int64_t end, const int32_t v[4]) {
-    if (j0 + 4 <= end && (((uintptr_t)p) & 15) == 0) {
-        *reinterpret_cast<int4*>(p + j0) = make_int4(v[0], v[1], v[2], v[3]);
-    } else {
-        for (int q = 0; q < 4; ++q)
-            if (j0 + q < end) p[j0 + q] = v[q];
     }
 }
 
@@ -286,7 +258,7 @@ __global__ __launch_bounds__(WIN_THREADS) void td_win_slots(const WindowArgs a) 
                 }
                 if (!fast) {
                     if (o < a.b) v[q] = a.bos;
-                    else if (o < a.b + body) v[q] = win_load1(a, tlo + start + o - a.b);
+                    else if (o < a.b + body) v[q] = rows_load1(a, tlo + start + o - a.b);
                     else if (a.e && o == a.b + body) v[q] = a.eos;
                     else v[q] = a.pad;
                 }
@@ -297,8 +269,8 @@ __global__ __launch_bounds__(WIN_THREADS) void td_win_slots(const WindowArgs a) 
                     if (a.row_start) a.row_start[r] = start;
                 }
             }
-            win_put4(a.out, j0, s1, v);
-            if (a.pos) win_put4(a.pos, j0, s1, ps);
+            rows_put4(a.out, j0, s1, v);
+            if (a.pos) rows_put4(a.pos, j0, s1, ps);
         }
     }
 }
