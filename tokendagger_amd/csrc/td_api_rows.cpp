@@ -1,0 +1,762 @@
+// Per-token starts (td_offsets.hip) and the four row layouts (td_rows.hip, td_pack.hip, td_windows.hip): one host path.
+#include <type_traits>
+
+#include "td_handle.h"
+#include "td_offsets.h"
+#include "td_pack.h"
+#include "td_rows.h"
+#include "td_windows.h"
+
+namespace {
+
+// ---- per-token starts (td_offsets.hip) -------------------------------------------------------------------------------------
+int starts_args(td_tokenizer* t, StartsArgs& a, const void* tokens, const void* tok_off, int64_t n_docs, int64_t n_bound, int kind,
+                void* out) {
+    int rc;
+    const int64_t nch = n_bound / OFF_CHUNK + 2;
+    if ((rc = ensure(t, t->off_heads, (size_t)(n_bound / 32 + 2) * 4))) return rc;
+    if ((rc = ensure(t, t->off_chunks, (size_t)nch * 12))) return rc;
+    memset(&a, 0, sizeof a);
+    a.tokens = (const int32_t*)tokens;
+    a.tok_off = (const int64_t*)tok_off;
+    a.n_docs = n_docs;
+    a.n_bound = n_bound;
+    a.len_off = t->dT.tok_off;
+    a.ctab = t->d_ctab;
+    a.max_id = t->H.max_id;
+    a.kind = kind;
+    a.out = (int64_t*)out;
+    a.heads = (uint32_t*)t->off_heads.p;
+    a.chunk_sum = (unsigned long long*)t->off_chunks.p;
+    a.chunk_head = (uint32_t*)(a.chunk_sum + nch);
+    Ctl* ctl = (Ctl*)t->ctl.p;
+    a.err = &ctl->err;
+    a.err_pos = &ctl->err_pos;
+    return TD_OK;
+}
+
+int token_starts_locked(td_tokenizer* t, const void* d_tokens, int64_t n_tokens, const void* d_tok_off, int64_t n_docs, int unit, void* d_out,
+                        hipStream_t stream) {
+    int rc;
+    if ((rc = order_before(t, stream))) return rc;
+    StartsArgs a;
+    if ((rc = starts_args(t, a, d_tokens, d_tok_off, n_docs, n_tokens, unit == TD_UNIT_CHARS ? OFF_CHARS : OFF_BYTES, d_out))) return rc;
+    HIP_TRY(t, launch_token_starts(a, stream));
+    return order_after(t, stream);
+}
+
+// ---- training rows (td_rows.hip, td_pack.hip, td_windows.hip): what the layouts share ----------------------------------------
+enum RowsFamily { FAM_ROWS, FAM_BESTFIT, FAM_WINDOWS };  // the layouts an entry point takes: CONCAT / PAD, BESTFIT, WINDOWS
+
+// The checks of a spec that need no handle (nullptr: fine).  overlap: FAM_WINDOWS only; want_cu: cu_seqlens requested.
+const char* rows_spec_error(RowsFamily fam, const td_rows_spec* sp, int64_t overlap, int64_t rows_capacity, bool want_cu) {
+    if (!sp) return "null td_rows_spec";
+    if (fam == FAM_ROWS && sp->layout != TD_ROWS_CONCAT && sp->layout != TD_ROWS_PAD) return "layout must be TD_ROWS_CONCAT or TD_ROWS_PAD";
+    if (fam == FAM_BESTFIT && sp->layout != TD_ROWS_BESTFIT) return "layout must be TD_ROWS_BESTFIT";
+    if (fam == FAM_WINDOWS && sp->layout != TD_ROWS_WINDOWS) return "layout must be TD_ROWS_WINDOWS";
+    if (sp->seq_len < 1 || sp->seq_len > INT32_MAX) return "seq_len must be in 1 .. 2^31 - 1";
+    if (fam == FAM_ROWS && (sp->flags & ~(int64_t)TD_ROWS_DROP_LAST)) return "unknown td_rows_spec flags";
+    if (fam == FAM_ROWS && (sp->flags & TD_ROWS_DROP_LAST) && sp->layout != TD_ROWS_CONCAT) return "TD_ROWS_DROP_LAST is for TD_ROWS_CONCAT only";
+    if (fam == FAM_BESTFIT && (sp->flags & ~(int64_t)TD_ROWS_TRUNCATE)) return "flags must be 0 or TD_ROWS_TRUNCATE";
+    if (fam == FAM_WINDOWS && sp->flags != 0) return "flags must be 0";
+    if (sp->pad_id < INT32_MIN || sp->pad_id > INT32_MAX) return "pad_id must be an int32";
+    const int64_t C = sp->seq_len - (sp->bos_id >= 0) - (sp->eos_id >= 0);  // body room
+    if (sp->layout == TD_ROWS_PAD && C < 0) return "TD_ROWS_PAD needs seq_len >= the BOS and EOS slots";
+    if (fam == FAM_BESTFIT && (sp->flags & TD_ROWS_TRUNCATE) && C < 0) return "TD_ROWS_TRUNCATE needs seq_len >= the BOS and EOS slots";
+    if (fam == FAM_WINDOWS && C < 1) return "seq_len must leave room for one id beside BOS and EOS";
+    if (fam == FAM_WINDOWS && (overlap < 0 || overlap >= C)) return "overlap must be in 0 .. seq_len - BOS - EOS - 1";
+    if (rows_capacity < 0) return "rows_capacity must be >= 0";
+    if (rows_capacity > ((int64_t)1 << 62) / sp->seq_len) return "rows_capacity * seq_len is too large";
+    if (want_cu && rows_capacity * sp->seq_len >= ((int64_t)1 << 31))
+        return "cu_seqlens entries are int32: rows_capacity * seq_len must stay below 2^31";
+    return nullptr;
+}
+
+// The outputs struct of a BESTFIT (td_pack_outputs) or WINDOWS (td_window_outputs) entry point, then its spec.
+template <class O>
+const char* rows_args_error(const td_rows_spec* sp, int64_t overlap, int64_t n_docs, int64_t rows_capacity, const O* o) {
+    constexpr bool pack = std::is_same<O, td_pack_outputs>::value;
+    if (!o) return pack ? "null td_pack_outputs" : "null td_window_outputs";
+    if (n_docs > INT32_MAX) return pack ? "n_docs must be below 2^31" : "n_docs must stay below 2^31";
+    if (rows_capacity > 0 && !o->ids) return "null ids output";
+    bool want_cu = false;
+    if constexpr (pack) want_cu = o->cu_seqlens != nullptr;
+    return rows_spec_error(pack ? FAM_BESTFIT : FAM_WINDOWS, sp, overlap, rows_capacity, want_cu);
+}
+
+// bos_id / eos_id: -1, or an id of the vocabulary (ordinary or special)
+int rows_check_ids(td_tokenizer* t, const td_rows_spec* sp) {
+    for (const int64_t id : {sp->bos_id, sp->eos_id}) {
+        if (id == -1) continue;
+        if (id < 0 || id > INT32_MAX || td_token_bytes(t, (int32_t)id, nullptr, nullptr) != TD_OK)
+            return fail_unlocked(t, TD_E_BAD_TOKEN, "td_rows_spec: bos_id / eos_id " + std::to_string(id) + " is not in the vocabulary");
+    }
+    return TD_OK;
+}
+
+// The entry points' step between their null tests and the lock: a spec or outputs error `m` as "<fn>: <m>", then the ids' check.
+int rows_spec_fail(td_tokenizer* t, const char* fn, const char* m, const td_rows_spec* sp) {
+    if (m) return fail_unlocked(t, TD_E_INVALID, std::string(fn) + ": " + m);
+    return rows_check_ids(t, sp);
+}
+
+int64_t rows_needed(const td_rows_spec* sp, int64_t n_ids, int64_t n_docs) {
+    if (sp->layout == TD_ROWS_PAD) return n_docs;
+    const int64_t T = n_ids + n_docs * ((sp->bos_id >= 0) + (sp->eos_id >= 0));
+    return (sp->flags & TD_ROWS_DROP_LAST) ? T / sp->seq_len : (T + sp->seq_len - 1) / sp->seq_len;
+}
+
+int rows_funnel_src() {  // TD_ROWS_FUNNEL=1 in the environment: misaligned ids read as aligned int4 and a funnel (A/B)
+    static const int v = getenv("TD_ROWS_FUNNEL") && atoi(getenv("TD_ROWS_FUNNEL")) == 1;
+    return v;
+}
+
+// Zeroes a RowsArgs / PackArgs / WindowArgs and fills the fields they share: the input and the spec's framing.
+template <class A>
+void rows_fill_args(A& a, const void* d_ids, int64_t n_tokens, const void* d_toff, int64_t n_docs, const td_rows_spec* sp) {
+    memset(&a, 0, sizeof a);
+    a.ids = (const int32_t*)d_ids;
+    a.n_tokens = n_tokens;
+    a.tok_off = (const int64_t*)d_toff;
+    a.n_docs = n_docs;
+    a.S = sp->seq_len;
+    a.b = sp->bos_id >= 0;
+    a.e = sp->eos_id >= 0;
+    a.bos = a.b ? (int32_t)sp->bos_id : 0;
+    a.eos = a.e ? (int32_t)sp->eos_id : 0;
+    a.pad = (int32_t)sp->pad_id;
+}
+
+int rows_launch_locked(td_tokenizer* t, const void* d_ids, int64_t n_tokens, const void* d_toff, int64_t n_docs, const td_rows_spec* sp,
+                       void* d_out, int64_t cap, void* d_pos, void* d_aux, void* d_counts, hipStream_t s) {
+    int rc;
+    if ((rc = order_before(t, s))) return rc;
+    t->rows_last = true;
+    RowsArgs a;
+    rows_fill_args(a, d_ids, n_tokens, d_toff, n_docs, sp);
+    a.layout = (int)sp->layout;
+    a.drop_last = (sp->flags & TD_ROWS_DROP_LAST) ? 1 : 0;
+    a.s_magic = ~0ull / (unsigned long long)sp->seq_len;
+    a.funnel_src = rows_funnel_src();
+    a.out = (int32_t*)d_out;
+    a.rows_cap = cap;
+    a.pos = (int32_t*)d_pos;
+    a.aux = (int32_t*)d_aux;
+    a.aux_cap = sp->layout == TD_ROWS_CONCAT ? n_docs + cap + 1 : n_docs;
+    a.counts = (long long*)d_counts;
+    if (d_aux && sp->layout == TD_ROWS_CONCAT) {
+        const size_t bytes = (size_t)rows_scan_words(n_docs) * 8;
+        if ((rc = ensure(t, t->rows_scan, bytes))) return rc;
+        a.scan = (unsigned long long*)t->rows_scan.p;
+        HIP_TRY(t, hipMemsetAsync(a.scan, 0, bytes, s));
+    }
+    HIP_TRY(t, hipMemsetAsync(d_counts, 0, 4 * sizeof(int64_t), s));
+    Ctl* ctl = (Ctl*)t->ctl.p;
+    a.err = &ctl->err;
+    a.err_pos = &ctl->err_pos;
+    HIP_TRY(t, launch_rows(a, s));
+    return order_after(t, s);
+}
+
+// One output of a host-bound form: made on the device in the handle's buffer `dev`, then copied to the caller's `host`.
+struct RowsOut {
+    bool want;
+    void* host;
+    DevBuf* dev;
+    size_t elem;              // bytes an element
+    int64_t n_alloc, n_copy;  // elements the kernels may write, elements the caller gets
+    void* p() const { return want ? dev->p : nullptr; }
+};
+
+int rows_out_ensure(td_tokenizer* t, const RowsOut* o, int n) {
+    int rc;
+    for (int i = 0; i < n; ++i)
+        if (o[i].want && (rc = ensure(t, *o[i].dev, (size_t)std::max<int64_t>(o[i].n_alloc, 1) * o[i].elem))) return rc;
+    return TD_OK;
+}
+
+int rows_out_copy(td_tokenizer* t, const RowsOut* o, int n, hipStream_t s) {
+    int rc;
+    for (int i = 0; i < n; ++i)
+        if (o[i].want && (rc = copy_wait(t, o[i].host, o[i].dev->p, (size_t)o[i].n_copy * o[i].elem, hipMemcpyDeviceToHost, s))) return rc;
+    return TD_OK;
+}
+
+// Host entry points: rows (known on the host, checked against the capacity by the caller) from ids already on the device, into
+// the handle's buffers, then to the caller's.
+int rows_to_host(td_tokenizer* t, const void* d_ids, int64_t n_ids, const void* d_toff, int64_t n_docs, const td_rows_spec* sp, int64_t rows,
+                 int32_t* out_ids, int32_t* out_pos, int32_t* out_aux, int64_t* counts, hipStream_t s) {
+    int rc;
+    const bool concat = sp->layout == TD_ROWS_CONCAT;
+    const int64_t slots = rows * sp->seq_len;
+    RowsOut o[] = {{true, out_ids, &t->rows_out, 4, slots, slots},
+                   {out_pos != nullptr, out_pos, &t->rows_pos, 4, slots, slots},
+                   {out_aux != nullptr, out_aux, &t->rows_aux, 4, concat ? n_docs + rows + 1 : n_docs, n_docs}};
+    if ((rc = rows_out_ensure(t, o, 3))) return rc;
+    if ((rc = ensure(t, t->rows_counts, 4 * sizeof(int64_t)))) return rc;
+    if ((rc = rows_launch_locked(t, d_ids, n_ids, d_toff, n_docs, sp, o[0].p(), rows, o[1].p(), o[2].p(), t->rows_counts.p, s))) return rc;
+    if ((rc = device_status_locked(t, s, nullptr))) return rc;
+    if ((rc = copy_wait(t, counts, t->rows_counts.p, 4 * sizeof(int64_t), hipMemcpyDeviceToHost, s))) return rc;
+    if (concat) o[2].n_copy = counts[2] + 1;  // (cu_seqlens: the segments and the end)
+    return rows_out_copy(t, o, 3, s);
+}
+
+int rows_capacity_fail(td_tokenizer* t, int64_t rows, int64_t* counts) {
+    counts[0] = rows;
+    counts[1] = counts[2] = counts[3] = 0;
+    t->err = "output capacity too small: " + std::to_string(rows) + " rows needed";
+    return TD_E_CAPACITY;
+}
+
+
+// td_make_rows, td_pack_rows, td_window_rows: the checks of the caller's ids and offsets (nothing allocated, nothing enqueued) ...
+int rows_check_host_ids(td_tokenizer* t, const int32_t* ids, int64_t n_tokens, const int64_t* tok_offsets, int64_t n_docs) {
+    int rc;
+    if ((rc = check_offsets(t, "tok_offsets", tok_offsets, n_docs, ids))) return rc;
+    if (tok_offsets[n_docs] > n_tokens) { t->err = "tok_offsets[n_docs] exceeds n_tokens"; return TD_E_INVALID; }
+    return TD_OK;
+}
+
+// ... and their upload into dec_tokens / d_offsets on the handle's own stream `s`.
+int rows_stage_host_ids(td_tokenizer* t, const int32_t* ids, const int64_t* tok_offsets, int64_t n_docs, hipStream_t& s) {
+    int rc;
+    const int64_t total = tok_offsets[n_docs];
+    if ((rc = ensure(t, t->dec_tokens, (size_t)std::max<int64_t>(total, 1) * 4))) return rc;
+    if ((rc = ensure(t, t->d_offsets, (size_t)(n_docs + 1) * 8))) return rc;
+    if ((rc = own_streams(t))) return rc;
+    s = t->s_own;
+    if ((rc = order_before(t, s))) return rc;
+    if (total > 0) HIP_TRY(t, hipMemcpyAsync(t->dec_tokens.p, ids, (size_t)total * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(t, hipMemcpyAsync(t->d_offsets.p, tok_offsets, (size_t)(n_docs + 1) * 8, hipMemcpyHostToDevice, s));
+    return TD_OK;
+}
+
+// td_encode_batch_rows, _pack_rows, _window_rows: the documents encoded on the handle's own stream `s` into d_tokens (room for
+// dev_cap ids) / d_offsets, and the encode's errors returned as such, before the rows read its ids.
+int rows_encode_locked(td_tokenizer* t, const uint8_t* text, const int64_t* doc_offsets, int64_t n_docs, int mode, int64_t& dev_cap,
+                       hipStream_t& s) {
+    int rc;
+    if ((rc = check_offsets(t, "doc_offsets", doc_offsets, n_docs, text))) return rc;
+    const int64_t n = doc_offsets[n_docs];
+    dev_cap = std::max<int64_t>(n, 1);  // (at most one id per byte)
+    if ((rc = ensure(t, t->h2d_text, (size_t)n + 64))) return rc;
+    if ((rc = ensure(t, t->h2d_offs, (size_t)(n_docs + 1) * 8))) return rc;
+    if ((rc = ensure(t, t->d_offsets, (size_t)(n_docs + 1) * 8))) return rc;
+    if ((rc = ensure(t, t->d_tokens, (size_t)dev_cap * 4))) return rc;
+    if ((rc = own_streams(t))) return rc;
+    s = t->s_own;
+    if ((rc = order_before(t, s))) return rc;
+    if (n > 0) {
+        HIP_TRY(t, hipMemcpyAsync(t->h2d_text.p, text, (size_t)n, hipMemcpyHostToDevice, s));
+        HIP_TRY(t, hipMemcpyAsync(t->h2d_offs.p, doc_offsets, (size_t)(n_docs + 1) * 8, hipMemcpyHostToDevice, s));
+        if ((rc = encode_device_locked(t, t->h2d_text.p, n, t->h2d_offs.p, n_docs, mode, t->d_tokens.p, dev_cap, t->d_offsets.p, s))) return rc;
+    } else {  // (nothing but empty documents: no encode)
+        HIP_TRY(t, hipMemsetAsync(t->d_offsets.p, 0, (size_t)(n_docs + 1) * 8, s));
+    }
+    return device_status_locked(t, s, nullptr);
+}
+
+// ---- window rows (td_windows.hip) ---------------------------------------------------------------------------------------------
+// w_d = max(1, ceil((L - overlap) / step))
+int64_t window_count(int64_t L, int64_t C, int64_t overlap) { return L <= C ? 1 : (L - overlap + (C - overlap) - 1) / (C - overlap); }
+
+// Enqueues the scan and the slot kernel into the outputs of o (device pointers); d_counts is device memory.
+int window_launch_locked(td_tokenizer* t, const void* d_ids, int64_t n_tokens, const void* d_toff, int64_t n_docs, const td_rows_spec* sp,
+                         int64_t overlap, const td_window_outputs& o, int64_t cap, void* d_counts, hipStream_t s) {
+    int rc;
+    if ((rc = order_before(t, s))) return rc;
+    t->rows_last = true;
+    WindowArgs a;
+    rows_fill_args(a, d_ids, n_tokens, d_toff, n_docs, sp);
+    a.C = a.S - a.b - a.e;
+    a.overlap = overlap;
+    a.step = a.C - overlap;
+    a.s_magic = ~0ull / (unsigned long long)a.S;
+    a.step_magic = ~0ull / (unsigned long long)a.step;
+    a.out = o.ids;
+    a.rows_cap = cap;
+    a.pos = o.positions;
+    a.row_len = o.row_lengths;
+    a.row_doc = o.row_docs;
+    a.row_start = o.row_starts;
+    a.counts = (long long*)d_counts;
+    const size_t scan_bytes = (size_t)windows_scan_words(n_docs) * 8;
+    if ((rc = ensure(t, t->win_scan, scan_bytes))) return rc;
+    if ((rc = ensure(t, t->win_first, (size_t)(n_docs + 1) * 8))) return rc;
+    a.scan = (unsigned long long*)t->win_scan.p;
+    a.first_row = (int64_t*)t->win_first.p;
+    HIP_TRY(t, hipMemsetAsync(a.scan, 0, WIN_SCAN_HEAD * 8, s));
+    Ctl* ctl = (Ctl*)t->ctl.p;
+    a.err = &ctl->err;
+    a.err_pos = &ctl->err_pos;
+    HIP_TRY(t, launch_windows(a, s));
+    return order_after(t, s);
+}
+
+// Host entry points: `rows` rows (known on the host, checked against the capacity by the caller) from ids already on the device,
+// into the handle's buffers, then into host_out.
+int window_to_host(td_tokenizer* t, const void* d_ids, int64_t n_ids, const void* d_toff, int64_t n_docs, const td_rows_spec* sp,
+                   int64_t overlap, const td_window_outputs& ho, int64_t rows, int64_t* counts, hipStream_t s) {
+    int rc;
+    const int64_t slots = rows * sp->seq_len;
+    RowsOut o[] = {{true, ho.ids, &t->rows_out, 4, slots, slots},
+                   {ho.positions != nullptr, ho.positions, &t->rows_pos, 4, slots, slots},
+                   {ho.row_lengths != nullptr, ho.row_lengths, &t->win_len, 4, rows, rows},
+                   {ho.row_docs != nullptr, ho.row_docs, &t->win_docs, 8, rows, rows},
+                   {ho.row_starts != nullptr, ho.row_starts, &t->win_starts, 8, rows, rows}};
+    if ((rc = rows_out_ensure(t, o, 5))) return rc;
+    if ((rc = ensure(t, t->rows_counts, 4 * sizeof(int64_t)))) return rc;
+    const td_window_outputs d{(int32_t*)o[0].p(), (int32_t*)o[1].p(), (int32_t*)o[2].p(), (int64_t*)o[3].p(), (int64_t*)o[4].p()};
+    if ((rc = window_launch_locked(t, d_ids, n_ids, d_toff, n_docs, sp, overlap, d, rows, t->rows_counts.p, s))) return rc;
+    if ((rc = device_status_locked(t, s, nullptr))) return rc;
+    if ((rc = copy_wait(t, counts, t->rows_counts.p, 4 * sizeof(int64_t), hipMemcpyDeviceToHost, s))) return rc;
+    return rows_out_copy(t, o, 5, s);
+}
+
+// ---- best-fit packing (td_pack.hip) ------------------------------------------------------------------------------------------
+// A document's slots after truncation, its full chunks and its remainder (the one item that is not a full row).
+struct PackDoc {
+    int64_t n, full, rem;
+    bool cut;
+};
+PackDoc pack_doc(const td_rows_spec* sp, int64_t L) {
+    const int64_t S = sp->seq_len, b = sp->bos_id >= 0, e = sp->eos_id >= 0;
+    PackDoc p;
+    if (sp->flags & TD_ROWS_TRUNCATE) {
+        const int64_t body = std::min(L, S - b - e);
+        p.n = b + body + e;
+        p.full = p.n == S;
+        p.rem = p.n == S ? 0 : p.n;
+        p.cut = body < L;
+    } else {
+        p.n = b + L + e;
+        p.full = p.n / S;
+        p.rem = p.n % S;
+        p.cut = p.n > S;
+    }
+    return p;
+}
+
+
+// The device pipeline up to the plan: items, scan, sort and run-length encode on `s`, one read-back and synchronisation, the
+// host plan.  Fills `a` (everything but the outputs and the segment arrays) and counts.  Offsets that are negative, decreasing
+// or beyond n_tokens: TD_E_INVALID, nothing launched behind the read-back.
+int pack_prepare(td_tokenizer* t, const void* d_ids, int64_t n_tokens, const void* d_toff, int64_t n_docs, const td_rows_spec* sp,
+                 hipStream_t s, PackArgs& a, PackPlan& plan, int64_t* counts) {
+    int rc;
+    if ((rc = order_before(t, s))) return rc;
+    rows_fill_args(a, d_ids, n_tokens, d_toff, n_docs, sp);
+    a.truncate = (sp->flags & TD_ROWS_TRUNCATE) ? 1 : 0;
+    const size_t nd = (size_t)std::max<int64_t>(n_docs, 1);
+    for (DevBuf* b : {&t->pack_key, &t->pack_val, &t->pack_key2, &t->pack_val2})
+        if ((rc = ensure(t, *b, nd * 4))) return rc;
+    if ((rc = ensure(t, t->pack_full, nd * 8)) || (rc = ensure(t, t->pack_pref, nd * 8))) return rc;
+    if ((rc = ensure(t, t->pack_hdr, PACK_HDR * 8 + nd * 8))) return rc;
+    a.key = (uint32_t*)t->pack_key.p;
+    a.val = (uint32_t*)t->pack_val.p;
+    a.full = (int64_t*)t->pack_full.p;
+    a.hdr = (long long*)t->pack_hdr.p;
+    uint32_t* runs_key = (uint32_t*)(a.hdr + PACK_HDR);
+    uint32_t* runs_cnt = runs_key + nd;
+    size_t tb = 0;
+    HIP_TRY(t, pack_sort_runs(nullptr, tb, a, (uint32_t*)t->pack_key2.p, (uint32_t*)t->pack_val2.p, (int64_t*)t->pack_pref.p, runs_key, runs_cnt, s));
+    if ((rc = ensure(t, t->pack_tmp, tb))) return rc;
+    HIP_TRY(t, hipMemsetAsync(a.hdr, 0, PACK_HDR * 8, s));
+    HIP_TRY(t, launch_pack_items(a, s));
+    HIP_TRY(t, pack_sort_runs(t->pack_tmp.p, tb, a, (uint32_t*)t->pack_key2.p, (uint32_t*)t->pack_val2.p, (int64_t*)t->pack_pref.p, runs_key, runs_cnt, s));
+    // the header and the first runs in one round trip
+    const int64_t k0 = std::min<int64_t>(n_docs, PACK_RUNS_FIRST);
+    if ((rc = pinned_ensure(t, t->pack_h, PACK_HDR * 8 + (size_t)k0 * 8))) return rc;
+    long long* h = (long long*)t->pack_h.p;
+    uint32_t* h_key = (uint32_t*)(h + PACK_HDR);
+    uint32_t* h_cnt = h_key + k0;
+    HIP_TRY(t, hipMemcpyAsync(h, a.hdr, PACK_HDR * 8, hipMemcpyDeviceToHost, s));
+    if (k0 > 0) {
+        HIP_TRY(t, hipMemcpyAsync(h_key, runs_key, (size_t)k0 * 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(t, hipMemcpyAsync(h_cnt, runs_cnt, (size_t)k0 * 4, hipMemcpyDeviceToHost, s));
+    }
+    HIP_TRY(t, hipStreamSynchronize(s));
+    if (h[PH_ERR]) {
+        t->err = "tok_offsets: document " + std::to_string(n_docs - h[PH_ERR_DOC]) +
+                 " has offsets that are negative, decreasing or beyond n_tokens";
+        return TD_E_INVALID;
+    }
+    const int64_t n_runs = (int64_t)(uint32_t)h[PH_RUNS];
+    std::vector<uint32_t> more_key, more_cnt;
+    if (n_runs > k0) {  // (S > PACK_RUNS_FIRST and that many distinct lengths)
+        more_key.resize(n_runs - k0);
+        more_cnt.resize(n_runs - k0);
+        if ((rc = copy_wait(t, more_key.data(), runs_key + k0, (size_t)(n_runs - k0) * 4, hipMemcpyDeviceToHost, s))) return rc;
+        if ((rc = copy_wait(t, more_cnt.data(), runs_cnt + k0, (size_t)(n_runs - k0) * 4, hipMemcpyDeviceToHost, s))) return rc;
+    }
+    std::vector<int64_t> lens, cnts;
+    for (int64_t r = 0; r < n_runs; ++r) {
+        const uint32_t key = r < k0 ? h_key[r] : more_key[r - k0];
+        if ((int64_t)key == a.S) continue;  // documents without a remainder item
+        lens.push_back(a.S - (int64_t)key);
+        cnts.push_back(r < k0 ? h_cnt[r] : more_cnt[r - k0]);
+    }
+    pack_plan_runs(a.S, h[PH_FULL], h[PH_REAL], lens.data(), cnts.data(), (int64_t)lens.size(), plan);
+    a.full_rows = plan.full;
+    a.n_mixed = (int64_t)plan.fill.size();
+    a.n_items = h[PH_ITEMS];
+    a.rows = plan.rows;
+    a.segs = plan.segs;
+    a.pref = (const int64_t*)t->pack_pref.p;
+    a.sorted_doc = (const uint32_t*)t->pack_val2.p;
+    counts[0] = plan.rows;
+    counts[1] = plan.real;
+    counts[2] = plan.segs;
+    counts[3] = h[PH_CUT];
+    return TD_OK;
+}
+
+// Uploads the plan and enqueues td_pack_segments + td_pack_slots into the outputs of o (device pointers).
+int pack_emit(td_tokenizer* t, PackArgs& a, const PackPlan& plan, const td_pack_outputs& o, hipStream_t s) {
+    int rc;
+    const size_t n_pl = plan.pl.size(), n_m = plan.fill.size();
+    const size_t up = n_pl * sizeof(PackPlacement) + (n_m + n_m + 1) * 8;
+    if ((rc = pinned_ensure(t, t->pack_up, up))) return rc;
+    if ((rc = ensure(t, t->pack_plan, up))) return rc;
+    char* hp = (char*)t->pack_up.p;
+    if (n_pl) memcpy(hp, plan.pl.data(), n_pl * sizeof(PackPlacement));
+    if (n_m) memcpy(hp + n_pl * sizeof(PackPlacement), plan.fill.data(), n_m * 8);
+    memcpy(hp + n_pl * sizeof(PackPlacement) + n_m * 8, plan.seg0.data(), (n_m + 1) * 8);
+    HIP_TRY(t, hipMemcpyAsync(t->pack_plan.p, hp, up, hipMemcpyHostToDevice, s));
+    const char* dp = (const char*)t->pack_plan.p;
+    a.pl = (const PackPlacement*)dp;
+    a.n_pl = (int64_t)n_pl;
+    a.fill = (const int64_t*)(dp + n_pl * sizeof(PackPlacement));
+    a.seg0 = a.fill + n_m;
+    const size_t ns = (size_t)plan.segs + 1;
+    if ((rc = ensure(t, t->pack_seg, ns * 8 * 3))) return rc;
+    a.seg_start = (int64_t*)t->pack_seg.p;
+    a.seg_doc = a.seg_start + ns;
+    a.seg_q0 = a.seg_doc + ns;
+    a.out = o.ids;
+    a.pos = o.positions;
+    a.cu = o.cu_seqlens;
+    a.lengths = o.row_lengths;
+    a.docs = o.seg_docs;
+    HIP_TRY(t, launch_pack_outputs(a, s));
+    return order_after(t, s);
+}
+
+// Host entry points: packs ids already on the device into the handle's buffers, then copies them into host_out.
+int pack_to_host(td_tokenizer* t, const void* d_ids, int64_t n_ids, const void* d_toff, int64_t n_docs, const td_rows_spec* sp,
+                 const td_pack_outputs& ho, int64_t cap, int64_t* counts, hipStream_t s) {
+    int rc;
+    PackArgs a;
+    PackPlan plan;
+    if ((rc = pack_prepare(t, d_ids, n_ids, d_toff, n_docs, sp, s, a, plan, counts))) return rc;
+    if (plan.rows > cap) return rows_capacity_fail(t, plan.rows, counts);
+    const int64_t slots = plan.rows * sp->seq_len;
+    const RowsOut o[] = {{true, ho.ids, &t->rows_out, 4, slots, slots},
+                         {ho.positions != nullptr, ho.positions, &t->rows_pos, 4, slots, slots},
+                         {ho.cu_seqlens != nullptr, ho.cu_seqlens, &t->rows_aux, 4, plan.segs + 1, plan.segs + 1},
+                         {ho.row_lengths != nullptr, ho.row_lengths, &t->pack_len, 4, plan.rows, plan.rows},
+                         {ho.seg_docs != nullptr, ho.seg_docs, &t->pack_docs, 8, plan.segs + 1, plan.segs}};
+    if ((rc = rows_out_ensure(t, o, 5))) return rc;
+    const td_pack_outputs d{(int32_t*)o[0].p(), (int32_t*)o[1].p(), (int32_t*)o[2].p(), (int32_t*)o[3].p(), (int64_t*)o[4].p()};
+    if ((rc = pack_emit(t, a, plan, d, s))) return rc;
+    if ((rc = rows_out_copy(t, o, 5, s))) return rc;
+    HIP_TRY(t, hipStreamSynchronize(s));  // (nothing copied at all: the kernels are still done when the call returns)
+    return TD_OK;
+}
+
+}  // namespace
+
+// Behind encode_device_locked, on the same stream: the generic engine's bitmaps in the workspace are still those of this call.
+// Starts by the covered rule (chars: bytes and characters packed, every document checked against its length), then the documents
+// with skipped text through the covered-byte bitmap.
+int td::encode_starts_locked(td_tokenizer* t, const void* d_text, int64_t n, const void* d_offs, int64_t n_docs, const void* d_tokens,
+                             int64_t cap, const void* d_out_offs, int unit, void* d_starts, hipStream_t stream) {
+    const int64_t bound = std::min(cap, n);
+    if (bound <= 0 || n_docs <= 0) return TD_OK;  // (no ids; a capacity too small for the ids is the encode's error)
+    const bool chars = unit == TD_UNIT_CHARS, generic = t->H.pattern_kind == PATTERN_GENERIC;
+    int rc;
+    StartsArgs a;
+    if ((rc = starts_args(t, a, d_tokens, d_out_offs, n_docs, bound, chars ? OFF_PAIR : OFF_BYTES, d_starts))) return rc;
+    if ((rc = ensure(t, t->off_docs, (size_t)n_docs + 16))) return rc;
+    a.text = (const uint8_t*)d_text;
+    a.n = n;
+    a.doc_off = (const int64_t*)d_offs;
+    a.doc_gap = (uint8_t*)t->off_docs.p;
+    a.generic = generic ? 1 : 0;
+    a.chars = chars ? 1 : 0;
+    if (generic) {
+        if ((rc = ensure(t, t->off_rank, off_rank_bytes(n)))) return rc;
+        off_rank_layout(a, t->off_rank.p, n);
+        a.startbits = (const uint32_t*)t->startbits.p;
+        a.gapbits = (const uint32_t*)t->gapbits.p;
+    }
+    HIP_TRY(t, launch_token_starts(a, stream));
+    HIP_TRY(t, launch_encode_starts(a, stream));
+    return order_after(t, stream);
+}
+
+extern "C" {
+
+int td_token_starts(td_tokenizer* t, const int32_t* tokens, int64_t n_tokens, const int64_t* tok_offsets, int64_t n_docs, int unit,
+                    int64_t* out_starts) {
+    if (!t || n_tokens < 0 || (n_tokens > 0 && (!tokens || !out_starts)) || !tok_offsets || n_docs < 0 ||
+        (unit != TD_UNIT_BYTES && unit != TD_UNIT_CHARS))
+        return TD_E_INVALID;
+    return locked(t, [&] {
+        int rc;
+        if ((rc = check_offsets(t, "tok_offsets", tok_offsets, n_docs, tokens))) return rc;
+        const int64_t total = tok_offsets[n_docs];
+        if (total > n_tokens) { t->err = "output capacity too small: " + std::to_string(total) + " starts needed"; return (int)TD_E_CAPACITY; }
+        if (total == 0) return (int)TD_OK;
+        if ((rc = ensure(t, t->dec_tokens, (size_t)total * 4))) return rc;
+        if ((rc = ensure(t, t->d_offsets, (size_t)(n_docs + 1) * 8))) return rc;
+        if ((rc = ensure(t, t->off_starts, (size_t)total * 8))) return rc;
+        if ((rc = own_streams(t))) return rc;
+        hipStream_t s = t->s_own;
+        if ((rc = order_before(t, s))) return rc;
+        HIP_TRY(t, hipMemcpyAsync(t->dec_tokens.p, tokens, (size_t)total * 4, hipMemcpyHostToDevice, s));
+        HIP_TRY(t, hipMemcpyAsync(t->d_offsets.p, tok_offsets, (size_t)(n_docs + 1) * 8, hipMemcpyHostToDevice, s));
+        if ((rc = token_starts_locked(t, t->dec_tokens.p, total, t->d_offsets.p, n_docs, unit, t->off_starts.p, s))) return rc;
+        if ((rc = device_status_locked(t, s, nullptr))) return rc;
+        return copy_wait(t, out_starts, t->off_starts.p, (size_t)total * 8, hipMemcpyDeviceToHost, s);
+    });
+}
+
+int td_token_starts_device(td_tokenizer* t, const void* d_tokens, int64_t n_tokens, const void* d_tok_offsets, int64_t n_docs, int unit,
+                           void* d_out_starts, void* hip_stream) {
+    if (!t || n_tokens < 0 || (n_tokens > 0 && (!d_tokens || !d_out_starts)) || !d_tok_offsets || n_docs < 0 ||
+        (unit != TD_UNIT_BYTES && unit != TD_UNIT_CHARS))
+        return TD_E_INVALID;
+    return locked(t, [&] {
+        return token_starts_locked(t, d_tokens, n_tokens, d_tok_offsets, n_docs, unit, d_out_starts, (hipStream_t)hip_stream);
+    });
+}
+
+int td_encode_device_with_starts(td_tokenizer* t, const void* d_text, int64_t n_bytes, const void* d_doc_offsets, int64_t n_docs, int mode,
+                                 int unit, void* d_out_tokens, int64_t out_capacity, void* d_out_offsets, void* d_out_starts,
+                                 void* hip_stream) {
+    if (!t || (unit != TD_UNIT_BYTES && unit != TD_UNIT_CHARS) || (n_bytes > 0 && out_capacity > 0 && !d_out_starts)) return TD_E_INVALID;
+    if (unit == TD_UNIT_CHARS && n_bytes >= (1ll << 32))
+        return fail_unlocked(t, TD_E_INVALID, "td_encode_device_with_starts: character starts need less than 4 GiB of text a call");
+    return locked(t, [&] {
+        const hipStream_t s = (hipStream_t)hip_stream;
+        int rc = encode_device_locked(t, d_text, n_bytes, d_doc_offsets, n_docs, mode, d_out_tokens, out_capacity, d_out_offsets, s);
+        if (rc) return rc;
+        return encode_starts_locked(t, d_text, n_bytes, d_doc_offsets, n_docs, d_out_tokens, out_capacity, d_out_offsets, unit, d_out_starts, s);
+    });
+}
+
+int td_make_rows_device(td_tokenizer* t, const void* d_ids, int64_t n_tokens, const void* d_tok_offsets, int64_t n_docs,
+                        const td_rows_spec* spec, void* d_out_ids, int64_t rows_capacity, void* d_positions, void* d_aux,
+                        void* d_counts, void* hip_stream) {
+    if (!t || !spec || n_tokens < 0 || n_docs < 0 || !d_tok_offsets || (n_tokens > 0 && !d_ids) || !d_counts ||
+        (rows_capacity > 0 && !d_out_ids))
+        return TD_E_INVALID;
+    if (int rc = rows_spec_fail(t, "td_make_rows_device",
+                                rows_spec_error(FAM_ROWS, spec, 0, rows_capacity, spec->layout == TD_ROWS_CONCAT && d_aux), spec)) return rc;
+    return locked(t, [&] {
+        return rows_launch_locked(t, d_ids, n_tokens, d_tok_offsets, n_docs, spec, d_out_ids, rows_capacity, d_positions, d_aux, d_counts,
+                                  (hipStream_t)hip_stream);
+    });
+}
+
+int td_make_rows(td_tokenizer* t, const int32_t* ids, int64_t n_tokens, const int64_t* tok_offsets, int64_t n_docs,
+                 const td_rows_spec* spec, int32_t* out_ids, int64_t rows_capacity, int32_t* out_positions, int32_t* out_aux,
+                 int64_t* counts) {
+    if (!t || !spec || n_tokens < 0 || n_docs < 0 || !tok_offsets || !counts || (rows_capacity > 0 && !out_ids)) return TD_E_INVALID;
+    if (int rc = rows_spec_fail(t, "td_make_rows",
+                                rows_spec_error(FAM_ROWS, spec, 0, rows_capacity, spec->layout == TD_ROWS_CONCAT && out_aux), spec)) return rc;
+    return locked(t, [&] {
+        int rc2;
+        if ((rc2 = rows_check_host_ids(t, ids, n_tokens, tok_offsets, n_docs))) return rc2;
+        const int64_t total = tok_offsets[n_docs];
+        const int64_t rows = rows_needed(spec, total, n_docs);
+        if (rows > rows_capacity) return rows_capacity_fail(t, rows, counts);
+        hipStream_t s;
+        if ((rc2 = rows_stage_host_ids(t, ids, tok_offsets, n_docs, s))) return rc2;
+        return rows_to_host(t, t->dec_tokens.p, total, t->d_offsets.p, n_docs, spec, rows, out_ids, out_positions, out_aux, counts, s);
+    });
+}
+
+int td_encode_batch_rows(td_tokenizer* t, const uint8_t* text, const int64_t* doc_offsets, int64_t n_docs, int mode,
+                         const td_rows_spec* spec, int32_t* out_ids, int64_t rows_capacity, int32_t* out_positions, int32_t* out_aux,
+                         int64_t* counts) {
+    if (!t || !spec || !doc_offsets || n_docs < 0 || !counts || (rows_capacity > 0 && !out_ids) ||
+        (mode != TD_MODE_ENCODE && mode != TD_MODE_ORDINARY))
+        return TD_E_INVALID;
+    if (int rc = rows_spec_fail(t, "td_encode_batch_rows",
+                                rows_spec_error(FAM_ROWS, spec, 0, rows_capacity, spec->layout == TD_ROWS_CONCAT && out_aux), spec)) return rc;
+    return locked(t, [&] {
+        int rc2;
+        int64_t dev_cap;
+        hipStream_t s;
+        if ((rc2 = rows_encode_locked(t, text, doc_offsets, n_docs, mode, dev_cap, s))) return rc2;
+        int64_t total = 0;
+        if ((rc2 = copy_wait(t, &total, (const int64_t*)t->d_offsets.p + n_docs, 8, hipMemcpyDeviceToHost, s))) return rc2;
+        const int64_t rows = rows_needed(spec, total, n_docs);
+        if (rows > rows_capacity) return rows_capacity_fail(t, rows, counts);
+        return rows_to_host(t, t->d_tokens.p, dev_cap, t->d_offsets.p, n_docs, spec, rows, out_ids, out_positions, out_aux, counts, s);
+    });
+}
+
+int td_pack_plan(const int64_t* tok_offsets, int64_t n_docs, const td_rows_spec* spec, int64_t* counts, int64_t* doc_row,
+                 int64_t* doc_slot) {
+    if (!tok_offsets || n_docs < 0 || n_docs > INT32_MAX || !counts || rows_spec_error(FAM_BESTFIT, spec, 0, 0, false)) return TD_E_INVALID;
+    if (tok_offsets[0] != 0) return TD_E_INVALID;
+    for (int64_t d = 0; d < n_docs; ++d)
+        if (tok_offsets[d + 1] < tok_offsets[d]) return TD_E_INVALID;
+    const int64_t S = spec->seq_len;
+    std::vector<int64_t> rem((size_t)n_docs), order;
+    int64_t F = 0, R = 0, cut = 0;
+    for (int64_t d = 0; d < n_docs; ++d) {
+        const PackDoc p = pack_doc(spec, tok_offsets[d + 1] - tok_offsets[d]);
+        if (doc_row) doc_row[d] = p.full == 1 && p.rem == 0 ? F : -1;  // (a document that is exactly one full row)
+        if (doc_slot) doc_slot[d] = p.full == 1 && p.rem == 0 ? 0 : -1;
+        rem[d] = p.rem;
+        F += p.full;
+        R += p.n;
+        cut += p.cut;
+        if (p.rem) order.push_back(d);
+    }
+    std::stable_sort(order.begin(), order.end(), [&](int64_t x, int64_t y) { return rem[x] > rem[y]; });
+    std::vector<int64_t> lens, cnts;
+    for (const int64_t d : order) {
+        if (lens.empty() || lens.back() != rem[d]) { lens.push_back(rem[d]); cnts.push_back(0); }
+        ++cnts.back();
+    }
+    PackPlan plan;
+    pack_plan_runs(S, F, R, lens.data(), cnts.data(), (int64_t)lens.size(), plan);
+    if (doc_row || doc_slot)
+        for (const PackPlacement& p : plan.pl)
+            for (int64_t j = 0; j < p.count; ++j) {
+                const int64_t d = order[p.first_item + j];
+                if (doc_row) doc_row[d] = p.row;
+                if (doc_slot) doc_slot[d] = p.slot + j * p.len;
+            }
+    counts[0] = plan.rows;
+    counts[1] = R;
+    counts[2] = plan.segs;
+    counts[3] = cut;
+    return TD_OK;
+}
+
+int td_pack_rows(td_tokenizer* t, const int32_t* ids, int64_t n_tokens, const int64_t* tok_offsets, int64_t n_docs,
+                 const td_rows_spec* spec, const td_pack_outputs* host_out, int64_t rows_capacity, int64_t* counts) {
+    if (!t || !spec || !host_out || n_tokens < 0 || n_docs < 0 || !tok_offsets || !counts) return TD_E_INVALID;
+    if (int rc = rows_spec_fail(t, "td_pack_rows", rows_args_error(spec, 0, n_docs, rows_capacity, host_out), spec)) return rc;
+    return locked(t, [&] {
+        int rc2;
+        if ((rc2 = rows_check_host_ids(t, ids, n_tokens, tok_offsets, n_docs))) return rc2;
+        const int64_t total = tok_offsets[n_docs];
+        hipStream_t s;
+        if ((rc2 = rows_stage_host_ids(t, ids, tok_offsets, n_docs, s))) return rc2;
+        return pack_to_host(t, t->dec_tokens.p, total, t->d_offsets.p, n_docs, spec, *host_out, rows_capacity, counts, s);
+    });
+}
+
+int td_pack_rows_device(td_tokenizer* t, const void* d_ids, int64_t n_tokens, const void* d_tok_offsets, int64_t n_docs,
+                        const td_rows_spec* spec, const td_pack_outputs* dev_out, int64_t rows_capacity, int64_t* counts,
+                        void* hip_stream) {
+    if (!t || !spec || !dev_out || n_tokens < 0 || n_docs < 0 || !d_tok_offsets || (n_tokens > 0 && !d_ids) || !counts)
+        return TD_E_INVALID;
+    if (int rc = rows_spec_fail(t, "td_pack_rows_device", rows_args_error(spec, 0, n_docs, rows_capacity, dev_out), spec)) return rc;
+    return locked(t, [&] {
+        hipStream_t s = (hipStream_t)hip_stream;
+        PackArgs a;
+        PackPlan plan;
+        int rc2;
+        if ((rc2 = pack_prepare(t, d_ids, n_tokens, d_tok_offsets, n_docs, spec, s, a, plan, counts))) return rc2;
+        if (plan.rows > rows_capacity) return rows_capacity_fail(t, plan.rows, counts);
+        return pack_emit(t, a, plan, *dev_out, s);
+    });
+}
+
+int td_encode_batch_pack_rows(td_tokenizer* t, const uint8_t* text, const int64_t* doc_offsets, int64_t n_docs, int mode,
+                              const td_rows_spec* spec, const td_pack_outputs* host_out, int64_t rows_capacity, int64_t* counts) {
+    if (!t || !spec || !host_out || !doc_offsets || n_docs < 0 || !counts || (mode != TD_MODE_ENCODE && mode != TD_MODE_ORDINARY))
+        return TD_E_INVALID;
+    if (int rc = rows_spec_fail(t, "td_encode_batch_pack_rows", rows_args_error(spec, 0, n_docs, rows_capacity, host_out), spec)) return rc;
+    return locked(t, [&] {
+        int rc2;
+        int64_t dev_cap;
+        hipStream_t s;
+        if ((rc2 = rows_encode_locked(t, text, doc_offsets, n_docs, mode, dev_cap, s))) return rc2;
+        return pack_to_host(t, t->d_tokens.p, dev_cap, t->d_offsets.p, n_docs, spec, *host_out, rows_capacity, counts, s);
+    });
+}
+
+int td_window_plan(const int64_t* tok_offsets, int64_t n_docs, const td_rows_spec* spec, int64_t overlap, int64_t* counts,
+                   int64_t* first_row) {
+    if (!tok_offsets || n_docs < 0 || n_docs > INT32_MAX || !counts || rows_spec_error(FAM_WINDOWS, spec, overlap, 0, false)) return TD_E_INVALID;
+    if (tok_offsets[0] != 0) return TD_E_INVALID;
+    const int64_t k = (spec->bos_id >= 0) + (spec->eos_id >= 0), C = spec->seq_len - k;
+    int64_t rows = 0, R = 0, multi = 0, mx = 0;
+    for (int64_t d = 0; d < n_docs; ++d) {
+        const int64_t L = tok_offsets[d + 1] - tok_offsets[d];
+        if (L < 0) return TD_E_INVALID;
+        const int64_t w = window_count(L, C, overlap);
+        if (first_row) first_row[d] = rows;
+        rows += w;
+        R += w * k + L + (w - 1) * overlap;
+        multi += w > 1;
+        mx = std::max(mx, w);
+    }
+    if (first_row) first_row[n_docs] = rows;
+    counts[0] = rows;
+    counts[1] = R;
+    counts[2] = multi;
+    counts[3] = mx;
+    return TD_OK;
+}
+
+int td_window_rows_device(td_tokenizer* t, const void* d_ids, int64_t n_tokens, const void* d_tok_offsets, int64_t n_docs,
+                          const td_rows_spec* spec, int64_t overlap, const td_window_outputs* dev_out, int64_t rows_capacity,
+                          void* d_counts, void* hip_stream) {
+    if (!t || !spec || !dev_out || n_tokens < 0 || n_docs < 0 || !d_tok_offsets || (n_tokens > 0 && !d_ids) || !d_counts)
+        return TD_E_INVALID;
+    if (int rc = rows_spec_fail(t, "td_window_rows_device", rows_args_error(spec, overlap, n_docs, rows_capacity, dev_out), spec)) return rc;
+    return locked(t, [&] {
+        return window_launch_locked(t, d_ids, n_tokens, d_tok_offsets, n_docs, spec, overlap, *dev_out, rows_capacity, d_counts,
+                                    (hipStream_t)hip_stream);
+    });
+}
+
+int td_window_rows(td_tokenizer* t, const int32_t* ids, int64_t n_tokens, const int64_t* tok_offsets, int64_t n_docs,
+                   const td_rows_spec* spec, int64_t overlap, const td_window_outputs* host_out, int64_t rows_capacity, int64_t* counts) {
+    if (!t || !spec || !host_out || n_tokens < 0 || n_docs < 0 || !tok_offsets || !counts) return TD_E_INVALID;
+    if (int rc = rows_spec_fail(t, "td_window_rows", rows_args_error(spec, overlap, n_docs, rows_capacity, host_out), spec)) return rc;
+    return locked(t, [&] {
+        int rc2;
+        if ((rc2 = rows_check_host_ids(t, ids, n_tokens, tok_offsets, n_docs))) return rc2;
+        const int64_t total = tok_offsets[n_docs];
+        int64_t plan[4];
+        if (td_window_plan(tok_offsets, n_docs, spec, overlap, plan, nullptr) != TD_OK) { t->err = "invalid tok_offsets"; return (int)TD_E_INVALID; }
+        if (plan[0] > rows_capacity) return rows_capacity_fail(t, plan[0], counts);
+        hipStream_t s;
+        if ((rc2 = rows_stage_host_ids(t, ids, tok_offsets, n_docs, s))) return rc2;
+        return window_to_host(t, t->dec_tokens.p, total, t->d_offsets.p, n_docs, spec, overlap, *host_out, plan[0], counts, s);
+    });
+}
+
+int td_encode_batch_window_rows(td_tokenizer* t, const uint8_t* text, const int64_t* doc_offsets, int64_t n_docs, int mode,
+                                const td_rows_spec* spec, int64_t overlap, const td_window_outputs* host_out, int64_t rows_capacity,
+                                int64_t* counts) {
+    if (!t || !spec || !host_out || !doc_offsets || n_docs < 0 || !counts || (mode != TD_MODE_ENCODE && mode != TD_MODE_ORDINARY))
+        return TD_E_INVALID;
+    if (int rc = rows_spec_fail(t, "td_encode_batch_window_rows", rows_args_error(spec, overlap, n_docs, rows_capacity, host_out), spec)) return rc;
+    return locked(t, [&] {
+        int rc2;
+        int64_t dev_cap;
+        hipStream_t s;
+        if ((rc2 = rows_encode_locked(t, text, doc_offsets, n_docs, mode, dev_cap, s))) return rc2;
+        // the rows are known from the token offsets: they come back (8 bytes a document) and are planned on the host
+        std::vector<int64_t> toff((size_t)n_docs + 1);
+        if ((rc2 = copy_wait(t, toff.data(), t->d_offsets.p, (size_t)(n_docs + 1) * 8, hipMemcpyDeviceToHost, s))) return rc2;
+        int64_t plan[4];
+        if (td_window_plan(toff.data(), n_docs, spec, overlap, plan, nullptr) != TD_OK) { t->err = "invalid token offsets"; return (int)TD_E_INVALID; }
+        if (plan[0] > rows_capacity) return rows_capacity_fail(t, plan[0], counts);
+        return window_to_host(t, t->d_tokens.p, dev_cap, t->d_offsets.p, n_docs, spec, overlap, *host_out, plan[0], counts, s);
+    });
+}
+
+}  // extern "C"

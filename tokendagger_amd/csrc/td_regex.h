@@ -1,6 +1,6 @@
 // Generic split patterns: a compiled form of the backtracking subset of PCRE2 patterns that tokenizer split
 // patterns are written in, and the matcher that runs it — the SAME code on the device (td_generic.hip: one lane per
-// document), on the host (td_regex.cpp compiles; td_api.cpp's last-piece helper) and in the CPU twin of the test-suite.
+// document), on the host (td_regex.cpp compiles; td_api_special.cpp's last-piece helper) and in the CPU twin of the test-suite.
 //
 // What the reference does with a pattern (tiktoken.cpp:47-128): pcre2_compile(pattern, PCRE2_UTF | PCRE2_UCP), then a
 // loop of pcre2_match(subject = the document, start_offset, PCRE2_NOTEMPTY): the leftmost match at or behind start_offset

@@ -6,6 +6,8 @@ R=$(cd "$(dirname "$0")/.." && pwd)
 name=$1; shift
 mkdir -p $R/variants
 C=$R/tokendagger_amd/csrc
+# (every source of the library, as build_hip() in __graft_entry__.py takes them: all of csrc/ but the pybind module)
+srcs=$(ls $C/*.hip $C/*.cpp | grep -v '/py_binding\.cpp$')
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -shared -Wno-unused-function "$@" \
-  $C/td_kernels.hip $C/td_generic.hip $C/td_special.hip $C/td_api.cpp $C/td_tables.cpp $C/td_regex.cpp $C/td_vocab.cpp $C/td_comm.cpp -I$R/include -ldl -o $R/variants/$name.so
+  $srcs -I$R/include -ldl -o $R/variants/$name.so
 echo built $R/variants/$name.so
