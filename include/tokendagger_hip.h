@@ -390,6 +390,65 @@ int td_encode_batch_window_rows(td_tokenizer* t, const uint8_t* text, const int6
                                 const td_rows_spec* spec, int64_t overlap, const td_window_outputs* host_out, int64_t rows_capacity,
                                 int64_t* counts);
 
+/* ---- loss labels: train only inside marked id spans (td_labels.hip) ----------------------------------------------------------
+ * ids + per-document token offsets -> labels[i] = ids[i] where the loss applies, ignore_index everywhere else.  The rule knows
+ * no chat template: a span is opened by an opener id SEQUENCE (e.g. the three ids of <|header_start|>assistant<|header_end|>)
+ * and closed by a closer ID (e.g. <|eot|>, <|eom|>).
+ *
+ * Per document [a, z) = [tok_offsets[d], tok_offsets[d + 1]):
+ *   open event at q    some opener o of length k has ids[q-k+1 .. q] == o with q-k+1 >= a (a match never reaches across a
+ *                      document start);
+ *   close event at q   ids[q] is a closer.  No opener may contain a closer, so no position is both kinds of event;
+ *   inside(i), a <= i <= z: the last event at a position in [a, i) is an open event (no event: false);
+ *   trained(i) = inside(i) && (!close(i) || TD_LABELS_TRAIN_CLOSE).
+ * So the header ids are not trained (the opener that starts a span lies in front of it), nor anything outside spans; an opener
+ * while already inside is content; a closer while outside has no effect; a document that ends inside is "unterminated".
+ * This is the obvious sequential two-state walk over every document.
+ *
+ * Outputs:
+ *   labels[i] = trained(i) ? ids[i] : ignore_index                                   (int32, required)
+ *   mask[i] = trained(i)                                                             (uint8, optional)
+ *   trained_offsets[n_docs + 1]: the trained ids in front of every document start, the total last; its differences are the
+ *                                per-document trained counts                         (int64, optional)
+ *   counts[4] = {trained ids, spans (open events at q with !inside(q)), unterminated documents, 0}   (int64, required)
+ * Slots at or above tok_offsets[n_docs] are not written.
+ *
+ * Spec errors are TD_E_INVALID with a message, before any launch: n_open outside 1..8, an open_len outside 1..8, n_close
+ * outside 0..16, a negative spec id, a closer inside an opener, ignore_index outside int32, unknown flags.  Ids in the DATA are
+ * not checked against the vocabulary: a negative or out-of-range id matches nothing. */
+#define TD_LABELS_MAX_OPEN 8      /* opener sequences */
+#define TD_LABELS_MAX_OPEN_LEN 8  /* ids per opener */
+#define TD_LABELS_MAX_CLOSE 16
+#define TD_LABELS_TRAIN_CLOSE 1   /* flags: a closer that ends a span is itself trained (the model must learn to stop) */
+typedef struct td_labels_spec {
+    int64_t n_open;
+    int64_t open_len[TD_LABELS_MAX_OPEN];
+    int32_t open_ids[TD_LABELS_MAX_OPEN][TD_LABELS_MAX_OPEN_LEN];
+    int64_t n_close;
+    int32_t close_ids[TD_LABELS_MAX_CLOSE];
+    int64_t ignore_index; /* any int32, e.g. -100 */
+    int64_t flags;
+} td_labels_spec;
+
+/* Device buffers, asynchronously on hip_stream (never the null stream's work of the library itself; no synchronisation, no
+ * read-back).  d_mask and d_trained_offsets may be NULL.  tok_offsets that do not start at 0, decrease, are negative or end
+ * above n_tokens raise TD_E_INVALID through td_device_status with err_pos = the first such document found; then nothing is
+ * written to any output and no id outside [0, n_tokens) is read. */
+int td_span_labels_device(td_tokenizer* t, const void* d_ids, int64_t n_tokens, const void* d_tok_offsets, int64_t n_docs,
+                          const td_labels_spec* spec, void* d_labels, void* d_mask, void* d_trained_offsets, void* d_counts,
+                          void* hip_stream);
+/* Host buffers, synchronous; tok_offsets are checked like every host entry point's.  mask and trained_offsets may be NULL. */
+int td_span_labels(td_tokenizer* t, const int32_t* ids, int64_t n_tokens, const int64_t* tok_offsets, int64_t n_docs,
+                   const td_labels_spec* spec, int32_t* labels, uint8_t* mask, int64_t* trained_offsets, int64_t* counts);
+/* td_encode_batch_with_special_strs (TD_MODE_ENCODE; the same ids and offsets) and td_span_labels in one call, from chat text
+ * to ids + labels: where the encode leaves its ids on the device they are labelled there.  out_labels (and out_mask) have
+ * room for out_capacity entries.  *n_tokens = ids needed (also on TD_E_CAPACITY).  Synchronous. */
+int td_encode_batch_span_labels(td_tokenizer* t, const uint8_t* text, const int64_t* doc_offsets, int64_t n_docs,
+                                const uint8_t* allowed_bytes, const int64_t* allowed_offsets, int64_t n_allowed,
+                                const td_labels_spec* spec, int32_t* out_tokens, int64_t out_capacity, int64_t* out_offsets,
+                                int32_t* out_labels, uint8_t* out_mask, int64_t* out_trained_offsets, int64_t* counts,
+                                int64_t* n_tokens);
+
 /* Options. */
 #define TD_OPT_LONG_POOL_BYTES 1 /* scratch for pieces longer than 64 bytes (default max(64 MiB, 2 x input)) */
 #define TD_OPT_PROFILE 2         /* 1: bracket the kernels of every td_encode_device call with HIP events on the

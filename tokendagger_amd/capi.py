@@ -59,6 +59,7 @@ EXPORTS = [
     "td_encode_device_with_starts", "td_make_rows_device", "td_make_rows", "td_encode_batch_rows",
     "td_pack_plan", "td_pack_rows", "td_pack_rows_device", "td_encode_batch_pack_rows",
     "td_window_plan", "td_window_rows", "td_window_rows_device", "td_encode_batch_window_rows",
+    "td_span_labels", "td_span_labels_device", "td_encode_batch_span_labels",
 ]
 
 
@@ -137,6 +138,12 @@ def load_library():
     lib.td_window_rows_device.argtypes = [vp, vp, i64, vp, i64, vp, i64, vp, i64, vp, vp]
     lib.td_encode_batch_window_rows.restype = i32
     lib.td_encode_batch_window_rows.argtypes = [vp, vp, vp, i64, i32, vp, i64, vp, i64, vp]
+    lib.td_span_labels_device.restype = i32
+    lib.td_span_labels_device.argtypes = [vp, vp, i64, vp, i64, vp, vp, vp, vp, vp, vp]
+    lib.td_span_labels.restype = i32
+    lib.td_span_labels.argtypes = [vp, vp, i64, vp, i64, vp, vp, vp, vp, vp]
+    lib.td_encode_batch_span_labels.restype = i32
+    lib.td_encode_batch_span_labels.argtypes = [vp, vp, vp, i64, vp, vp, i64, vp, vp, i64, vp, vp, vp, vp, vp, ctypes.POINTER(i64)]
     lib.td_comm_unique_id.restype = i32
     lib.td_comm_unique_id.argtypes = [vp]
     lib.td_comm_create.restype = i32
@@ -307,6 +314,38 @@ def window_plan(tok_offsets, spec: RowsSpec, overlap: int = 0, first_row: bool =
     return (counts, fr) if first_row else counts
 
 
+TD_LABELS_MAX_OPEN, TD_LABELS_MAX_OPEN_LEN, TD_LABELS_MAX_CLOSE, TD_LABELS_TRAIN_CLOSE = 8, 8, 16, 1
+
+
+class LabelsSpec(ctypes.Structure):
+    """td_labels_spec (include/tokendagger_hip.h): opener id sequences, closer ids, ignore_index, flags."""
+    _fields_ = [("n_open", ctypes.c_int64), ("open_len", ctypes.c_int64 * TD_LABELS_MAX_OPEN),
+                ("open_ids", (ctypes.c_int32 * TD_LABELS_MAX_OPEN_LEN) * TD_LABELS_MAX_OPEN), ("n_close", ctypes.c_int64),
+                ("close_ids", ctypes.c_int32 * TD_LABELS_MAX_CLOSE), ("ignore_index", ctypes.c_int64), ("flags", ctypes.c_int64)]
+
+
+def labels_spec(open, close, ignore_index: int = -100, train_close: bool = True) -> LabelsSpec:
+    """open: opener id sequences (at most 8 of at most 8 ids); close: closer ids (at most 16).  What fits the struct is passed
+    on as it is: the library checks the rest (TD_E_INVALID with a message)."""
+    open = [[int(i) for i in o] for o in open]
+    close = [int(c) for c in close]
+    if len(open) > TD_LABELS_MAX_OPEN:
+        raise ValueError(f"{len(open)} openers: a td_labels_spec holds at most {TD_LABELS_MAX_OPEN}")
+    if len(close) > TD_LABELS_MAX_CLOSE:
+        raise ValueError(f"{len(close)} closers: a td_labels_spec holds at most {TD_LABELS_MAX_CLOSE}")
+    sp = LabelsSpec()
+    sp.n_open, sp.n_close, sp.ignore_index, sp.flags = len(open), len(close), int(ignore_index), TD_LABELS_TRAIN_CLOSE if train_close else 0
+    for k, o in enumerate(open):
+        if len(o) > TD_LABELS_MAX_OPEN_LEN:
+            raise ValueError(f"opener {k} has {len(o)} ids: an opener holds at most {TD_LABELS_MAX_OPEN_LEN}")
+        sp.open_len[k] = len(o)
+        for j, i in enumerate(o):
+            sp.open_ids[k][j] = i
+    for k, c in enumerate(close):
+        sp.close_ids[k] = c
+    return sp
+
+
 def _as_u8(data) -> np.ndarray:
     if isinstance(data, np.ndarray):
         return np.ascontiguousarray(data, dtype=np.uint8)
@@ -427,6 +466,15 @@ class HipTokenizer:
             raise TokenDaggerHipError(rc, self._lib.td_last_error(None).decode("utf-8", "replace"))
         self._h = h
 
+    @classmethod
+    def borrow(cls, handle: int) -> "HipTokenizer":
+        """The methods of this class on a td_tokenizer that someone else owns (closing the result does nothing)."""
+        self = cls.__new__(cls)
+        self._lib = load_library()
+        self._h = ctypes.c_void_p(handle)
+        self._borrowed = True
+        return self
+
     def clone(self) -> "HipTokenizer":
         """td_clone: a second handle on the same device tables (own lock, workspace and streams) — one per host thread / HIP
         stream for concurrent encodes.  Either handle may be closed first."""
@@ -442,7 +490,8 @@ class HipTokenizer:
 
     def close(self):
         if getattr(self, "_h", None):
-            self._lib.td_destroy(self._h)
+            if not getattr(self, "_borrowed", False):
+                self._lib.td_destroy(self._h)
             self._h = None
 
     __del__ = close
@@ -685,6 +734,50 @@ class HipTokenizer:
         self._check(self._lib.td_encode_batch_window_rows(self._h, buf.ctypes.data if len(buf) else None, offs.ctypes.data, n_docs, mode,
                                                           ctypes.byref(spec), overlap, ctypes.byref(outs), rows, counts.ctypes.data))
         return self._rows_result("windows", spec, b, counts, n_docs)
+
+    # ---- loss labels (td_labels_spec) ----------------------------------------------------------------------------
+    def span_labels(self, ids, tok_offsets, spec: LabelsSpec, mask: bool = False, trained_offsets: bool = False, n_tokens: int | None = None):
+        """td_span_labels -> (labels int32[total], mask uint8[total] | None, trained_offsets int64[n_docs + 1] | None,
+        counts int64[4] = trained ids, spans, unterminated documents, 0)."""
+        t = np.ascontiguousarray(ids, dtype=np.int32)
+        o = np.ascontiguousarray(tok_offsets, dtype=np.int64)
+        n_docs, total = len(o) - 1, int(o[-1])
+        lab = np.empty(max(total, 1), dtype=np.int32)
+        m = np.empty(max(total, 1), dtype=np.uint8) if mask else None
+        to = np.empty(n_docs + 1, dtype=np.int64) if trained_offsets else None
+        counts = np.zeros(4, dtype=np.int64)
+        self._check(self._lib.td_span_labels(self._h, t.ctypes.data if len(t) else None, len(t) if n_tokens is None else n_tokens, o.ctypes.data,
+                                             n_docs, ctypes.byref(spec), lab.ctypes.data, m.ctypes.data if mask else None,
+                                             to.ctypes.data if trained_offsets else None, counts.ctypes.data))
+        return lab[:total], m[:total] if mask else None, to, counts
+
+    def span_labels_device(self, d_ids: int, n_tokens: int, d_tok_offsets: int, n_docs: int, spec: LabelsSpec, d_labels: int, d_mask: int = 0,
+                           d_trained_offsets: int = 0, d_counts: int = 0, stream: int = 0):
+        """td_span_labels_device: raw device pointers, asynchronous on `stream`; check with device_status(stream)."""
+        self._check(self._lib.td_span_labels_device(self._h, d_ids or None, n_tokens, d_tok_offsets, n_docs, ctypes.byref(spec), d_labels or None,
+                                                    d_mask or None, d_trained_offsets or None, d_counts or None, stream or None))
+
+    def encode_batch_span_labels(self, text, doc_offsets, allowed, spec: LabelsSpec, mask: bool = False, trained_offsets: bool = False):
+        """td_encode_batch_span_labels: encode_batch_with_special_strs + span_labels in one call ->
+        (tokens int32[total], offsets int64[n_docs + 1], labels, mask | None, trained_offsets | None, counts)."""
+        buf = _as_u8(text)
+        offs = np.ascontiguousarray(doc_offsets, dtype=np.int64)
+        ab, ao = self._pack_strs(list(allowed))
+        n_docs = len(offs) - 1
+        n = int(offs[-1]) if len(offs) else 0
+        cap = n + 16
+        out_offs = np.empty(n_docs + 1, dtype=np.int64)
+        toks, lab = np.empty(cap, dtype=np.int32), np.empty(cap, dtype=np.int32)
+        m = np.empty(cap, dtype=np.uint8) if mask else None
+        to = np.empty(n_docs + 1, dtype=np.int64) if trained_offsets else None
+        counts = np.zeros(4, dtype=np.int64)
+        ntok = ctypes.c_int64(0)
+        self._check(self._lib.td_encode_batch_span_labels(self._h, buf.ctypes.data if n else None, offs.ctypes.data, n_docs, ab.ctypes.data,
+                                                          ao.ctypes.data, len(ao) - 1, ctypes.byref(spec), toks.ctypes.data, cap,
+                                                          out_offs.ctypes.data, lab.ctypes.data, m.ctypes.data if mask else None,
+                                                          to.ctypes.data if trained_offsets else None, counts.ctypes.data, ctypes.byref(ntok)))
+        k = ntok.value
+        return toks[:k].copy(), out_offs, lab[:k].copy(), m[:k].copy() if mask else None, to, counts
 
     def device_status_pos(self, stream: int = 0) -> tuple[int, int]:
         """td_device_status without raising: (code, err_pos)."""

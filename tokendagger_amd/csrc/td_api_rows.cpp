@@ -209,8 +209,10 @@ int rows_capacity_fail(td_tokenizer* t, int64_t rows, int64_t* counts) {
 }
 
 
-// td_make_rows, td_pack_rows, td_window_rows: the checks of the caller's ids and offsets (nothing allocated, nothing enqueued) ...
-int rows_check_host_ids(td_tokenizer* t, const int32_t* ids, int64_t n_tokens, const int64_t* tok_offsets, int64_t n_docs) {
+}  // namespace
+
+// td_make_rows, td_pack_rows, td_window_rows, td_span_labels: the checks of the caller's ids and offsets (nothing allocated, nothing enqueued) ...
+int td::rows_check_host_ids(td_tokenizer* t, const int32_t* ids, int64_t n_tokens, const int64_t* tok_offsets, int64_t n_docs) {
     int rc;
     if ((rc = check_offsets(t, "tok_offsets", tok_offsets, n_docs, ids))) return rc;
     if (tok_offsets[n_docs] > n_tokens) { t->err = "tok_offsets[n_docs] exceeds n_tokens"; return TD_E_INVALID; }
@@ -218,7 +220,7 @@ int rows_check_host_ids(td_tokenizer* t, const int32_t* ids, int64_t n_tokens, c
 }
 
 // ... and their upload into dec_tokens / d_offsets on the handle's own stream `s`.
-int rows_stage_host_ids(td_tokenizer* t, const int32_t* ids, const int64_t* tok_offsets, int64_t n_docs, hipStream_t& s) {
+int td::rows_stage_host_ids(td_tokenizer* t, const int32_t* ids, const int64_t* tok_offsets, int64_t n_docs, hipStream_t& s) {
     int rc;
     const int64_t total = tok_offsets[n_docs];
     if ((rc = ensure(t, t->dec_tokens, (size_t)std::max<int64_t>(total, 1) * 4))) return rc;
@@ -230,6 +232,8 @@ int rows_stage_host_ids(td_tokenizer* t, const int32_t* ids, const int64_t* tok_
     HIP_TRY(t, hipMemcpyAsync(t->d_offsets.p, tok_offsets, (size_t)(n_docs + 1) * 8, hipMemcpyHostToDevice, s));
     return TD_OK;
 }
+
+namespace {
 
 // td_encode_batch_rows, _pack_rows, _window_rows: the documents encoded on the handle's own stream `s` into d_tokens (room for
 // dev_cap ids) / d_offsets, and the encode's errors returned as such, before the rows read its ids.

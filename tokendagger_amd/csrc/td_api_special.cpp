@@ -269,6 +269,7 @@ int encode_special_locked(td_tokenizer* t, const uint8_t* text, const int64_t* d
             if (rc == TD_OK) {
                 if ((rc = copy_wait(t, out_offsets, t->d_offsets.p, (size_t)(n_docs + 1) * 8, hipMemcpyDeviceToHost, s))) return rc;
                 const int64_t total = out_offsets[n_docs];
+                t->enc_resident = true;
                 return deliver_ids(t, total, out_capacity, out_tokens, n_tokens,
                                    [&] { return copy_wait(t, out_tokens, t->d_tokens.p, (size_t)total * 4, hipMemcpyDeviceToHost, s); });
             }
@@ -451,6 +452,14 @@ int32_t last_piece_token_len_host(td_tokenizer* t, const uint8_t* text, int64_t 
 
 const int64_t no_offs[1] = {0};  // allowed_offsets of an empty allowed set
 
+int td::encode_special_strs_locked(td_tokenizer* t, const uint8_t* text, const int64_t* doc_offsets, int64_t n_docs,
+                                   const uint8_t* allowed_bytes, const int64_t* allowed_offsets, int64_t n_allowed, int32_t* out_tokens,
+                                   int64_t out_capacity, int64_t* out_offsets, int64_t* n_tokens) {
+    t->enc_resident = false;
+    return encode_special_locked(t, text, doc_offsets, n_docs, allowed_bytes, n_allowed ? allowed_offsets : no_offs, nullptr, n_allowed,
+                                 out_tokens, out_capacity, out_offsets, n_tokens, nullptr, nullptr);
+}
+
 extern "C" {
 
 int td_encode_device_with_special(td_tokenizer* t, const void* d_text, int64_t n_bytes, const void* d_doc_offsets, int64_t n_docs,
@@ -492,8 +501,8 @@ int td_encode_batch_with_special_strs(td_tokenizer* t, const uint8_t* text, cons
         out_capacity < 0)
         return TD_E_INVALID;
     return locked(t, [&] {
-        return encode_special_locked(t, text, doc_offsets, n_docs, allowed_bytes, n_allowed ? allowed_offsets : no_offs, nullptr, n_allowed,
-                                     out_tokens, out_capacity, out_offsets, n_tokens, nullptr, nullptr);
+        return encode_special_strs_locked(t, text, doc_offsets, n_docs, allowed_bytes, allowed_offsets, n_allowed, out_tokens, out_capacity,
+                                          out_offsets, n_tokens);
     });
 }
 

@@ -246,6 +246,9 @@ struct td_tokenizer {
     // window rows (td_windows.hip): the scan words and first_row, the host entry points' per-row outputs on the device
     DevBuf win_scan, win_first, win_len, win_docs, win_starts;
     bool rows_last = false;  // the last call launched the rows kernels (the unit of a TD_E_CAPACITY position)
+    // loss labels (td_labels.hip): the counts and flags, the document-start bitmap, the tiles' events / states, their trained ids
+    // and the lanes' (trained_offsets only); the host entry points' outputs on the device
+    DevBuf lab_head, lab_bits, lab_tiles, lab_cnt, lab_aux, lab_out, lab_mask, lab_toff, lab_counts;
     // best-fit packing (td_pack.hip): the items, the sort's and the scan's scratch, the header + runs read back, the plan uploaded,
     // the segments; the host entry points' row lengths and segment documents on the device
     DevBuf pack_key, pack_val, pack_key2, pack_val2, pack_full, pack_pref, pack_tmp, pack_hdr, pack_plan, pack_seg, pack_len, pack_docs;
@@ -270,6 +273,7 @@ struct td_tokenizer {
     DevBuf sp_bytes, sp_off, sp_len, sp_id, sp_parent, sp_first2, sp_hit, sp_acc, sp_cpos, sp_clit, sp_ccount;
     uint32_t sp_n = 0, sp_maxlen = 0;
     bool sp_active = false;          // this call cuts allowed specials (set around encode_device_locked)
+    bool enc_resident = false;       // the last encode_special_strs_locked left the ids and offsets it returned in d_tokens / d_offsets too
     // generic patterns with left-context assertions behind special cuts: per document of the NEXT host batch, the bytes at its
     // start that are context only (set around encode_batch_locked by encode_special_locked)
     const uint8_t* gx_prefix_host = nullptr;
@@ -347,7 +351,16 @@ int absorb_ctl(td_tokenizer* t, Ctl c, hipStream_t stream, int64_t* err_pos);
 int device_status_locked(td_tokenizer* t, hipStream_t stream, int64_t* err_pos);
 int encode_batch_locked(td_tokenizer* t, const uint8_t* text, const int64_t* doc_offsets, int64_t n_docs, int mode, int32_t* out_tokens,
                         int64_t out_capacity, int64_t* out_offsets, int64_t* n_tokens, int unit = TD_UNIT_BYTES, int64_t* out_starts = nullptr);
+// ---- defined in td_api_special.cpp --------------------------------------------------------------------------------------------------
+// td_encode_batch_with_special_strs under the caller's lock; sets t->enc_resident.
+int encode_special_strs_locked(td_tokenizer* t, const uint8_t* text, const int64_t* doc_offsets, int64_t n_docs, const uint8_t* allowed_bytes,
+                               const int64_t* allowed_offsets, int64_t n_allowed, int32_t* out_tokens, int64_t out_capacity,
+                               int64_t* out_offsets, int64_t* n_tokens);
 // ---- defined in td_api_rows.cpp -----------------------------------------------------------------------------------------------------
+// The checks of a caller's host ids and offsets (nothing allocated, nothing enqueued), and their upload into dec_tokens / d_offsets
+// on the handle's own stream, which `s` becomes.
+int rows_check_host_ids(td_tokenizer* t, const int32_t* ids, int64_t n_tokens, const int64_t* tok_offsets, int64_t n_docs);
+int rows_stage_host_ids(td_tokenizer* t, const int32_t* ids, const int64_t* tok_offsets, int64_t n_docs, hipStream_t& s);
 int encode_starts_locked(td_tokenizer* t, const void* d_text, int64_t n, const void* d_offs, int64_t n_docs, const void* d_tokens, int64_t cap,
                          const void* d_out_offs, int unit, void* d_starts, hipStream_t stream);
 

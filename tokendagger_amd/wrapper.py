@@ -56,6 +56,17 @@ class WindowRows(NamedTuple):
     counts: np.ndarray              # int64 [4]: rows, real slots, documents with more than one window, the most windows of one
 
 
+class Labels(NamedTuple):
+    """Loss labels for marked id spans (Tokenizer.ids_to_labels / encode_batch_to_labels; the contract:
+    include/tokendagger_hip.h, td_labels_spec)."""
+    ids: np.ndarray                     # int32 [total]
+    tok_offsets: np.ndarray             # int64 [n_docs + 1]
+    labels: np.ndarray                  # int32 [total]: the id where the loss applies, ignore_index elsewhere
+    mask: np.ndarray | None             # uint8 [total]: 1 where the loss applies
+    trained_offsets: np.ndarray | None  # int64 [n_docs + 1]: trained ids in front of every document, the total last
+    counts: np.ndarray                  # int64 [4]: trained ids, spans, unterminated documents, 0
+
+
 class TokenDaggerError(Exception):
     """Base exception for TokenDagger errors (reference: wrapper.py:23-25)."""
 
@@ -409,6 +420,54 @@ class Tokenizer:
         except Exception as ex:
             raise TokenDaggerError(f"Encoding failed: {ex}")
         return self._windows(r, no_pad)
+
+    # ------------------------------------------------------------------ loss labels ------------
+    # labels[i] = ids[i] inside a span, ignore_index elsewhere.  A span starts behind an opener (a string, encoded once with every
+    # special token allowed, or a list of ids: at most 8 openers of at most 8 ids) and ends with a closer (a special-token string
+    # or an id: at most 16), which is trained itself unless train_close=False.  For Llama-4 chat data:
+    # open=["<|header_start|>assistant<|header_end|>"], close=["<|eot|>", "<|eom|>"].  Rows of labels: ids_to_rows /
+    # ids_to_packed_rows / ids_to_window_rows on `labels` with the same tok_offsets, pad=ignore_index and no bos / eos.
+    def _labels_spec(self, open, close, ignore_index: int, train_close: bool):
+        hip = _capi.HipTokenizer.borrow(self._core_bpe.handle())
+        openers = []
+        for o in open:
+            if isinstance(o, (str, bytes)):
+                text = o if isinstance(o, str) else bytes(o).decode("utf-8")
+                ids = [int(i) for i in hip.encode_with_special_strs(text.encode("utf-8"), list(self._special_tokens))[0]]
+                if len(ids) > _capi.TD_LABELS_MAX_OPEN_LEN:
+                    raise ValueError(f"opener {o!r} encodes to {len(ids)} ids: an opener holds at most {_capi.TD_LABELS_MAX_OPEN_LEN}")
+                if not ids:
+                    raise ValueError("an opener must not be empty")
+                openers.append(ids)
+            else:
+                openers.append([int(i) for i in o])
+        closers = [self.encode_single_token(c) if isinstance(c, (str, bytes)) else int(c) for c in close]
+        return hip, _capi.labels_spec(openers, closers, ignore_index, train_close)
+
+    def ids_to_labels(self, ids: np.ndarray, tok_offsets: np.ndarray, *, open, close, ignore_index: int = -100, train_close: bool = True,
+                      mask: bool = False, trained_offsets: bool = False) -> Labels:
+        """Loss labels from ids already encoded (int32 ids + int64 per-document token offsets)."""
+        hip, spec = self._labels_spec(open, close, ignore_index, train_close)
+        ids = np.ascontiguousarray(ids, dtype=np.int32)
+        offs = np.ascontiguousarray(tok_offsets, dtype=np.int64)
+        try:
+            lab, m, to, counts = hip.span_labels(ids, offs, spec, mask=mask, trained_offsets=trained_offsets)
+        except _capi.TokenDaggerHipError as ex:
+            raise TokenDaggerError(f"Making labels failed: {ex}")
+        return Labels(ids[:len(lab)], offs, lab, m, to, counts)
+
+    def encode_batch_to_labels(self, text: np.ndarray | bytes, offsets: np.ndarray, *, allowed_special: Literal["all"] | AbstractSet[str] = "all",
+                               open, close, ignore_index: int = -100, train_close: bool = True, mask: bool = False,
+                               trained_offsets: bool = False) -> Labels:
+        """Chat text straight to ids + labels (one call): the allowed special tokens are cut out, the ids labelled on the device."""
+        hip, spec = self._labels_spec(open, close, ignore_index, train_close)
+        allowed = sorted(self._special_tokens) if allowed_special == "all" else sorted(allowed_special)
+        buf = np.frombuffer(text, dtype=np.uint8) if isinstance(text, (bytes, bytearray)) else text
+        try:
+            return Labels(*hip.encode_batch_span_labels(buf, np.asarray(offsets, dtype=np.int64), allowed, spec, mask=mask,
+                                                        trained_offsets=trained_offsets))
+        except _capi.TokenDaggerHipError as ex:
+            raise TokenDaggerError(f"Encoding failed: {ex}")
 
     # ------------------------------------------------------------------ decoding ---------------
     def decode_bytes(self, tokens: Sequence[int]) -> bytes:
