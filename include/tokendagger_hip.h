@@ -390,6 +390,50 @@ int td_encode_batch_window_rows(td_tokenizer* t, const uint8_t* text, const int6
                                 const td_rows_spec* spec, int64_t overlap, const td_window_outputs* host_out, int64_t rows_capacity,
                                 int64_t* counts);
 
+/* ---- label rows: a second stream placed beside the ids, in every row layout (td_*_labeled) -------------------------------------
+ * A LABEL STREAM is a second int32 array src[n_tokens], index-aligned with ids (e.g. the labels of td_span_labels*).  The labeled
+ * form of a row entry point places it by the very same placement as the ids into dst[rows_capacity * S], in the same pass: the
+ * slot kernels resolve every slot's source index once and move both streams.  For every layout:
+ *   a slot whose id row holds body id ids[i] holds src[i];
+ *   a slot that holds the inserted BOS holds bos_value, the inserted EOS eos_value, a pad slot pad_value (any int32 each);
+ *   with TD_ROWLAB_MASK_OVERLAP (TD_ROWS_WINDOWS only), body slot j < overlap of a window k > 0 holds pad_value instead of src[i]:
+ *   these are the ids the window repeats, so every id of a document is trained in exactly one row.
+ * Values in src are data: any int32, never checked.  src and dst are host or device memory, as the entry point's ids and out ids.
+ * Spec errors are TD_E_INVALID with a message, before any launch and behind the counterpart's own argument checks: a value
+ * outside int32, unknown flags, TD_ROWLAB_MASK_OVERLAP on another layout, src or dst NULL.
+ * Each labeled entry point has the signature of its counterpart plus a trailing td_rows_labels.  Every other output equals the
+ * counterpart's byte for byte; error codes, err_pos, the order of the checks and the synchronisation are the counterpart's
+ * (td_pack_rows_labeled_device synchronises once, the other device forms not at all); where the counterpart writes nothing on an
+ * error (capacity, bad offsets), nothing is written to dst either.
+ * Without BOS / EOS, dst is what the counterpart makes of src in place of ids with pad_id = pad_value. */
+#define TD_ROWLAB_MASK_OVERLAP 1   /* TD_ROWS_WINDOWS only */
+typedef struct td_rows_labels {
+    const int32_t* src;   /* host or device memory, as the entry point's ids */
+    int32_t* dst;         /* like the entry point's out ids */
+    int64_t bos_value;    /* any int32: what dst holds where the id row holds the inserted BOS */
+    int64_t eos_value;    /* ... the inserted EOS */
+    int64_t pad_value;    /* ... a pad slot */
+    int64_t flags;
+} td_rows_labels;
+int td_make_rows_labeled(td_tokenizer* t, const int32_t* ids, int64_t n_tokens, const int64_t* tok_offsets, int64_t n_docs,
+                         const td_rows_spec* spec, int32_t* out_ids, int64_t rows_capacity, int32_t* out_positions, int32_t* out_aux,
+                         int64_t* counts, const td_rows_labels* lab);
+int td_make_rows_labeled_device(td_tokenizer* t, const void* d_ids, int64_t n_tokens, const void* d_tok_offsets, int64_t n_docs,
+                                const td_rows_spec* spec, void* d_out_ids, int64_t rows_capacity, void* d_positions, void* d_aux,
+                                void* d_counts, void* hip_stream, const td_rows_labels* lab);
+int td_pack_rows_labeled(td_tokenizer* t, const int32_t* ids, int64_t n_tokens, const int64_t* tok_offsets, int64_t n_docs,
+                         const td_rows_spec* spec, const td_pack_outputs* host_out, int64_t rows_capacity, int64_t* counts,
+                         const td_rows_labels* lab);
+int td_pack_rows_labeled_device(td_tokenizer* t, const void* d_ids, int64_t n_tokens, const void* d_tok_offsets, int64_t n_docs,
+                                const td_rows_spec* spec, const td_pack_outputs* dev_out, int64_t rows_capacity, int64_t* counts,
+                                void* hip_stream, const td_rows_labels* lab);
+int td_window_rows_labeled(td_tokenizer* t, const int32_t* ids, int64_t n_tokens, const int64_t* tok_offsets, int64_t n_docs,
+                           const td_rows_spec* spec, int64_t overlap, const td_window_outputs* host_out, int64_t rows_capacity,
+                           int64_t* counts, const td_rows_labels* lab);
+int td_window_rows_labeled_device(td_tokenizer* t, const void* d_ids, int64_t n_tokens, const void* d_tok_offsets, int64_t n_docs,
+                                  const td_rows_spec* spec, int64_t overlap, const td_window_outputs* dev_out, int64_t rows_capacity,
+                                  void* d_counts, void* hip_stream, const td_rows_labels* lab);
+
 /* ---- loss labels: train only inside marked id spans (td_labels.hip) ----------------------------------------------------------
  * ids + per-document token offsets -> labels[i] = ids[i] where the loss applies, ignore_index everywhere else.  The rule knows
  * no chat template: a span is opened by an opener id SEQUENCE (e.g. the three ids of <|header_start|>assistant<|header_end|>)
@@ -448,6 +492,28 @@ int td_encode_batch_span_labels(td_tokenizer* t, const uint8_t* text, const int6
                                 const td_labels_spec* spec, int32_t* out_tokens, int64_t out_capacity, int64_t* out_offsets,
                                 int32_t* out_labels, uint8_t* out_mask, int64_t* out_trained_offsets, int64_t* counts,
                                 int64_t* n_tokens);
+
+/* From chat text to trainer-ready (input_ids, labels) rows in one call: td_encode_batch_span_labels followed by the labeled row
+ * call of rspec->layout (td_make_rows_labeled / td_pack_rows_labeled / td_window_rows_labeled; overlap: TD_ROWS_WINDOWS), with the
+ * labels as the label stream.  Ids and labels stay on the device between the steps.  lab gives bos_value, eos_value, pad_value
+ * and flags; its src and dst are ignored.  host_out: fields that the layout does not have must be NULL (TD_E_INVALID).
+ * row_counts[4] are the row call's counts (also on TD_E_CAPACITY: [0] = the rows needed), label_counts[4] the labels'.
+ * Synchronous. */
+typedef struct td_label_rows_outputs {
+    int32_t* ids;          /* int32 [rows * S] */
+    int32_t* labels;       /* int32 [rows * S] */
+    int32_t* positions;    /* optional */
+    int32_t* aux;          /* optional: CONCAT cu_seqlens / PAD lengths / BESTFIT cu_seqlens */
+    int32_t* row_lengths;  /* optional: BESTFIT, WINDOWS */
+    int64_t* seg_docs;     /* optional: BESTFIT */
+    int64_t* row_docs;     /* optional: WINDOWS */
+    int64_t* row_starts;   /* optional: WINDOWS */
+} td_label_rows_outputs;
+int td_encode_batch_span_label_rows(td_tokenizer* t, const uint8_t* text, const int64_t* doc_offsets, int64_t n_docs,
+                                    const uint8_t* allowed_bytes, const int64_t* allowed_offsets, int64_t n_allowed,
+                                    const td_labels_spec* lspec, const td_rows_spec* rspec, int64_t overlap, const td_rows_labels* lab,
+                                    const td_label_rows_outputs* host_out, int64_t rows_capacity, int64_t* row_counts,
+                                    int64_t* label_counts);
 
 /* Options. */
 #define TD_OPT_LONG_POOL_BYTES 1 /* scratch for pieces longer than 64 bytes (default max(64 MiB, 2 x input)) */

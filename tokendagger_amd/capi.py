@@ -60,6 +60,8 @@ EXPORTS = [
     "td_pack_plan", "td_pack_rows", "td_pack_rows_device", "td_encode_batch_pack_rows",
     "td_window_plan", "td_window_rows", "td_window_rows_device", "td_encode_batch_window_rows",
     "td_span_labels", "td_span_labels_device", "td_encode_batch_span_labels",
+    "td_make_rows_labeled", "td_make_rows_labeled_device", "td_pack_rows_labeled", "td_pack_rows_labeled_device",
+    "td_window_rows_labeled", "td_window_rows_labeled_device", "td_encode_batch_span_label_rows",
 ]
 
 
@@ -144,6 +146,13 @@ def load_library():
     lib.td_span_labels.argtypes = [vp, vp, i64, vp, i64, vp, vp, vp, vp, vp]
     lib.td_encode_batch_span_labels.restype = i32
     lib.td_encode_batch_span_labels.argtypes = [vp, vp, vp, i64, vp, vp, i64, vp, vp, i64, vp, vp, vp, vp, vp, ctypes.POINTER(i64)]
+    for fn, base in (("td_make_rows_labeled", lib.td_make_rows), ("td_make_rows_labeled_device", lib.td_make_rows_device),
+                     ("td_pack_rows_labeled", lib.td_pack_rows), ("td_pack_rows_labeled_device", lib.td_pack_rows_device),
+                     ("td_window_rows_labeled", lib.td_window_rows), ("td_window_rows_labeled_device", lib.td_window_rows_device)):
+        getattr(lib, fn).restype = i32
+        getattr(lib, fn).argtypes = [*base.argtypes, vp]  # (the counterpart's signature and a trailing td_rows_labels)
+    lib.td_encode_batch_span_label_rows.restype = i32
+    lib.td_encode_batch_span_label_rows.argtypes = [vp, vp, vp, i64, vp, vp, i64, vp, vp, i64, vp, vp, i64, vp, vp]
     lib.td_comm_unique_id.restype = i32
     lib.td_comm_unique_id.argtypes = [vp]
     lib.td_comm_create.restype = i32
@@ -312,6 +321,28 @@ def window_plan(tok_offsets, spec: RowsSpec, overlap: int = 0, first_row: bool =
     if rc != TD_OK:
         raise TokenDaggerHipError(rc, "td_window_plan: invalid spec, overlap or tok_offsets")
     return (counts, fr) if first_row else counts
+
+
+TD_ROWLAB_MASK_OVERLAP = 1
+
+
+class RowsLabels(ctypes.Structure):
+    """td_rows_labels (include/tokendagger_hip.h): the label stream of a labeled row call.  src / dst are addresses."""
+    _fields_ = [("src", ctypes.c_void_p), ("dst", ctypes.c_void_p), ("bos_value", ctypes.c_int64), ("eos_value", ctypes.c_int64),
+                ("pad_value", ctypes.c_int64), ("flags", ctypes.c_int64)]
+
+
+def rows_labels(src: int = 0, dst: int = 0, bos_value: int = -100, eos_value: int = -100, pad_value: int = -100,
+                mask_overlap: bool = False, flags: int | None = None) -> RowsLabels:
+    """src / dst: raw addresses (0: NULL); flags: given as they are when not None (the library checks them)."""
+    return RowsLabels(src or None, dst or None, bos_value, eos_value, pad_value,
+                      flags if flags is not None else (TD_ROWLAB_MASK_OVERLAP if mask_overlap else 0))
+
+
+class LabelRowsOutputs(ctypes.Structure):
+    """td_label_rows_outputs (include/tokendagger_hip.h): addresses, None for an output not wanted or not of the layout."""
+    _fields_ = [("ids", ctypes.c_void_p), ("labels", ctypes.c_void_p), ("positions", ctypes.c_void_p), ("aux", ctypes.c_void_p),
+                ("row_lengths", ctypes.c_void_p), ("seg_docs", ctypes.c_void_p), ("row_docs", ctypes.c_void_p), ("row_starts", ctypes.c_void_p)]
 
 
 TD_LABELS_MAX_OPEN, TD_LABELS_MAX_OPEN_LEN, TD_LABELS_MAX_CLOSE, TD_LABELS_TRAIN_CLOSE = 8, 8, 16, 1
@@ -778,6 +809,125 @@ class HipTokenizer:
                                                           to.ctypes.data if trained_offsets else None, counts.ctypes.data, ctypes.byref(ntok)))
         k = ntok.value
         return toks[:k].copy(), out_offs, lab[:k].copy(), m[:k].copy() if mask else None, to, counts
+
+    # ---- label rows (td_rows_labels): the labeled form of the row calls ---------------------------------------------
+    def _check_counts(self, rc: int, counts):
+        try:
+            self._check(rc)
+        except TokenDaggerHipError as ex:
+            ex.counts = counts  # (TD_E_CAPACITY: counts[0] = the rows needed)
+            raise
+
+    def _labeled_host(self, kind: str, fn, ids, labels, tok_offsets, spec: RowsSpec, lab: RowsLabels, rows: int, want, extra=()):
+        """A labeled host call: the result tuple of the counterpart, then the label rows int32[rows, S].  lab gives the fill values
+        and the flags; its src / dst are set here."""
+        t = np.ascontiguousarray(ids, dtype=np.int32)
+        src = np.ascontiguousarray(labels, dtype=np.int32)
+        o = np.ascontiguousarray(tok_offsets, dtype=np.int64)
+        n_docs = len(o) - 1
+        if len(src) < len(t):
+            raise ValueError("labels must have an entry for every id")
+        b, addr, counts = self._rows_buffers(kind, spec, rows, n_docs, *want)
+        dst = np.empty(max(rows * spec.seq_len, 1), dtype=np.int32)
+        lab = RowsLabels((src if len(src) else np.zeros(1, np.int32)).ctypes.data, dst.ctypes.data, lab.bos_value, lab.eos_value,
+                         lab.pad_value, lab.flags)
+        outs = {"rows": None, "pack": PackOutputs, "windows": WindowOutputs}[kind]
+        head = (self._h, t.ctypes.data if len(t) else None, len(t), o.ctypes.data, n_docs, ctypes.byref(spec))
+        if outs is None:
+            rc = fn(*head, addr[0], rows, addr[1], addr[2], counts.ctypes.data, ctypes.byref(lab))
+        else:
+            rc = fn(*head, *extra, ctypes.byref(outs(*addr)), rows, counts.ctypes.data, ctypes.byref(lab))
+        self._check_counts(rc, counts)
+        r = int(counts[0])
+        return (*self._rows_result(kind, spec, b, counts, n_docs), dst[:r * spec.seq_len].reshape(r, spec.seq_len).copy())
+
+    def make_rows_labeled(self, ids, labels, tok_offsets, spec: RowsSpec, lab: RowsLabels, positions: bool = False, aux: bool = True,
+                          rows_capacity: int | None = None):
+        """td_make_rows_labeled -> make_rows' tuple (ids, positions, aux, counts) and the label rows int32[rows, S]."""
+        o = np.asarray(tok_offsets, dtype=np.int64)
+        rows = rows_capacity if rows_capacity is not None else rows_capacity_of(spec, int(o[-1]) if len(o) else 0, len(o) - 1)
+        return self._labeled_host("rows", self._lib.td_make_rows_labeled, ids, labels, o, spec, lab, rows, (positions, aux))
+
+    def pack_rows_labeled(self, ids, labels, tok_offsets, spec: RowsSpec, lab: RowsLabels, positions: bool = False, cu_seqlens: bool = True,
+                          lengths: bool = False, docs: bool = False, rows_capacity: int | None = None):
+        """td_pack_rows_labeled -> pack_rows' tuple and the label rows int32[rows, S]."""
+        o = np.ascontiguousarray(tok_offsets, dtype=np.int64)
+        rows = rows_capacity if rows_capacity is not None else int(pack_plan(o, spec)[0])
+        return self._labeled_host("pack", self._lib.td_pack_rows_labeled, ids, labels, o, spec, lab, rows, (positions, cu_seqlens, lengths, docs))
+
+    def window_rows_labeled(self, ids, labels, tok_offsets, spec: RowsSpec, lab: RowsLabels, overlap: int = 0, positions: bool = False,
+                            lengths: bool = True, docs: bool = True, starts: bool = True, rows_capacity: int | None = None):
+        """td_window_rows_labeled -> window_rows' tuple and the label rows int32[rows, S]."""
+        o = np.ascontiguousarray(tok_offsets, dtype=np.int64)
+        rows = rows_capacity if rows_capacity is not None else int(window_plan(o, spec, overlap)[0])
+        return self._labeled_host("windows", self._lib.td_window_rows_labeled, ids, labels, o, spec, lab, rows,
+                                  (positions, lengths, docs, starts), extra=(overlap,))
+
+    def make_rows_labeled_device(self, d_ids: int, n_tokens: int, d_tok_offsets: int, n_docs: int, spec: RowsSpec, d_out_ids: int,
+                                 rows_capacity: int, lab: RowsLabels, d_positions: int = 0, d_aux: int = 0, d_counts: int = 0, stream: int = 0):
+        """td_make_rows_labeled_device: raw device pointers (lab.src / lab.dst too), asynchronous on `stream`."""
+        self._check(self._lib.td_make_rows_labeled_device(self._h, d_ids or None, n_tokens, d_tok_offsets, n_docs, ctypes.byref(spec),
+                                                          d_out_ids or None, rows_capacity, d_positions or None, d_aux or None,
+                                                          d_counts or None, stream or None, ctypes.byref(lab)))
+
+    def pack_rows_labeled_device(self, d_ids: int, n_tokens: int, d_tok_offsets: int, n_docs: int, spec: RowsSpec, d_out_ids: int,
+                                 rows_capacity: int, lab: RowsLabels, d_positions: int = 0, d_cu_seqlens: int = 0, d_row_lengths: int = 0,
+                                 d_seg_docs: int = 0, stream: int = 0) -> np.ndarray:
+        """td_pack_rows_labeled_device: raw device pointers; synchronises once on `stream` to plan; returns counts int64[4]."""
+        outs = PackOutputs(d_out_ids or None, d_positions or None, d_cu_seqlens or None, d_row_lengths or None, d_seg_docs or None)
+        counts = np.zeros(4, dtype=np.int64)
+        rc = self._lib.td_pack_rows_labeled_device(self._h, d_ids or None, n_tokens, d_tok_offsets, n_docs, ctypes.byref(spec),
+                                                   ctypes.byref(outs), rows_capacity, counts.ctypes.data, stream or None, ctypes.byref(lab))
+        self._check_counts(rc, counts)
+        return counts
+
+    def window_rows_labeled_device(self, d_ids: int, n_tokens: int, d_tok_offsets: int, n_docs: int, spec: RowsSpec, overlap: int,
+                                   d_out_ids: int, rows_capacity: int, lab: RowsLabels, d_positions: int = 0, d_row_lengths: int = 0,
+                                   d_row_docs: int = 0, d_row_starts: int = 0, d_counts: int = 0, stream: int = 0):
+        """td_window_rows_labeled_device: raw device pointers (lab.src / lab.dst too), asynchronous on `stream`."""
+        outs = WindowOutputs(d_out_ids or None, d_positions or None, d_row_lengths or None, d_row_docs or None, d_row_starts or None)
+        self._check(self._lib.td_window_rows_labeled_device(self._h, d_ids or None, n_tokens, d_tok_offsets, n_docs, ctypes.byref(spec),
+                                                            overlap, ctypes.byref(outs), rows_capacity, d_counts or None, stream or None,
+                                                            ctypes.byref(lab)))
+
+    def encode_batch_span_label_rows(self, text, doc_offsets, allowed, lspec: LabelsSpec, rspec: RowsSpec, lab: RowsLabels, overlap: int = 0,
+                                     positions: bool = False, aux: bool = True, lengths: bool = True, docs: bool = True, starts: bool = True,
+                                     rows_capacity: int | None = None):
+        """td_encode_batch_span_label_rows: chat text -> the layout's result tuple (as make_rows / pack_rows / window_rows give it,
+        counts = the row counts), then the label rows int32[rows, S] and the labels' counts int64[4].  The default capacity is the
+        most rows the text can need (one id per byte)."""
+        buf = _as_u8(text)
+        offs = np.ascontiguousarray(doc_offsets, dtype=np.int64)
+        ab, ao = self._pack_strs(list(allowed))
+        n_docs = len(offs) - 1
+        n = int(offs[-1]) if len(offs) else 0
+        lay, S = rspec.layout, rspec.seq_len
+        k = (rspec.bos_id >= 0) + (rspec.eos_id >= 0)
+        if rows_capacity is not None:
+            rows = rows_capacity
+        elif lay == TD_ROWS_BESTFIT:
+            rows = pack_rows_capacity_of(rspec, n, n_docs)
+            if aux:
+                rows = min(rows, ((1 << 31) - 1) // max(S, 1))
+        elif lay == TD_ROWS_WINDOWS:
+            rows = n_docs + n // max(S - k - overlap, 1)
+        else:
+            rows = rows_capacity_of(rspec, n, n_docs)
+        kind = {TD_ROWS_BESTFIT: "pack", TD_ROWS_WINDOWS: "windows"}.get(lay, "rows")
+        want = {"rows": (positions, aux), "pack": (positions, aux, lengths, docs), "windows": (positions, lengths, docs, starts)}[kind]
+        b, addr, counts = self._rows_buffers(kind, rspec, rows, n_docs, *want)
+        dst = np.empty(max(rows * S, 1), dtype=np.int32)
+        none = None
+        outs = {"rows": lambda: LabelRowsOutputs(addr[0], dst.ctypes.data, addr[1], addr[2], none, none, none, none),
+                "pack": lambda: LabelRowsOutputs(addr[0], dst.ctypes.data, addr[1], addr[2], addr[3], addr[4], none, none),
+                "windows": lambda: LabelRowsOutputs(addr[0], dst.ctypes.data, addr[1], none, addr[2], none, addr[3], addr[4])}[kind]()
+        lcounts = np.zeros(4, dtype=np.int64)
+        rc = self._lib.td_encode_batch_span_label_rows(self._h, buf.ctypes.data if n else None, offs.ctypes.data, n_docs, ab.ctypes.data,
+                                                       ao.ctypes.data, len(ao) - 1, ctypes.byref(lspec), ctypes.byref(rspec), overlap,
+                                                       ctypes.byref(lab), ctypes.byref(outs), rows, counts.ctypes.data, lcounts.ctypes.data)
+        self._check_counts(rc, counts)
+        r = int(counts[0])
+        return (*self._rows_result(kind, rspec, b, counts, n_docs), dst[:r * S].reshape(r, S).copy(), lcounts)
 
     def device_status_pos(self, stream: int = 0) -> tuple[int, int]:
         """td_device_status without raising: (code, err_pos)."""

@@ -718,6 +718,51 @@ public:
         });
     }
 
+    // ---- label rows (td_make_rows_labeled, td_pack_rows_labeled, td_window_rows_labeled) ------------------------------------------
+    // One method for the four layouts: the layout's own result tuple (ids_to_rows / ids_to_packed_rows / ids_to_window_rows), then
+    // the label rows int32[rows, S].  flags: td_rows_spec's; lab_flags: td_rows_labels'.  The capacity is the exact rows.
+    py::tuple ids_to_labeled_rows(py::array_t<int32_t, py::array::c_style | py::array::forcecast> ids,
+                                  py::array_t<int32_t, py::array::c_style | py::array::forcecast> labels,
+                                  py::array_t<int64_t, py::array::c_style | py::array::forcecast> tok_offsets, int64_t seq_len, int layout,
+                                  int64_t overlap, int64_t bos, int64_t eos, int64_t pad, int64_t flags, int64_t lab_bos, int64_t lab_eos,
+                                  int64_t lab_pad, int64_t lab_flags, bool positions, bool aux, bool lengths, bool docs, bool starts) {
+        const int64_t n_docs = (int64_t)tok_offsets.size() - 1;
+        if (n_docs < 0) throw TiktokenError("tok_offsets must have n_docs+1 entries");
+        if (labels.size() < ids.size()) throw TiktokenError("labels must have an entry for every id");
+        const td_rows_spec sp{layout, seq_len, bos, eos, pad, flags};
+        const int64_t n = (int64_t)ids.size();
+        const int32_t* tp = ids.data();
+        const int64_t* op = tok_offsets.data();
+        int64_t plan[4] = {0, 0, 0, 0};
+        if (layout == TD_ROWS_BESTFIT) {
+            if (td_pack_plan(op, n_docs, &sp, plan, nullptr, nullptr) != TD_OK) throw TiktokenError("invalid seq_len / flags or tok_offsets");
+        } else if (layout == TD_ROWS_WINDOWS) {
+            if (td_window_plan(op, n_docs, &sp, overlap, plan, nullptr) != TD_OK) throw TiktokenError("invalid seq_len / overlap or tok_offsets");
+        } else {
+            plan[0] = rows_for(sp, std::min<int64_t>(op[n_docs], n), n_docs);
+        }
+        const int64_t cap = plan[0], S = seq_len > 0 ? seq_len : 1;
+        py::array_t<int32_t> dst(std::max<int64_t>(cap * S, 1));
+        static const int32_t no_labels = 0;  // (no ids: src still has to point somewhere)
+        const td_rows_labels lab{labels.size() ? labels.data() : &no_labels, dst.mutable_data(), lab_bos, lab_eos, lab_pad, lab_flags};
+        py::tuple r;
+        if (layout == TD_ROWS_BESTFIT)
+            r = pack_call(sp, cap, n_docs, positions, aux, lengths, docs, [&](const td_pack_outputs* o, int64_t* cp) {
+                return td_pack_rows_labeled(h_, tp, n, op, n_docs, &sp, o, cap, cp, &lab);
+            });
+        else if (layout == TD_ROWS_WINDOWS)
+            r = window_call(sp, cap, positions, lengths, docs, starts, [&](const td_window_outputs* o, int64_t* cp) {
+                return td_window_rows_labeled(h_, tp, n, op, n_docs, &sp, overlap, o, cap, cp, &lab);
+            });
+        else
+            r = rows_call(sp, cap, n_docs, positions, aux, [&](int32_t* ip, int32_t* pp, int32_t* ap, int64_t* cp) {
+                return td_make_rows_labeled(h_, tp, n, op, n_docs, &sp, ip, cap, pp, ap, cp, &lab);
+            });
+        const int64_t rows = r[r.size() - 1].cast<py::array_t<int64_t>>().data()[0];
+        dst.resize({(py::ssize_t)(rows * S)}, false);
+        return r + py::make_tuple(dst.attr("reshape")(rows, S));
+    }
+
     // list[str] in, list[list[int]] out through ONE device batch (PackedTexts / IntCache above)
     py::list encode_batch(const py::sequence& texts, int mode) {
         PackedTexts in(texts);
@@ -891,6 +936,10 @@ PYBIND11_MODULE(_tokendagger_core, m) {
         .def("encode_batch_numpy_window_rows", &CoreBPE::encode_batch_numpy_window_rows, py::arg("text"), py::arg("offsets"), py::arg("seq_len"),
              py::arg("overlap") = 0, py::arg("bos") = -1, py::arg("eos") = -1, py::arg("pad") = 0, py::arg("positions") = false,
              py::arg("lengths") = true, py::arg("docs") = true, py::arg("starts") = true, py::arg("mode") = TD_MODE_ENCODE)
+        .def("ids_to_labeled_rows", &CoreBPE::ids_to_labeled_rows, py::arg("ids"), py::arg("labels"), py::arg("tok_offsets"), py::arg("seq_len"),
+             py::arg("layout") = TD_ROWS_CONCAT, py::arg("overlap") = 0, py::arg("bos") = -1, py::arg("eos") = -1, py::arg("pad") = 0,
+             py::arg("flags") = 0, py::arg("lab_bos") = -100, py::arg("lab_eos") = -100, py::arg("lab_pad") = -100, py::arg("lab_flags") = 0,
+             py::arg("positions") = false, py::arg("aux") = true, py::arg("lengths") = true, py::arg("docs") = true, py::arg("starts") = true)
         .def("decode_batch", &CoreBPE::decode_batch, py::arg("docs"))
         .def("encode_batch_special", &CoreBPE::encode_batch_special, py::arg("texts"), py::arg("allowed_special"))
         .def("token_bytes", &CoreBPE::token_bytes, py::arg("id"))

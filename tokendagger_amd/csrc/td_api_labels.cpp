@@ -154,4 +154,50 @@ int td_encode_batch_span_labels(td_tokenizer* t, const uint8_t* text, const int6
     });
 }
 
+int td_encode_batch_span_label_rows(td_tokenizer* t, const uint8_t* text, const int64_t* doc_offsets, int64_t n_docs,
+                                    const uint8_t* allowed_bytes, const int64_t* allowed_offsets, int64_t n_allowed,
+                                    const td_labels_spec* lspec, const td_rows_spec* rspec, int64_t overlap, const td_rows_labels* lab,
+                                    const td_label_rows_outputs* host_out, int64_t rows_capacity, int64_t* row_counts,
+                                    int64_t* label_counts) {
+    const char* fn = "td_encode_batch_span_label_rows";
+    if (!t || !lspec || !rspec || !lab || !host_out || !doc_offsets || n_docs < 0 || n_allowed < 0 ||
+        (n_allowed > 0 && (!allowed_bytes || !allowed_offsets)) || !row_counts || !label_counts)
+        return TD_E_INVALID;
+    LabSpec sp;
+    if (int rc = labels_spec_fail(t, fn, labels_spec_error(lspec, sp))) return rc;
+    if (int rc = label_rows_check(t, fn, rspec, overlap, n_docs, lab, host_out, rows_capacity)) return rc;
+    return locked(t, [&] {
+        int rc;
+        if ((rc = check_offsets(t, "doc_offsets", doc_offsets, n_docs, text))) return rc;
+        const int64_t n = doc_offsets[n_docs];
+        std::vector<int64_t> toff((size_t)n_docs + 1);
+        // One encode.  Where it leaves its ids in d_tokens (the device search, td_api_special.cpp) they are not copied out as well and
+        // `ids` is never touched; everywhere else it writes host ids (at most one per byte), which are staged like a caller's.
+        std::unique_ptr<int32_t[]> ids(new int32_t[(size_t)std::max<int64_t>(n, 1)]);
+        int64_t total = 0;
+        t->enc_keep_resident = true;
+        rc = encode_special_strs_locked(t, text, doc_offsets, n_docs, allowed_bytes, allowed_offsets, n_allowed, ids.get(),
+                                        std::max<int64_t>(n, 1), toff.data(), &total);
+        t->enc_keep_resident = false;
+        if (rc) return rc;
+        total = toff[(size_t)n_docs];
+        hipStream_t s;
+        const void* d_ids;
+        if (t->enc_resident) {
+            s = t->s_own;
+            d_ids = t->d_tokens.p;
+        } else {
+            if ((rc = rows_stage_host_ids(t, ids.get(), toff.data(), n_docs, s))) return rc;
+            d_ids = t->dec_tokens.p;
+        }
+        if ((rc = ensure(t, t->lab_out, (size_t)std::max<int64_t>(total, 1) * 4))) return rc;
+        if ((rc = ensure(t, t->lab_counts, 4 * sizeof(int64_t)))) return rc;
+        if ((rc = labels_launch_locked(t, d_ids, total, t->d_offsets.p, n_docs, sp, t->lab_out.p, nullptr, nullptr, t->lab_counts.p, s))) return rc;
+        if ((rc = device_status_locked(t, s, nullptr))) return rc;
+        if ((rc = copy_wait(t, label_counts, t->lab_counts.p, 4 * sizeof(int64_t), hipMemcpyDeviceToHost, s))) return rc;
+        return label_rows_to_host(t, d_ids, t->lab_out.p, t->d_offsets.p, toff.data(), n_docs, rspec, overlap, lab, *host_out, rows_capacity,
+                                  row_counts, s);
+    });
+}
+
 }  // extern "C"

@@ -100,6 +100,44 @@ int rows_spec_fail(td_tokenizer* t, const char* fn, const char* m, const td_rows
     return rows_check_ids(t, sp);
 }
 
+// ---- the label stream of the labeled entry points (td_rows_labels) ---------------------------------------------------------------
+// The one checker of a td_rows_labels (no handle); with_ptrs: src and dst are the caller's (not the fused entry's own buffers).
+const char* rows_labels_error(const td_rows_labels* lab, int64_t layout, bool with_ptrs) {
+    if (!lab) return "null td_rows_labels";
+    for (const int64_t v : {lab->bos_value, lab->eos_value, lab->pad_value})
+        if (v < INT32_MIN || v > INT32_MAX) return "bos_value, eos_value and pad_value must be int32";
+    if (lab->flags & ~(int64_t)TD_ROWLAB_MASK_OVERLAP) return "unknown td_rows_labels flags";
+    if ((lab->flags & TD_ROWLAB_MASK_OVERLAP) && layout != TD_ROWS_WINDOWS) return "TD_ROWLAB_MASK_OVERLAP is for TD_ROWS_WINDOWS only";
+    if (with_ptrs && !lab->src) return "null td_rows_labels src";
+    if (with_ptrs && !lab->dst) return "null td_rows_labels dst";
+    return nullptr;
+}
+
+// A call's label stream on its way to the kernels: spec null is a one-stream call.  d_src is device memory; dst is the caller's
+// (device memory in the device forms, host memory where the rows come back through the handle's buffers).
+struct LabCall {
+    const td_rows_labels* spec = nullptr;
+    const void* d_src = nullptr;
+    void* dst = nullptr;
+};
+
+// The entry points' step behind rows_spec_fail: nothing for a one-stream call, the label spec's checks for a labeled one.
+int rows_lab_fail(td_tokenizer* t, const char* fn, const td_rows_labels* lab, const td_rows_spec* sp, bool labeled) {
+    if (!labeled) return TD_OK;
+    const char* m = rows_labels_error(lab, sp->layout, true);
+    return m ? fail_unlocked(t, TD_E_INVALID, std::string(fn) + ": " + m) : (int)TD_OK;
+}
+
+void rows_fill_lab(LabArgs& l, const LabCall& lc, void* d_dst) {  // (behind rows_fill_args: l is zero)
+    if (!lc.spec) return;
+    l.src = (const int32_t*)lc.d_src;
+    l.dst = (int32_t*)d_dst;
+    l.bos = (int32_t)lc.spec->bos_value;
+    l.eos = (int32_t)lc.spec->eos_value;
+    l.pad = (int32_t)lc.spec->pad_value;
+    l.mask_overlap = (lc.spec->flags & TD_ROWLAB_MASK_OVERLAP) ? 1 : 0;
+}
+
 int64_t rows_needed(const td_rows_spec* sp, int64_t n_ids, int64_t n_docs) {
     if (sp->layout == TD_ROWS_PAD) return n_docs;
     const int64_t T = n_ids + n_docs * ((sp->bos_id >= 0) + (sp->eos_id >= 0));
@@ -111,7 +149,7 @@ int rows_funnel_src() {  // TD_ROWS_FUNNEL=1 in the environment: misaligned ids 
     return v;
 }
 
-// Zeroes a RowsArgs / PackArgs / WindowArgs and fills the fields they share: the input and the spec's framing.
+// Zeroes a RowsLabArgs / PackLabArgs / WindowLabArgs and fills the fields they share: the input and the spec's framing.
 template <class A>
 void rows_fill_args(A& a, const void* d_ids, int64_t n_tokens, const void* d_toff, int64_t n_docs, const td_rows_spec* sp) {
     memset(&a, 0, sizeof a);
@@ -128,12 +166,13 @@ void rows_fill_args(A& a, const void* d_ids, int64_t n_tokens, const void* d_tof
 }
 
 int rows_launch_locked(td_tokenizer* t, const void* d_ids, int64_t n_tokens, const void* d_toff, int64_t n_docs, const td_rows_spec* sp,
-                       void* d_out, int64_t cap, void* d_pos, void* d_aux, void* d_counts, hipStream_t s) {
+                       void* d_out, int64_t cap, void* d_pos, void* d_aux, void* d_counts, const LabCall& lc, hipStream_t s) {
     int rc;
     if ((rc = order_before(t, s))) return rc;
     t->rows_last = true;
-    RowsArgs a;
+    RowsLabArgs a;
     rows_fill_args(a, d_ids, n_tokens, d_toff, n_docs, sp);
+    rows_fill_lab(a.lab, lc, lc.dst);
     a.layout = (int)sp->layout;
     a.drop_last = (sp->flags & TD_ROWS_DROP_LAST) ? 1 : 0;
     a.s_magic = ~0ull / (unsigned long long)sp->seq_len;
@@ -185,20 +224,23 @@ int rows_out_copy(td_tokenizer* t, const RowsOut* o, int n, hipStream_t s) {
 // Host entry points: rows (known on the host, checked against the capacity by the caller) from ids already on the device, into
 // the handle's buffers, then to the caller's.
 int rows_to_host(td_tokenizer* t, const void* d_ids, int64_t n_ids, const void* d_toff, int64_t n_docs, const td_rows_spec* sp, int64_t rows,
-                 int32_t* out_ids, int32_t* out_pos, int32_t* out_aux, int64_t* counts, hipStream_t s) {
+                 int32_t* out_ids, int32_t* out_pos, int32_t* out_aux, int64_t* counts, const LabCall& lc, hipStream_t s) {
     int rc;
     const bool concat = sp->layout == TD_ROWS_CONCAT;
     const int64_t slots = rows * sp->seq_len;
     RowsOut o[] = {{true, out_ids, &t->rows_out, 4, slots, slots},
                    {out_pos != nullptr, out_pos, &t->rows_pos, 4, slots, slots},
-                   {out_aux != nullptr, out_aux, &t->rows_aux, 4, concat ? n_docs + rows + 1 : n_docs, n_docs}};
-    if ((rc = rows_out_ensure(t, o, 3))) return rc;
+                   {out_aux != nullptr, out_aux, &t->rows_aux, 4, concat ? n_docs + rows + 1 : n_docs, n_docs},
+                   {lc.spec != nullptr, lc.dst, &t->rows_lab, 4, slots, slots}};
+    if ((rc = rows_out_ensure(t, o, 4))) return rc;
     if ((rc = ensure(t, t->rows_counts, 4 * sizeof(int64_t)))) return rc;
-    if ((rc = rows_launch_locked(t, d_ids, n_ids, d_toff, n_docs, sp, o[0].p(), rows, o[1].p(), o[2].p(), t->rows_counts.p, s))) return rc;
+    if ((rc = rows_launch_locked(t, d_ids, n_ids, d_toff, n_docs, sp, o[0].p(), rows, o[1].p(), o[2].p(), t->rows_counts.p,
+                                 LabCall{lc.spec, lc.d_src, o[3].p()}, s)))
+        return rc;
     if ((rc = device_status_locked(t, s, nullptr))) return rc;
     if ((rc = copy_wait(t, counts, t->rows_counts.p, 4 * sizeof(int64_t), hipMemcpyDeviceToHost, s))) return rc;
     if (concat) o[2].n_copy = counts[2] + 1;  // (cu_seqlens: the segments and the end)
-    return rows_out_copy(t, o, 3, s);
+    return rows_out_copy(t, o, 4, s);
 }
 
 int rows_capacity_fail(td_tokenizer* t, int64_t rows, int64_t* counts) {
@@ -235,6 +277,16 @@ int td::rows_stage_host_ids(td_tokenizer* t, const int32_t* ids, const int64_t* 
 
 namespace {
 
+// The labeled host entry points: the caller's label stream behind its ids, into rows_lab_src on the same stream.
+int rows_stage_host_src(td_tokenizer* t, const td_rows_labels* lab, int64_t total, LabCall& lc, hipStream_t s) {
+    if (!lab) return TD_OK;
+    int rc;
+    if ((rc = ensure(t, t->rows_lab_src, (size_t)std::max<int64_t>(total, 1) * 4))) return rc;
+    if (total > 0) HIP_TRY(t, hipMemcpyAsync(t->rows_lab_src.p, lab->src, (size_t)total * 4, hipMemcpyHostToDevice, s));
+    lc = LabCall{lab, t->rows_lab_src.p, lab->dst};
+    return TD_OK;
+}
+
 // td_encode_batch_rows, _pack_rows, _window_rows: the documents encoded on the handle's own stream `s` into d_tokens (room for
 // dev_cap ids) / d_offsets, and the encode's errors returned as such, before the rows read its ids.
 int rows_encode_locked(td_tokenizer* t, const uint8_t* text, const int64_t* doc_offsets, int64_t n_docs, int mode, int64_t& dev_cap,
@@ -266,12 +318,13 @@ int64_t window_count(int64_t L, int64_t C, int64_t overlap) { return L <= C ? 1 
 
 // Enqueues the scan and the slot kernel into the outputs of o (device pointers); d_counts is device memory.
 int window_launch_locked(td_tokenizer* t, const void* d_ids, int64_t n_tokens, const void* d_toff, int64_t n_docs, const td_rows_spec* sp,
-                         int64_t overlap, const td_window_outputs& o, int64_t cap, void* d_counts, hipStream_t s) {
+                         int64_t overlap, const td_window_outputs& o, int64_t cap, void* d_counts, const LabCall& lc, hipStream_t s) {
     int rc;
     if ((rc = order_before(t, s))) return rc;
     t->rows_last = true;
-    WindowArgs a;
+    WindowLabArgs a;
     rows_fill_args(a, d_ids, n_tokens, d_toff, n_docs, sp);
+    rows_fill_lab(a.lab, lc, lc.dst);
     a.C = a.S - a.b - a.e;
     a.overlap = overlap;
     a.step = a.C - overlap;
@@ -300,21 +353,24 @@ int window_launch_locked(td_tokenizer* t, const void* d_ids, int64_t n_tokens, c
 // Host entry points: `rows` rows (known on the host, checked against the capacity by the caller) from ids already on the device,
 // into the handle's buffers, then into host_out.
 int window_to_host(td_tokenizer* t, const void* d_ids, int64_t n_ids, const void* d_toff, int64_t n_docs, const td_rows_spec* sp,
-                   int64_t overlap, const td_window_outputs& ho, int64_t rows, int64_t* counts, hipStream_t s) {
+                   int64_t overlap, const td_window_outputs& ho, int64_t rows, int64_t* counts, const LabCall& lc, hipStream_t s) {
     int rc;
     const int64_t slots = rows * sp->seq_len;
     RowsOut o[] = {{true, ho.ids, &t->rows_out, 4, slots, slots},
                    {ho.positions != nullptr, ho.positions, &t->rows_pos, 4, slots, slots},
                    {ho.row_lengths != nullptr, ho.row_lengths, &t->win_len, 4, rows, rows},
                    {ho.row_docs != nullptr, ho.row_docs, &t->win_docs, 8, rows, rows},
-                   {ho.row_starts != nullptr, ho.row_starts, &t->win_starts, 8, rows, rows}};
-    if ((rc = rows_out_ensure(t, o, 5))) return rc;
+                   {ho.row_starts != nullptr, ho.row_starts, &t->win_starts, 8, rows, rows},
+                   {lc.spec != nullptr, lc.dst, &t->rows_lab, 4, slots, slots}};
+    if ((rc = rows_out_ensure(t, o, 6))) return rc;
     if ((rc = ensure(t, t->rows_counts, 4 * sizeof(int64_t)))) return rc;
     const td_window_outputs d{(int32_t*)o[0].p(), (int32_t*)o[1].p(), (int32_t*)o[2].p(), (int64_t*)o[3].p(), (int64_t*)o[4].p()};
-    if ((rc = window_launch_locked(t, d_ids, n_ids, d_toff, n_docs, sp, overlap, d, rows, t->rows_counts.p, s))) return rc;
+    if ((rc = window_launch_locked(t, d_ids, n_ids, d_toff, n_docs, sp, overlap, d, rows, t->rows_counts.p,
+                                   LabCall{lc.spec, lc.d_src, o[5].p()}, s)))
+        return rc;
     if ((rc = device_status_locked(t, s, nullptr))) return rc;
     if ((rc = copy_wait(t, counts, t->rows_counts.p, 4 * sizeof(int64_t), hipMemcpyDeviceToHost, s))) return rc;
-    return rows_out_copy(t, o, 5, s);
+    return rows_out_copy(t, o, 6, s);
 }
 
 // ---- best-fit packing (td_pack.hip) ------------------------------------------------------------------------------------------
@@ -346,7 +402,7 @@ PackDoc pack_doc(const td_rows_spec* sp, int64_t L) {
 // host plan.  Fills `a` (everything but the outputs and the segment arrays) and counts.  Offsets that are negative, decreasing
 // or beyond n_tokens: TD_E_INVALID, nothing launched behind the read-back.
 int pack_prepare(td_tokenizer* t, const void* d_ids, int64_t n_tokens, const void* d_toff, int64_t n_docs, const td_rows_spec* sp,
-                 hipStream_t s, PackArgs& a, PackPlan& plan, int64_t* counts) {
+                 hipStream_t s, PackLabArgs& a, PackPlan& plan, int64_t* counts) {
     int rc;
     if ((rc = order_before(t, s))) return rc;
     rows_fill_args(a, d_ids, n_tokens, d_toff, n_docs, sp);
@@ -416,8 +472,9 @@ int pack_prepare(td_tokenizer* t, const void* d_ids, int64_t n_tokens, const voi
 }
 
 // Uploads the plan and enqueues td_pack_segments + td_pack_slots into the outputs of o (device pointers).
-int pack_emit(td_tokenizer* t, PackArgs& a, const PackPlan& plan, const td_pack_outputs& o, hipStream_t s) {
+int pack_emit(td_tokenizer* t, PackLabArgs& a, const PackPlan& plan, const td_pack_outputs& o, const LabCall& lc, hipStream_t s) {
     int rc;
+    rows_fill_lab(a.lab, lc, lc.dst);
     const size_t n_pl = plan.pl.size(), n_m = plan.fill.size();
     const size_t up = n_pl * sizeof(PackPlacement) + (n_m + n_m + 1) * 8;
     if ((rc = pinned_ensure(t, t->pack_up, up))) return rc;
@@ -448,9 +505,9 @@ int pack_emit(td_tokenizer* t, PackArgs& a, const PackPlan& plan, const td_pack_
 
 // Host entry points: packs ids already on the device into the handle's buffers, then copies them into host_out.
 int pack_to_host(td_tokenizer* t, const void* d_ids, int64_t n_ids, const void* d_toff, int64_t n_docs, const td_rows_spec* sp,
-                 const td_pack_outputs& ho, int64_t cap, int64_t* counts, hipStream_t s) {
+                 const td_pack_outputs& ho, int64_t cap, int64_t* counts, const LabCall& lc, hipStream_t s) {
     int rc;
-    PackArgs a;
+    PackLabArgs a;
     PackPlan plan;
     if ((rc = pack_prepare(t, d_ids, n_ids, d_toff, n_docs, sp, s, a, plan, counts))) return rc;
     if (plan.rows > cap) return rows_capacity_fail(t, plan.rows, counts);
@@ -459,11 +516,12 @@ int pack_to_host(td_tokenizer* t, const void* d_ids, int64_t n_ids, const void* 
                          {ho.positions != nullptr, ho.positions, &t->rows_pos, 4, slots, slots},
                          {ho.cu_seqlens != nullptr, ho.cu_seqlens, &t->rows_aux, 4, plan.segs + 1, plan.segs + 1},
                          {ho.row_lengths != nullptr, ho.row_lengths, &t->pack_len, 4, plan.rows, plan.rows},
-                         {ho.seg_docs != nullptr, ho.seg_docs, &t->pack_docs, 8, plan.segs + 1, plan.segs}};
-    if ((rc = rows_out_ensure(t, o, 5))) return rc;
+                         {ho.seg_docs != nullptr, ho.seg_docs, &t->pack_docs, 8, plan.segs + 1, plan.segs},
+                         {lc.spec != nullptr, lc.dst, &t->rows_lab, 4, slots, slots}};
+    if ((rc = rows_out_ensure(t, o, 6))) return rc;
     const td_pack_outputs d{(int32_t*)o[0].p(), (int32_t*)o[1].p(), (int32_t*)o[2].p(), (int32_t*)o[3].p(), (int64_t*)o[4].p()};
-    if ((rc = pack_emit(t, a, plan, d, s))) return rc;
-    if ((rc = rows_out_copy(t, o, 5, s))) return rc;
+    if ((rc = pack_emit(t, a, plan, d, LabCall{lc.spec, lc.d_src, o[5].p()}, s))) return rc;
+    if ((rc = rows_out_copy(t, o, 6, s))) return rc;
     HIP_TRY(t, hipStreamSynchronize(s));  // (nothing copied at all: the kernels are still done when the call returns)
     return TD_OK;
 }
@@ -497,6 +555,52 @@ int td::encode_starts_locked(td_tokenizer* t, const void* d_text, int64_t n, con
     HIP_TRY(t, launch_token_starts(a, stream));
     HIP_TRY(t, launch_encode_starts(a, stream));
     return order_after(t, stream);
+}
+
+// td_encode_batch_span_label_rows (td_api_labels.cpp): the checks of its row arguments, nothing allocated or enqueued ...
+int td::label_rows_check(td_tokenizer* t, const char* fn, const td_rows_spec* sp, int64_t overlap, int64_t n_docs, const td_rows_labels* lab,
+                         const td_label_rows_outputs* o, int64_t rows_capacity) {
+    const char* m = nullptr;
+    if (!sp) m = "null td_rows_spec";
+    else if (!o) m = "null td_label_rows_outputs";
+    else if (sp->layout < TD_ROWS_CONCAT || sp->layout > TD_ROWS_WINDOWS) m = "unknown layout";
+    else if (rows_capacity > 0 && !o->labels) m = "null labels output";
+    else if (sp->layout <= TD_ROWS_PAD) {
+        if (o->row_lengths || o->seg_docs || o->row_docs || o->row_starts) m = "TD_ROWS_CONCAT / TD_ROWS_PAD have ids, labels, positions and aux only";
+        else if (rows_capacity > 0 && !o->ids) m = "null ids output";
+        else m = rows_spec_error(FAM_ROWS, sp, 0, rows_capacity, sp->layout == TD_ROWS_CONCAT && o->aux);
+    } else if (sp->layout == TD_ROWS_BESTFIT) {
+        const td_pack_outputs po{o->ids, o->positions, o->aux, o->row_lengths, o->seg_docs};
+        m = o->row_docs || o->row_starts ? "TD_ROWS_BESTFIT has no row_docs and no row_starts" : rows_args_error(sp, 0, n_docs, rows_capacity, &po);
+    } else {
+        const td_window_outputs wo{o->ids, o->positions, o->row_lengths, o->row_docs, o->row_starts};
+        m = o->aux || o->seg_docs ? "TD_ROWS_WINDOWS has no aux and no seg_docs" : rows_args_error(sp, overlap, n_docs, rows_capacity, &wo);
+    }
+    if (int rc = rows_spec_fail(t, fn, m, sp)) return rc;
+    m = rows_labels_error(lab, sp->layout, false);
+    return m ? fail_unlocked(t, TD_E_INVALID, std::string(fn) + ": " + m) : (int)TD_OK;
+}
+
+// ... and the labeled row call of sp->layout (checked by label_rows_check) on `total` ids and labels already on the device, on `s`:
+// the host path of td_make_rows_labeled / td_pack_rows_labeled / td_window_rows_labeled behind their staging.
+int td::label_rows_to_host(td_tokenizer* t, const void* d_ids, const void* d_src, const void* d_toff, const int64_t* h_toff, int64_t n_docs,
+                           const td_rows_spec* sp, int64_t overlap, const td_rows_labels* lab, const td_label_rows_outputs& o,
+                           int64_t rows_capacity, int64_t* counts, hipStream_t s) {
+    const int64_t total = h_toff[n_docs];
+    const LabCall lc{lab, d_src, o.labels};
+    if (sp->layout == TD_ROWS_BESTFIT)
+        return pack_to_host(t, d_ids, total, d_toff, n_docs, sp, td_pack_outputs{o.ids, o.positions, o.aux, o.row_lengths, o.seg_docs},
+                            rows_capacity, counts, lc, s);
+    if (sp->layout == TD_ROWS_WINDOWS) {
+        int64_t plan[4];
+        if (td_window_plan(h_toff, n_docs, sp, overlap, plan, nullptr) != TD_OK) { t->err = "invalid token offsets"; return TD_E_INVALID; }
+        if (plan[0] > rows_capacity) return rows_capacity_fail(t, plan[0], counts);
+        return window_to_host(t, d_ids, total, d_toff, n_docs, sp, overlap,
+                              td_window_outputs{o.ids, o.positions, o.row_lengths, o.row_docs, o.row_starts}, plan[0], counts, lc, s);
+    }
+    const int64_t rows = rows_needed(sp, total, n_docs);
+    if (rows > rows_capacity) return rows_capacity_fail(t, rows, counts);
+    return rows_to_host(t, d_ids, total, d_toff, n_docs, sp, rows, o.ids, o.positions, o.aux, counts, lc, s);
 }
 
 extern "C" {
@@ -550,26 +654,42 @@ int td_encode_device_with_starts(td_tokenizer* t, const void* d_text, int64_t n_
     });
 }
 
-int td_make_rows_device(td_tokenizer* t, const void* d_ids, int64_t n_tokens, const void* d_tok_offsets, int64_t n_docs,
-                        const td_rows_spec* spec, void* d_out_ids, int64_t rows_capacity, void* d_positions, void* d_aux,
-                        void* d_counts, void* hip_stream) {
+// Every entry point with a labeled form is one function: `fn` names the form called, lab is its td_rows_labels (labeled) or
+// nothing.  The label spec is checked behind the counterpart's own checks, before the lock and any launch.
+static int make_rows_device_any(const char* fn, bool labeled, td_tokenizer* t, const void* d_ids, int64_t n_tokens, const void* d_tok_offsets,
+                                int64_t n_docs, const td_rows_spec* spec, void* d_out_ids, int64_t rows_capacity, void* d_positions,
+                                void* d_aux, void* d_counts, void* hip_stream, const td_rows_labels* lab) {
     if (!t || !spec || n_tokens < 0 || n_docs < 0 || !d_tok_offsets || (n_tokens > 0 && !d_ids) || !d_counts ||
         (rows_capacity > 0 && !d_out_ids))
         return TD_E_INVALID;
-    if (int rc = rows_spec_fail(t, "td_make_rows_device",
-                                rows_spec_error(FAM_ROWS, spec, 0, rows_capacity, spec->layout == TD_ROWS_CONCAT && d_aux), spec)) return rc;
+    if (int rc = rows_spec_fail(t, fn, rows_spec_error(FAM_ROWS, spec, 0, rows_capacity, spec->layout == TD_ROWS_CONCAT && d_aux), spec)) return rc;
+    if (int rc = rows_lab_fail(t, fn, lab, spec, labeled)) return rc;
     return locked(t, [&] {
         return rows_launch_locked(t, d_ids, n_tokens, d_tok_offsets, n_docs, spec, d_out_ids, rows_capacity, d_positions, d_aux, d_counts,
-                                  (hipStream_t)hip_stream);
+                                  labeled ? LabCall{lab, lab->src, lab->dst} : LabCall{}, (hipStream_t)hip_stream);
     });
 }
 
-int td_make_rows(td_tokenizer* t, const int32_t* ids, int64_t n_tokens, const int64_t* tok_offsets, int64_t n_docs,
-                 const td_rows_spec* spec, int32_t* out_ids, int64_t rows_capacity, int32_t* out_positions, int32_t* out_aux,
-                 int64_t* counts) {
+int td_make_rows_device(td_tokenizer* t, const void* d_ids, int64_t n_tokens, const void* d_tok_offsets, int64_t n_docs,
+                        const td_rows_spec* spec, void* d_out_ids, int64_t rows_capacity, void* d_positions, void* d_aux,
+                        void* d_counts, void* hip_stream) {
+    return make_rows_device_any("td_make_rows_device", false, t, d_ids, n_tokens, d_tok_offsets, n_docs, spec, d_out_ids, rows_capacity,
+                                d_positions, d_aux, d_counts, hip_stream, nullptr);
+}
+
+int td_make_rows_labeled_device(td_tokenizer* t, const void* d_ids, int64_t n_tokens, const void* d_tok_offsets, int64_t n_docs,
+                                const td_rows_spec* spec, void* d_out_ids, int64_t rows_capacity, void* d_positions, void* d_aux,
+                                void* d_counts, void* hip_stream, const td_rows_labels* lab) {
+    return make_rows_device_any("td_make_rows_labeled_device", true, t, d_ids, n_tokens, d_tok_offsets, n_docs, spec, d_out_ids,
+                                rows_capacity, d_positions, d_aux, d_counts, hip_stream, lab);
+}
+
+static int make_rows_any(const char* fn, bool labeled, td_tokenizer* t, const int32_t* ids, int64_t n_tokens, const int64_t* tok_offsets,
+                         int64_t n_docs, const td_rows_spec* spec, int32_t* out_ids, int64_t rows_capacity, int32_t* out_positions,
+                         int32_t* out_aux, int64_t* counts, const td_rows_labels* lab) {
     if (!t || !spec || n_tokens < 0 || n_docs < 0 || !tok_offsets || !counts || (rows_capacity > 0 && !out_ids)) return TD_E_INVALID;
-    if (int rc = rows_spec_fail(t, "td_make_rows",
-                                rows_spec_error(FAM_ROWS, spec, 0, rows_capacity, spec->layout == TD_ROWS_CONCAT && out_aux), spec)) return rc;
+    if (int rc = rows_spec_fail(t, fn, rows_spec_error(FAM_ROWS, spec, 0, rows_capacity, spec->layout == TD_ROWS_CONCAT && out_aux), spec)) return rc;
+    if (int rc = rows_lab_fail(t, fn, lab, spec, labeled)) return rc;
     return locked(t, [&] {
         int rc2;
         if ((rc2 = rows_check_host_ids(t, ids, n_tokens, tok_offsets, n_docs))) return rc2;
@@ -577,9 +697,25 @@ int td_make_rows(td_tokenizer* t, const int32_t* ids, int64_t n_tokens, const in
         const int64_t rows = rows_needed(spec, total, n_docs);
         if (rows > rows_capacity) return rows_capacity_fail(t, rows, counts);
         hipStream_t s;
+        LabCall lc;
         if ((rc2 = rows_stage_host_ids(t, ids, tok_offsets, n_docs, s))) return rc2;
-        return rows_to_host(t, t->dec_tokens.p, total, t->d_offsets.p, n_docs, spec, rows, out_ids, out_positions, out_aux, counts, s);
+        if ((rc2 = rows_stage_host_src(t, lab, total, lc, s))) return rc2;
+        return rows_to_host(t, t->dec_tokens.p, total, t->d_offsets.p, n_docs, spec, rows, out_ids, out_positions, out_aux, counts, lc, s);
     });
+}
+
+int td_make_rows(td_tokenizer* t, const int32_t* ids, int64_t n_tokens, const int64_t* tok_offsets, int64_t n_docs,
+                 const td_rows_spec* spec, int32_t* out_ids, int64_t rows_capacity, int32_t* out_positions, int32_t* out_aux,
+                 int64_t* counts) {
+    return make_rows_any("td_make_rows", false, t, ids, n_tokens, tok_offsets, n_docs, spec, out_ids, rows_capacity, out_positions, out_aux,
+                         counts, nullptr);
+}
+
+int td_make_rows_labeled(td_tokenizer* t, const int32_t* ids, int64_t n_tokens, const int64_t* tok_offsets, int64_t n_docs,
+                         const td_rows_spec* spec, int32_t* out_ids, int64_t rows_capacity, int32_t* out_positions, int32_t* out_aux,
+                         int64_t* counts, const td_rows_labels* lab) {
+    return make_rows_any("td_make_rows_labeled", true, t, ids, n_tokens, tok_offsets, n_docs, spec, out_ids, rows_capacity, out_positions,
+                         out_aux, counts, lab);
 }
 
 int td_encode_batch_rows(td_tokenizer* t, const uint8_t* text, const int64_t* doc_offsets, int64_t n_docs, int mode,
@@ -599,7 +735,7 @@ int td_encode_batch_rows(td_tokenizer* t, const uint8_t* text, const int64_t* do
         if ((rc2 = copy_wait(t, &total, (const int64_t*)t->d_offsets.p + n_docs, 8, hipMemcpyDeviceToHost, s))) return rc2;
         const int64_t rows = rows_needed(spec, total, n_docs);
         if (rows > rows_capacity) return rows_capacity_fail(t, rows, counts);
-        return rows_to_host(t, t->d_tokens.p, dev_cap, t->d_offsets.p, n_docs, spec, rows, out_ids, out_positions, out_aux, counts, s);
+        return rows_to_host(t, t->d_tokens.p, dev_cap, t->d_offsets.p, n_docs, spec, rows, out_ids, out_positions, out_aux, counts, LabCall{}, s);
     });
 }
 
@@ -644,35 +780,65 @@ int td_pack_plan(const int64_t* tok_offsets, int64_t n_docs, const td_rows_spec*
     return TD_OK;
 }
 
-int td_pack_rows(td_tokenizer* t, const int32_t* ids, int64_t n_tokens, const int64_t* tok_offsets, int64_t n_docs,
-                 const td_rows_spec* spec, const td_pack_outputs* host_out, int64_t rows_capacity, int64_t* counts) {
+static int pack_rows_any(const char* fn, bool labeled, td_tokenizer* t, const int32_t* ids, int64_t n_tokens, const int64_t* tok_offsets,
+                         int64_t n_docs, const td_rows_spec* spec, const td_pack_outputs* host_out, int64_t rows_capacity, int64_t* counts,
+                         const td_rows_labels* lab) {
     if (!t || !spec || !host_out || n_tokens < 0 || n_docs < 0 || !tok_offsets || !counts) return TD_E_INVALID;
-    if (int rc = rows_spec_fail(t, "td_pack_rows", rows_args_error(spec, 0, n_docs, rows_capacity, host_out), spec)) return rc;
+    if (int rc = rows_spec_fail(t, fn, rows_args_error(spec, 0, n_docs, rows_capacity, host_out), spec)) return rc;
+    if (int rc = rows_lab_fail(t, fn, lab, spec, labeled)) return rc;
     return locked(t, [&] {
         int rc2;
         if ((rc2 = rows_check_host_ids(t, ids, n_tokens, tok_offsets, n_docs))) return rc2;
         const int64_t total = tok_offsets[n_docs];
         hipStream_t s;
+        LabCall lc;
         if ((rc2 = rows_stage_host_ids(t, ids, tok_offsets, n_docs, s))) return rc2;
-        return pack_to_host(t, t->dec_tokens.p, total, t->d_offsets.p, n_docs, spec, *host_out, rows_capacity, counts, s);
+        if ((rc2 = rows_stage_host_src(t, lab, total, lc, s))) return rc2;
+        return pack_to_host(t, t->dec_tokens.p, total, t->d_offsets.p, n_docs, spec, *host_out, rows_capacity, counts, lc, s);
+    });
+}
+
+int td_pack_rows(td_tokenizer* t, const int32_t* ids, int64_t n_tokens, const int64_t* tok_offsets, int64_t n_docs,
+                 const td_rows_spec* spec, const td_pack_outputs* host_out, int64_t rows_capacity, int64_t* counts) {
+    return pack_rows_any("td_pack_rows", false, t, ids, n_tokens, tok_offsets, n_docs, spec, host_out, rows_capacity, counts, nullptr);
+}
+
+int td_pack_rows_labeled(td_tokenizer* t, const int32_t* ids, int64_t n_tokens, const int64_t* tok_offsets, int64_t n_docs,
+                         const td_rows_spec* spec, const td_pack_outputs* host_out, int64_t rows_capacity, int64_t* counts,
+                         const td_rows_labels* lab) {
+    return pack_rows_any("td_pack_rows_labeled", true, t, ids, n_tokens, tok_offsets, n_docs, spec, host_out, rows_capacity, counts, lab);
+}
+
+static int pack_rows_device_any(const char* fn, bool labeled, td_tokenizer* t, const void* d_ids, int64_t n_tokens, const void* d_tok_offsets,
+                                int64_t n_docs, const td_rows_spec* spec, const td_pack_outputs* dev_out, int64_t rows_capacity,
+                                int64_t* counts, void* hip_stream, const td_rows_labels* lab) {
+    if (!t || !spec || !dev_out || n_tokens < 0 || n_docs < 0 || !d_tok_offsets || (n_tokens > 0 && !d_ids) || !counts)
+        return TD_E_INVALID;
+    if (int rc = rows_spec_fail(t, fn, rows_args_error(spec, 0, n_docs, rows_capacity, dev_out), spec)) return rc;
+    if (int rc = rows_lab_fail(t, fn, lab, spec, labeled)) return rc;
+    return locked(t, [&] {
+        hipStream_t s = (hipStream_t)hip_stream;
+        PackLabArgs a;
+        PackPlan plan;
+        int rc2;
+        if ((rc2 = pack_prepare(t, d_ids, n_tokens, d_tok_offsets, n_docs, spec, s, a, plan, counts))) return rc2;
+        if (plan.rows > rows_capacity) return rows_capacity_fail(t, plan.rows, counts);
+        return pack_emit(t, a, plan, *dev_out, labeled ? LabCall{lab, lab->src, lab->dst} : LabCall{}, s);
     });
 }
 
 int td_pack_rows_device(td_tokenizer* t, const void* d_ids, int64_t n_tokens, const void* d_tok_offsets, int64_t n_docs,
                         const td_rows_spec* spec, const td_pack_outputs* dev_out, int64_t rows_capacity, int64_t* counts,
                         void* hip_stream) {
-    if (!t || !spec || !dev_out || n_tokens < 0 || n_docs < 0 || !d_tok_offsets || (n_tokens > 0 && !d_ids) || !counts)
-        return TD_E_INVALID;
-    if (int rc = rows_spec_fail(t, "td_pack_rows_device", rows_args_error(spec, 0, n_docs, rows_capacity, dev_out), spec)) return rc;
-    return locked(t, [&] {
-        hipStream_t s = (hipStream_t)hip_stream;
-        PackArgs a;
-        PackPlan plan;
-        int rc2;
-        if ((rc2 = pack_prepare(t, d_ids, n_tokens, d_tok_offsets, n_docs, spec, s, a, plan, counts))) return rc2;
-        if (plan.rows > rows_capacity) return rows_capacity_fail(t, plan.rows, counts);
-        return pack_emit(t, a, plan, *dev_out, s);
-    });
+    return pack_rows_device_any("td_pack_rows_device", false, t, d_ids, n_tokens, d_tok_offsets, n_docs, spec, dev_out, rows_capacity, counts,
+                                hip_stream, nullptr);
+}
+
+int td_pack_rows_labeled_device(td_tokenizer* t, const void* d_ids, int64_t n_tokens, const void* d_tok_offsets, int64_t n_docs,
+                                const td_rows_spec* spec, const td_pack_outputs* dev_out, int64_t rows_capacity, int64_t* counts,
+                                void* hip_stream, const td_rows_labels* lab) {
+    return pack_rows_device_any("td_pack_rows_labeled_device", true, t, d_ids, n_tokens, d_tok_offsets, n_docs, spec, dev_out, rows_capacity,
+                                counts, hip_stream, lab);
 }
 
 int td_encode_batch_pack_rows(td_tokenizer* t, const uint8_t* text, const int64_t* doc_offsets, int64_t n_docs, int mode,
@@ -685,7 +851,7 @@ int td_encode_batch_pack_rows(td_tokenizer* t, const uint8_t* text, const int64_
         int64_t dev_cap;
         hipStream_t s;
         if ((rc2 = rows_encode_locked(t, text, doc_offsets, n_docs, mode, dev_cap, s))) return rc2;
-        return pack_to_host(t, t->d_tokens.p, dev_cap, t->d_offsets.p, n_docs, spec, *host_out, rows_capacity, counts, s);
+        return pack_to_host(t, t->d_tokens.p, dev_cap, t->d_offsets.p, n_docs, spec, *host_out, rows_capacity, counts, LabCall{}, s);
     });
 }
 
@@ -713,22 +879,40 @@ int td_window_plan(const int64_t* tok_offsets, int64_t n_docs, const td_rows_spe
     return TD_OK;
 }
 
-int td_window_rows_device(td_tokenizer* t, const void* d_ids, int64_t n_tokens, const void* d_tok_offsets, int64_t n_docs,
-                          const td_rows_spec* spec, int64_t overlap, const td_window_outputs* dev_out, int64_t rows_capacity,
-                          void* d_counts, void* hip_stream) {
+static int window_rows_device_any(const char* fn, bool labeled, td_tokenizer* t, const void* d_ids, int64_t n_tokens,
+                                  const void* d_tok_offsets, int64_t n_docs, const td_rows_spec* spec, int64_t overlap,
+                                  const td_window_outputs* dev_out, int64_t rows_capacity, void* d_counts, void* hip_stream,
+                                  const td_rows_labels* lab) {
     if (!t || !spec || !dev_out || n_tokens < 0 || n_docs < 0 || !d_tok_offsets || (n_tokens > 0 && !d_ids) || !d_counts)
         return TD_E_INVALID;
-    if (int rc = rows_spec_fail(t, "td_window_rows_device", rows_args_error(spec, overlap, n_docs, rows_capacity, dev_out), spec)) return rc;
+    if (int rc = rows_spec_fail(t, fn, rows_args_error(spec, overlap, n_docs, rows_capacity, dev_out), spec)) return rc;
+    if (int rc = rows_lab_fail(t, fn, lab, spec, labeled)) return rc;
     return locked(t, [&] {
         return window_launch_locked(t, d_ids, n_tokens, d_tok_offsets, n_docs, spec, overlap, *dev_out, rows_capacity, d_counts,
-                                    (hipStream_t)hip_stream);
+                                    labeled ? LabCall{lab, lab->src, lab->dst} : LabCall{}, (hipStream_t)hip_stream);
     });
 }
 
-int td_window_rows(td_tokenizer* t, const int32_t* ids, int64_t n_tokens, const int64_t* tok_offsets, int64_t n_docs,
-                   const td_rows_spec* spec, int64_t overlap, const td_window_outputs* host_out, int64_t rows_capacity, int64_t* counts) {
+int td_window_rows_device(td_tokenizer* t, const void* d_ids, int64_t n_tokens, const void* d_tok_offsets, int64_t n_docs,
+                          const td_rows_spec* spec, int64_t overlap, const td_window_outputs* dev_out, int64_t rows_capacity,
+                          void* d_counts, void* hip_stream) {
+    return window_rows_device_any("td_window_rows_device", false, t, d_ids, n_tokens, d_tok_offsets, n_docs, spec, overlap, dev_out,
+                                  rows_capacity, d_counts, hip_stream, nullptr);
+}
+
+int td_window_rows_labeled_device(td_tokenizer* t, const void* d_ids, int64_t n_tokens, const void* d_tok_offsets, int64_t n_docs,
+                                  const td_rows_spec* spec, int64_t overlap, const td_window_outputs* dev_out, int64_t rows_capacity,
+                                  void* d_counts, void* hip_stream, const td_rows_labels* lab) {
+    return window_rows_device_any("td_window_rows_labeled_device", true, t, d_ids, n_tokens, d_tok_offsets, n_docs, spec, overlap, dev_out,
+                                  rows_capacity, d_counts, hip_stream, lab);
+}
+
+static int window_rows_any(const char* fn, bool labeled, td_tokenizer* t, const int32_t* ids, int64_t n_tokens, const int64_t* tok_offsets,
+                           int64_t n_docs, const td_rows_spec* spec, int64_t overlap, const td_window_outputs* host_out,
+                           int64_t rows_capacity, int64_t* counts, const td_rows_labels* lab) {
     if (!t || !spec || !host_out || n_tokens < 0 || n_docs < 0 || !tok_offsets || !counts) return TD_E_INVALID;
-    if (int rc = rows_spec_fail(t, "td_window_rows", rows_args_error(spec, overlap, n_docs, rows_capacity, host_out), spec)) return rc;
+    if (int rc = rows_spec_fail(t, fn, rows_args_error(spec, overlap, n_docs, rows_capacity, host_out), spec)) return rc;
+    if (int rc = rows_lab_fail(t, fn, lab, spec, labeled)) return rc;
     return locked(t, [&] {
         int rc2;
         if ((rc2 = rows_check_host_ids(t, ids, n_tokens, tok_offsets, n_docs))) return rc2;
@@ -737,9 +921,24 @@ int td_window_rows(td_tokenizer* t, const int32_t* ids, int64_t n_tokens, const 
         if (td_window_plan(tok_offsets, n_docs, spec, overlap, plan, nullptr) != TD_OK) { t->err = "invalid tok_offsets"; return (int)TD_E_INVALID; }
         if (plan[0] > rows_capacity) return rows_capacity_fail(t, plan[0], counts);
         hipStream_t s;
+        LabCall lc;
         if ((rc2 = rows_stage_host_ids(t, ids, tok_offsets, n_docs, s))) return rc2;
-        return window_to_host(t, t->dec_tokens.p, total, t->d_offsets.p, n_docs, spec, overlap, *host_out, plan[0], counts, s);
+        if ((rc2 = rows_stage_host_src(t, lab, total, lc, s))) return rc2;
+        return window_to_host(t, t->dec_tokens.p, total, t->d_offsets.p, n_docs, spec, overlap, *host_out, plan[0], counts, lc, s);
     });
+}
+
+int td_window_rows(td_tokenizer* t, const int32_t* ids, int64_t n_tokens, const int64_t* tok_offsets, int64_t n_docs,
+                   const td_rows_spec* spec, int64_t overlap, const td_window_outputs* host_out, int64_t rows_capacity, int64_t* counts) {
+    return window_rows_any("td_window_rows", false, t, ids, n_tokens, tok_offsets, n_docs, spec, overlap, host_out, rows_capacity, counts,
+                           nullptr);
+}
+
+int td_window_rows_labeled(td_tokenizer* t, const int32_t* ids, int64_t n_tokens, const int64_t* tok_offsets, int64_t n_docs,
+                           const td_rows_spec* spec, int64_t overlap, const td_window_outputs* host_out, int64_t rows_capacity,
+                           int64_t* counts, const td_rows_labels* lab) {
+    return window_rows_any("td_window_rows_labeled", true, t, ids, n_tokens, tok_offsets, n_docs, spec, overlap, host_out, rows_capacity,
+                           counts, lab);
 }
 
 int td_encode_batch_window_rows(td_tokenizer* t, const uint8_t* text, const int64_t* doc_offsets, int64_t n_docs, int mode,
@@ -759,7 +958,7 @@ int td_encode_batch_window_rows(td_tokenizer* t, const uint8_t* text, const int6
         int64_t plan[4];
         if (td_window_plan(toff.data(), n_docs, spec, overlap, plan, nullptr) != TD_OK) { t->err = "invalid token offsets"; return (int)TD_E_INVALID; }
         if (plan[0] > rows_capacity) return rows_capacity_fail(t, plan[0], counts);
-        return window_to_host(t, t->d_tokens.p, dev_cap, t->d_offsets.p, n_docs, spec, overlap, *host_out, plan[0], counts, s);
+        return window_to_host(t, t->d_tokens.p, dev_cap, t->d_offsets.p, n_docs, spec, overlap, *host_out, plan[0], counts, LabCall{}, s);
     });
 }
 

@@ -270,6 +270,10 @@ int encode_special_locked(td_tokenizer* t, const uint8_t* text, const int64_t* d
                 if ((rc = copy_wait(t, out_offsets, t->d_offsets.p, (size_t)(n_docs + 1) * 8, hipMemcpyDeviceToHost, s))) return rc;
                 const int64_t total = out_offsets[n_docs];
                 t->enc_resident = true;
+                if (t->enc_keep_resident) {  // (the caller reads d_tokens: td_encode_batch_span_label_rows)
+                    if (n_tokens) *n_tokens = total;
+                    return TD_OK;
+                }
                 return deliver_ids(t, total, out_capacity, out_tokens, n_tokens,
                                    [&] { return copy_wait(t, out_tokens, t->d_tokens.p, (size_t)total * 4, hipMemcpyDeviceToHost, s); });
             }

@@ -243,6 +243,7 @@ struct td_tokenizer {
     DevBuf off_heads, off_chunks, off_docs, off_rank, off_starts;
     // training rows (td_rows.hip): the cu_seqlens scan's status words, the host entry points' outputs on the device
     DevBuf rows_scan, rows_out, rows_pos, rows_aux, rows_counts;
+    DevBuf rows_lab_src, rows_lab;  // the labeled host entry points: the caller's label stream, the label rows
     // window rows (td_windows.hip): the scan words and first_row, the host entry points' per-row outputs on the device
     DevBuf win_scan, win_first, win_len, win_docs, win_starts;
     bool rows_last = false;  // the last call launched the rows kernels (the unit of a TD_E_CAPACITY position)
@@ -273,6 +274,7 @@ struct td_tokenizer {
     DevBuf sp_bytes, sp_off, sp_len, sp_id, sp_parent, sp_first2, sp_hit, sp_acc, sp_cpos, sp_clit, sp_ccount;
     uint32_t sp_n = 0, sp_maxlen = 0;
     bool sp_active = false;          // this call cuts allowed specials (set around encode_device_locked)
+    bool enc_keep_resident = false;  // (set around encode_special_strs_locked) ids that stay in d_tokens are not copied to the host as well
     bool enc_resident = false;       // the last encode_special_strs_locked left the ids and offsets it returned in d_tokens / d_offsets too
     // generic patterns with left-context assertions behind special cuts: per document of the NEXT host batch, the bytes at its
     // start that are context only (set around encode_batch_locked by encode_special_locked)
@@ -361,6 +363,13 @@ int encode_special_strs_locked(td_tokenizer* t, const uint8_t* text, const int64
 // on the handle's own stream, which `s` becomes.
 int rows_check_host_ids(td_tokenizer* t, const int32_t* ids, int64_t n_tokens, const int64_t* tok_offsets, int64_t n_docs);
 int rows_stage_host_ids(td_tokenizer* t, const int32_t* ids, const int64_t* tok_offsets, int64_t n_docs, hipStream_t& s);
+// td_encode_batch_span_label_rows: the checks of its row arguments (before the lock), and the labeled row call of sp->layout on ids
+// and labels already on the device with their offsets (h_toff: the same on the host), into the caller's host outputs.
+int label_rows_check(td_tokenizer* t, const char* fn, const td_rows_spec* sp, int64_t overlap, int64_t n_docs, const td_rows_labels* lab,
+                     const td_label_rows_outputs* o, int64_t rows_capacity);
+int label_rows_to_host(td_tokenizer* t, const void* d_ids, const void* d_src, const void* d_toff, const int64_t* h_toff, int64_t n_docs,
+                       const td_rows_spec* sp, int64_t overlap, const td_rows_labels* lab, const td_label_rows_outputs& o,
+                       int64_t rows_capacity, int64_t* counts, hipStream_t s);
 int encode_starts_locked(td_tokenizer* t, const void* d_text, int64_t n, const void* d_offs, int64_t n_docs, const void* d_tokens, int64_t cap,
                          const void* d_out_offs, int unit, void* d_starts, hipStream_t stream);
 

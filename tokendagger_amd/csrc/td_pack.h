@@ -6,6 +6,8 @@
 #include <hip/hip_runtime_api.h>
 #include <stdint.h>
 
+#include "td_rows_lab.h"
+
 #include <vector>
 
 namespace td {
@@ -67,6 +69,12 @@ struct PackArgs {
     int64_t* docs;            // [segs]
 };
 
+// What the host fills and the launchers take: PackArgs, and behind it the label stream of the pair form (lab.src null: one stream).
+// The one-stream kernels get the PackArgs slice alone, so that their arguments are what they were without the pair form.
+struct PackLabArgs : PackArgs {
+    LabArgs lab;
+};
+
 // td_pack_items: per document n_d, its full chunks and remainder, the offsets' checks and the totals into hdr.
 hipError_t launch_pack_items(const PackArgs& a, hipStream_t stream);
 // The scan of full chunks, the stable sort of (key, document) and the run-length encode of the sorted keys (unique keys at
@@ -74,6 +82,6 @@ hipError_t launch_pack_items(const PackArgs& a, hipStream_t stream);
 hipError_t pack_sort_runs(void* temp, size_t& temp_bytes, const PackArgs& a, uint32_t* key_out, uint32_t* val_out, int64_t* pref,
                           uint32_t* runs_key, uint32_t* runs_cnt, hipStream_t stream);
 // td_pack_segments then td_pack_slots.
-hipError_t launch_pack_outputs(const PackArgs& a, hipStream_t stream);
+hipError_t launch_pack_outputs(const PackLabArgs& a, hipStream_t stream);
 
 }  // namespace td

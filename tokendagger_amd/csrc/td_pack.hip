@@ -11,7 +11,8 @@
 //                     seg_docs and row_lengths come out of the same pass
 //   td_pack_slots     td_rows_concat's tile walk with segments in place of documents: a tile of 4096 output slots keeps the
 //                     starts of the segments that overlap it in LDS (at most 4097: no segment is empty), every lane searches
-//                     them once for its first slot and walks a cursor; ids are written as int4, positions only when asked for
+//                     them once for its first slot and walks a cursor; ids are written as int4, positions only when asked for;
+//                     <PackLabArgs>: the pair form, lab.src -> lab.dst beside the ids (td_rows_common.h), <PackArgs>: one stream
 #include <hip/hip_runtime.h>
 
 #include <cstring>
@@ -200,7 +201,9 @@ __device__ __forceinline__ int64_t pack_seg_search(const PackArgs& a, int64_t j)
     return lo;
 }
 
-__global__ __launch_bounds__(PACK_THREADS) void td_pack_slots(const PackArgs a) {
+template <class A>
+__global__ __launch_bounds__(PACK_THREADS) void td_pack_slots(const A a) {
+    constexpr bool LAB = has_lab<A>;
     __shared__ int32_t s_rel[PACK_TILE + 2];  // starts of the tile's segments - t0 (the first clamped to 0), then the next one's
     const int tid = threadIdx.x;
     const int64_t S = a.S, total = a.rows * S;
@@ -229,8 +232,10 @@ __global__ __launch_bounds__(PACK_THREADS) void td_pack_slots(const PackArgs a) 
             int i = lo, cur = -1;
             int64_t d = -1, start = 0, q0 = 0, base = 0, eos_at = 0;
             int32_t v[4], ps[4];
+            [[maybe_unused]] int32_t lv[4];
             for (int q = 0; q < 4; ++q) {
                 const int64_t j = j0 + q;
+                if constexpr (LAB) lv[q] = a.lab.pad;  // (what every slot without a document holds)
                 if (j >= t1) { v[q] = a.pad; ps[q] = 0; continue; }
                 while (i + 1 < nk && s_rel[i + 1] <= (int32_t)(j - t0)) ++i;
                 if (i != cur) {
@@ -247,14 +252,21 @@ __global__ __launch_bounds__(PACK_THREADS) void td_pack_slots(const PackArgs a) 
                 if (d < 0) { v[q] = a.pad; ps[q] = 0; continue; }
                 const int64_t qq = q0 + (j - start);
                 ps[q] = (int32_t)(j - start);
-                if (a.b && qq == 0) v[q] = a.bos;
-                else if (a.e && qq == eos_at) v[q] = a.eos;
-                else {
+                if (a.b && qq == 0) {
+                    v[q] = a.bos;
+                    if constexpr (LAB) lv[q] = a.lab.bos;
+                } else if (a.e && qq == eos_at) {
+                    v[q] = a.eos;
+                    if constexpr (LAB) lv[q] = a.lab.eos;
+                } else {
                     const int64_t src = base + qq - a.b;
-                    v[q] = src >= 0 && src < a.n_tokens ? a.ids[src] : a.pad;  // (always inside: the items kernel checked the offsets)
+                    const bool in = src >= 0 && src < a.n_tokens;  // (always inside: the items kernel checked the offsets)
+                    v[q] = in ? a.ids[src] : a.pad;
+                    if constexpr (LAB) if (in) lv[q] = a.lab.src[src];
                 }
             }
             rows_put4(a.out, j0, t1, v);
+            lab_put4(a, j0, t1, lv);
             if (a.pos) rows_put4(a.pos, j0, t1, ps);
         }
     }
@@ -298,12 +310,14 @@ hipError_t pack_sort_runs(void* temp, size_t& temp_bytes, const PackArgs& a, uin
     return rocprim::run_length_encode(temp, sz, key_out, n, runs_key, runs_cnt, n_runs, stream);
 }
 
-hipError_t launch_pack_outputs(const PackArgs& a, hipStream_t stream) {
+hipError_t launch_pack_outputs(const PackLabArgs& al, hipStream_t stream) {
+    const PackArgs& a = al;
     const int64_t work = a.full_rows + a.n_items + a.n_mixed + a.rows;
     hipLaunchKernelGGL(td_pack_segments, dim3(pack_grid(work, 4096)), dim3(PACK_THREADS), 0, stream, a);
     const int64_t ntiles = (a.rows * a.S + PACK_TILE - 1) / PACK_TILE;
-    if (ntiles > 0)
-        hipLaunchKernelGGL(td_pack_slots, dim3((unsigned)std::min<int64_t>(ntiles, PACK_MAX_GRID)), dim3(PACK_THREADS), 0, stream, a);
+    const dim3 grid((unsigned)std::min<int64_t>(ntiles, PACK_MAX_GRID));
+    if (ntiles > 0 && al.lab.src) hipLaunchKernelGGL(td_pack_slots<PackLabArgs>, grid, dim3(PACK_THREADS), 0, stream, al);
+    else if (ntiles > 0) hipLaunchKernelGGL(td_pack_slots<PackArgs>, grid, dim3(PACK_THREADS), 0, stream, a);
     return hipGetLastError();
 }
 

@@ -6,6 +6,8 @@
 #include <hip/hip_runtime_api.h>
 #include <stdint.h>
 
+#include "td_rows_lab.h"
+
 namespace td {
 
 constexpr int ROWS_LDS_DOCS = 4352;   // relative document bases a CONCAT tile keeps in LDS (more: the tile searches global memory)
@@ -34,9 +36,15 @@ struct RowsArgs {
     long long* err_pos;
 };
 
+// What the host fills and the launchers take: RowsArgs, and behind it the label stream of the pair form (lab.src null: one stream).
+// The one-stream kernels get the RowsArgs slice alone, so that their arguments are what they were without the pair form.
+struct RowsLabArgs : RowsArgs {
+    LabArgs lab;
+};
+
 // The slot kernel of the layout; behind it (CONCAT, aux set) the single-pass cu_seqlens scan.  The caller zeroes counts and
 // (aux set) scan[0, rows_scan_words(n_docs)) on the same stream first.
-hipError_t launch_rows(const RowsArgs& a, hipStream_t stream);
+hipError_t launch_rows(const RowsLabArgs& a, hipStream_t stream);
 int64_t rows_scan_words(int64_t n_docs);
 
 }  // namespace td

@@ -13,7 +13,8 @@
 // summed by the waiting lane itself, so the spin is bounded and the result does not depend on scheduling), and write their entries
 // load-balanced across the workgroup, so a document with many rows inside it is written by all lanes.
 //
-//   td_rows_concat / td_rows_pad   slots, positions, lengths, counts
+//   td_rows_concat / td_rows_pad   slots, positions, lengths, counts; <RowsLabArgs>: the label stream lab.src -> lab.dst beside
+//                                  the ids (td_rows_common.h), <RowsArgs>: one stream, what the kernels were before the pair form
 //   td_rows_cu                     cu_seqlens
 #include <hip/hip_runtime.h>
 
@@ -63,9 +64,12 @@ __device__ Plan rows_plan(const RowsArgs& a, bool report) {
 
 __device__ __forceinline__ int64_t doc_base(const RowsArgs& a, int64_t d, int64_t k) { return a.tok_off[d] + d * k; }
 
-// ids[src .. src + 3], 0 <= src and src + 4 <= n_tokens
-__device__ __forceinline__ int4 rows_load4(const RowsArgs& a, int64_t src) {
-    const int32_t* p = a.ids;
+// ids[src .. src + 3] (L: lab.src[src .. src + 3]; the funnel is chosen per stream), 0 <= src and src + 4 <= n_tokens
+template <bool L, class A>
+__device__ __forceinline__ int4 rows_load4(const A& a, int64_t src) {
+    const int32_t* p;
+    if constexpr (L) p = a.lab.src;
+    else p = a.ids;
     if (a.funnel_src && (((uintptr_t)p) & 15) == 0) {
         const int64_t al = src & ~(int64_t)3;
         const int sh = (int)(src & 3);
@@ -92,7 +96,9 @@ __device__ int64_t doc_search(const RowsArgs& a, int64_t lo, int64_t j, int64_t 
     return lo;
 }
 
-__global__ __launch_bounds__(ROWS_THREADS) void td_rows_concat(const RowsArgs a) {
+template <class A>
+__global__ __launch_bounds__(ROWS_THREADS) void td_rows_concat(const A a) {
+    constexpr bool LAB = has_lab<A>;
     __shared__ int32_t s_lb[ROWS_LDS_DOCS];  // bases of the tile's documents - s0, clamped to [-1, ROWS_TILE + 1]
     __shared__ long long s_red[ROWS_THREADS / 64];
     const int tid = threadIdx.x;
@@ -185,13 +191,18 @@ __global__ __launch_bounds__(ROWS_THREADS) void td_rows_concat(const RowsArgs a)
                 }
             };
             int32_t v[4], ps[4];
+            [[maybe_unused]] int32_t lv[4];
             bool fast = false;
             if (j0 + 4 <= r1) {
                 seek(j0);
                 const int64_t src = j0 - d * k - a.b;
                 if (j0 - base >= a.b && j0 + 3 < end - a.e && src >= 0 && src + 4 <= a.n_tokens) {
-                    const int4 q = rows_load4(a, src);
+                    const int4 q = rows_load4<false>(a, src);
                     v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
+                    if constexpr (LAB) {
+                        const int4 l = rows_load4<true>(a, src);
+                        lv[0] = l.x; lv[1] = l.y; lv[2] = l.z; lv[3] = l.w;
+                    }
                     fast = true;
                 }
             }
@@ -201,18 +212,26 @@ __global__ __launch_bounds__(ROWS_THREADS) void td_rows_concat(const RowsArgs a)
                 while (j >= rs + S) rs += S;
                 if (j >= r1) {
                     v[q] = a.pad;
+                    if constexpr (LAB) lv[q] = a.lab.pad;
                     ps[q] = 0;
                     continue;
                 }
                 seek(j);
                 if (!fast) {
-                    if (a.b && j == base) v[q] = a.bos;
-                    else if (a.e && j == end - 1) v[q] = a.eos;
-                    else v[q] = rows_load1(a, j - d * k - a.b);
+                    if constexpr (LAB) {
+                        if (a.b && j == base) { v[q] = a.bos; lv[q] = a.lab.bos; }
+                        else if (a.e && j == end - 1) { v[q] = a.eos; lv[q] = a.lab.eos; }
+                        else v[q] = rows_load1_pair(a, j - d * k - a.b, lv[q]);
+                    } else {
+                        if (a.b && j == base) v[q] = a.bos;
+                        else if (a.e && j == end - 1) v[q] = a.eos;
+                        else v[q] = rows_load1(a, j - d * k - a.b);
+                    }
                 }
                 ps[q] = (int32_t)(j - (base > rs ? base : rs));
             }
             rows_put4(a.out, j0, s1, v);
+            lab_put4(a, j0, s1, lv);
             if (a.pos) rows_put4(a.pos, j0, s1, ps);
         }
     }
@@ -226,7 +245,9 @@ __global__ __launch_bounds__(ROWS_THREADS) void td_rows_concat(const RowsArgs a)
     }
 }
 
-__global__ __launch_bounds__(ROWS_THREADS) void td_rows_pad(const RowsArgs a) {
+template <class A>
+__global__ __launch_bounds__(ROWS_THREADS) void td_rows_pad(const A a) {
+    constexpr bool LAB = has_lab<A>;
     __shared__ long long s_red[ROWS_THREADS / 64];
     const int tid = threadIdx.x;
     const Plan p = rows_plan(a, blockIdx.x == 0 && tid == 0);
@@ -249,11 +270,16 @@ __global__ __launch_bounds__(ROWS_THREADS) void td_rows_pad(const RowsArgs a) {
             };
             load_doc();
             int32_t v[4], ps[4];
+            [[maybe_unused]] int32_t lv[4];
             bool fast = false;
             const int64_t src = lo + o - a.b;
             if (o + 4 <= S && j0 + 4 <= s1 && o >= a.b && o + 4 <= a.b + body && src >= 0 && src + 4 <= a.n_tokens) {
-                const int4 q = rows_load4(a, src);
+                const int4 q = rows_load4<false>(a, src);
                 v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
+                if constexpr (LAB) {
+                    const int4 l = rows_load4<true>(a, src);
+                    lv[0] = l.x; lv[1] = l.y; lv[2] = l.z; lv[3] = l.w;
+                }
                 fast = true;
             }
             for (int q = 0; q < 4; ++q) {
@@ -264,10 +290,17 @@ __global__ __launch_bounds__(ROWS_THREADS) void td_rows_pad(const RowsArgs a) {
                     load_doc();
                 }
                 if (!fast) {
-                    if (o < a.b) v[q] = a.bos;
-                    else if (o < a.b + body) v[q] = rows_load1(a, lo + o - a.b);
-                    else if (a.e && o == a.b + body) v[q] = a.eos;
-                    else v[q] = a.pad;
+                    if constexpr (LAB) {
+                        if (o < a.b) { v[q] = a.bos; lv[q] = a.lab.bos; }
+                        else if (o < a.b + body) v[q] = rows_load1_pair(a, lo + o - a.b, lv[q]);
+                        else if (a.e && o == a.b + body) { v[q] = a.eos; lv[q] = a.lab.eos; }
+                        else { v[q] = a.pad; lv[q] = a.lab.pad; }
+                    } else {
+                        if (o < a.b) v[q] = a.bos;
+                        else if (o < a.b + body) v[q] = rows_load1(a, lo + o - a.b);
+                        else if (a.e && o == a.b + body) v[q] = a.eos;
+                        else v[q] = a.pad;
+                    }
                 }
                 ps[q] = o < len ? (int32_t)o : 0;
                 if (o == 0) {
@@ -278,6 +311,7 @@ __global__ __launch_bounds__(ROWS_THREADS) void td_rows_pad(const RowsArgs a) {
                 }
             }
             rows_put4(a.out, j0, s1, v);
+            lab_put4(a, j0, s1, lv);
             if (a.pos) rows_put4(a.pos, j0, s1, ps);
         }
     }
@@ -405,15 +439,21 @@ __global__ __launch_bounds__(ROWS_THREADS) void td_rows_cu(const RowsArgs a) {
 
 int64_t rows_scan_words(int64_t n_docs) { return 1 + (n_docs > 0 ? (n_docs + ROWS_SCAN_DOCS - 1) / ROWS_SCAN_DOCS : 1); }
 
-hipError_t launch_rows(const RowsArgs& a, hipStream_t stream) {
+hipError_t launch_rows(const RowsLabArgs& a, hipStream_t stream) {
     const int64_t tiles = (a.rows_cap * a.S + ROWS_TILE - 1) / ROWS_TILE;  // (the host keeps rows_cap * S far from overflow)
     const int grid = (int)(tiles < 1 ? 1 : tiles < ROWS_MAX_GRID ? tiles : ROWS_MAX_GRID);
-    if (a.layout == TD_ROWS_PAD) hipLaunchKernelGGL(td_rows_pad, dim3(grid), dim3(ROWS_THREADS), 0, stream, a);
-    else hipLaunchKernelGGL(td_rows_concat, dim3(grid), dim3(ROWS_THREADS), 0, stream, a);
+    const RowsArgs& one = a;
+    if (a.lab.src) {  // the pair form: ids and labels by one resolution of every slot
+        if (a.layout == TD_ROWS_PAD) hipLaunchKernelGGL(td_rows_pad<RowsLabArgs>, dim3(grid), dim3(ROWS_THREADS), 0, stream, a);
+        else hipLaunchKernelGGL(td_rows_concat<RowsLabArgs>, dim3(grid), dim3(ROWS_THREADS), 0, stream, a);
+    } else {
+        if (a.layout == TD_ROWS_PAD) hipLaunchKernelGGL(td_rows_pad<RowsArgs>, dim3(grid), dim3(ROWS_THREADS), 0, stream, one);
+        else hipLaunchKernelGGL(td_rows_concat<RowsArgs>, dim3(grid), dim3(ROWS_THREADS), 0, stream, one);
+    }
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     if (a.layout == TD_ROWS_CONCAT && a.aux) {
-        hipLaunchKernelGGL(td_rows_cu, dim3((unsigned)(rows_scan_words(a.n_docs) - 1)), dim3(ROWS_THREADS), 0, stream, a);
+        hipLaunchKernelGGL(td_rows_cu, dim3((unsigned)(rows_scan_words(a.n_docs) - 1)), dim3(ROWS_THREADS), 0, stream, one);
         e = hipGetLastError();
     }
     return e;

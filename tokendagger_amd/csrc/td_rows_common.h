@@ -13,6 +13,10 @@ constexpr int RC_THREADS = 256;    // lanes of a workgroup, in every kernel of t
 constexpr int RC_TILE = 4096;      // output slots a workgroup writes per tile (four int4 stores a lane)
 constexpr int RC_MAX_GRID = 2048;  // slot kernels stride over tiles with at most this many workgroups
 
+// The pair form of a slot kernel (td_*_rows_labeled*): the kernel is instantiated for the arguments WITH the label stream (RowsLabArgs,
+// PackLabArgs, WindowLabArgs: LabArgs, td_rows_lab.h), LAB = has_lab<A>.  A slot's source index is resolved once and moves both streams: ids -> out, lab.src -> lab.dst.
+// The one-stream instantiation reads none of it and compiles to what the kernel was without it.
+
 // The first error of a call wins.  A: RowsArgs or WindowArgs (err, err_pos in the handle's control block).
 template <class A>
 __device__ __forceinline__ void rows_raise(const A& a, int code, int64_t pos) {
@@ -28,6 +32,29 @@ __device__ __forceinline__ int32_t rows_load1(const A& a, int64_t src) {
     return a.pad;
 }
 
+template <class A, class = void>
+constexpr bool has_lab = false;
+template <class A>
+constexpr bool has_lab<A, decltype((void)A::lab)> = true;
+
+// Both streams at src (checked once, like rows_load1): the id returned, the label into `lab`.
+template <class A>
+__device__ __forceinline__ int32_t rows_load1_pair(const A& a, int64_t src, int32_t& lab) {
+    if (src >= 0 && src < a.n_tokens) {
+        lab = a.lab.src[src];
+        return a.ids[src];
+    }
+    rows_raise(a, TD_E_INVALID, src);
+    lab = a.lab.pad;
+    return a.pad;
+}
+
+// p[src .. src + 3] as four dwords: the sources sit at a per-document shift, misaligned three times out of four
+__device__ __forceinline__ void rows_get4(const int32_t* p, int64_t src, int32_t v[4]) {
+    p += src;
+    v[0] = p[0]; v[1] = p[1]; v[2] = p[2]; v[3] = p[3];
+}
+
 // slots [j0, j0 + 4) below `end`; int4 when aligned (j0 is a multiple of 4)
 __device__ __forceinline__ void rows_put4(int32_t* p, int64_t j0, int64_t end, const int32_t v[4]) {
     if (j0 + 4 <= end && (((uintptr_t)p) & 15) == 0) {
@@ -36,6 +63,12 @@ __device__ __forceinline__ void rows_put4(int32_t* p, int64_t j0, int64_t end, c
         for (int q = 0; q < 4; ++q)
             if (j0 + q < end) p[j0 + q] = v[q];
     }
+}
+
+// the label slots, in the pair form only
+template <class A>
+__device__ __forceinline__ void lab_put4(const A& a, int64_t j0, int64_t end, const int32_t v[4]) {
+    if constexpr (has_lab<A>) rows_put4(a.lab.dst, j0, end, v);
 }
 
 // x / d for 0 <= x < 2^63 by the multiplier the host computed, magic = floor((2^64 - 1) / d): the estimate is low by at most one

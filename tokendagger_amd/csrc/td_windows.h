@@ -7,6 +7,8 @@
 #include <hip/hip_runtime_api.h>
 #include <stdint.h>
 
+#include "td_rows_lab.h"
+
 namespace td {
 
 constexpr int WIN_LDS_DOCS = 4352;    // first rows of a tile's documents kept in LDS (a tile has at most WIN_TILE + 1 rows)
@@ -35,9 +37,15 @@ struct WindowArgs {
     long long* err_pos;
 };
 
+// What the host fills and the launchers take: WindowArgs, and behind it the label stream of the pair form (lab.src null: one stream).
+// The one-stream kernels get the WindowArgs slice alone, so that their arguments are what they were without the pair form.
+struct WindowLabArgs : WindowArgs {
+    LabArgs lab;
+};
+
 // td_win_count, td_win_chunks, td_win_first (the window counts and their scan), then td_win_slots.  The caller zeroes
 // scan[0, WIN_SCAN_HEAD) on the same stream first.
-hipError_t launch_windows(const WindowArgs& a, hipStream_t stream);
+hipError_t launch_windows(const WindowLabArgs& a, hipStream_t stream);
 int64_t windows_scan_words(int64_t n_docs);
 
 }  // namespace td

@@ -16,7 +16,8 @@
 //                   consecutive and their documents ascend: one 256-way search over first_row finds the document of the tile's
 //                   first row (inside [r - (rows - n_docs), r]: first_row[d] - d never decreases, so without a split document
 //                   the search is no step at all), the first rows of the tile's documents go to LDS, and a lane finds its row's
-//                   document there.  The tile in which a row starts writes the row's length, document and start.
+//                   document there.  The tile in which a row starts writes the row's length, document and start.  <WindowLabArgs>:
+//                   the pair form, lab.src -> lab.dst beside the ids and the overlap mask (td_rows_common.h); <WindowArgs>: one stream.
 //
 // td_win_slots reads first_row[n_docs] itself (a kernel boundary lies behind td_win_chunks): above the capacity, or -1, it
 // leaves without a store.
@@ -178,7 +179,9 @@ __global__ __launch_bounds__(WIN_THREADS) void td_win_first(const WindowArgs a) 
     }
 }
 
-__global__ __launch_bounds__(WIN_THREADS) void td_win_slots(const WindowArgs a) {
+template <class A>
+__global__ __launch_bounds__(WIN_THREADS) void td_win_slots(const A a) {
+    constexpr bool LAB = has_lab<A>;
     __shared__ int32_t s_fr[WIN_LDS_DOCS];  // first rows of the tile's documents - r0, clamped to [-1, WIN_TILE + 2]
     const int tid = threadIdx.x;
     const int64_t rows = a.first_row[a.n_docs];
@@ -241,11 +244,13 @@ __global__ __launch_bounds__(WIN_THREADS) void td_win_slots(const WindowArgs a) 
             };
             load_row();
             int32_t v[4], ps[4];
+            [[maybe_unused]] int32_t lv[4];
             bool fast = false;
             const int64_t src = tlo + start + o - a.b;
             if (o + 4 <= S && j0 + 4 <= s1 && o >= a.b && o + 4 <= a.b + body && src >= 0 && src + 4 <= a.n_tokens) {
                 const int32_t* p = a.ids + src;  // (four dwords: the sources are misaligned three times out of four)
                 v[0] = p[0]; v[1] = p[1]; v[2] = p[2]; v[3] = p[3];
+                if constexpr (LAB) rows_get4(a.lab.src, src, lv);
                 fast = true;
             }
             for (int q = 0; q < 4; ++q) {
@@ -256,7 +261,16 @@ __global__ __launch_bounds__(WIN_THREADS) void td_win_slots(const WindowArgs a) 
                     if (i + 1 < nl && s_fr[i + 1] <= (int32_t)(r - r0)) ++i;
                     load_row();
                 }
-                if (!fast) {
+                if constexpr (LAB) {
+                    if (!fast) {
+                        if (o < a.b) { v[q] = a.bos; lv[q] = a.lab.bos; }
+                        else if (o < a.b + body) v[q] = rows_load1_pair(a, tlo + start + o - a.b, lv[q]);
+                        else if (a.e && o == a.b + body) { v[q] = a.eos; lv[q] = a.lab.eos; }
+                        else { v[q] = a.pad; lv[q] = a.lab.pad; }
+                    }
+                    // the ids a window k > 0 repeats: body slots [0, overlap), all below its body (body > overlap there)
+                    if (a.lab.mask_overlap && start > 0 && o >= a.b && o < a.b + a.overlap && o < a.b + body) lv[q] = a.lab.pad;
+                } else if (!fast) {
                     if (o < a.b) v[q] = a.bos;
                     else if (o < a.b + body) v[q] = rows_load1(a, tlo + start + o - a.b);
                     else if (a.e && o == a.b + body) v[q] = a.eos;
@@ -270,6 +284,7 @@ __global__ __launch_bounds__(WIN_THREADS) void td_win_slots(const WindowArgs a) 
                 }
             }
             rows_put4(a.out, j0, s1, v);
+            lab_put4(a, j0, s1, lv);
             if (a.pos) rows_put4(a.pos, j0, s1, ps);
         }
     }
@@ -279,7 +294,8 @@ __global__ __launch_bounds__(WIN_THREADS) void td_win_slots(const WindowArgs a) 
 
 int64_t windows_scan_words(int64_t n_docs) { return WIN_SCAN_HEAD + (n_docs > 0 ? (n_docs + WIN_SCAN_DOCS - 1) / WIN_SCAN_DOCS : 1); }
 
-hipError_t launch_windows(const WindowArgs& a, hipStream_t stream) {
+hipError_t launch_windows(const WindowLabArgs& al, hipStream_t stream) {
+    const WindowArgs& a = al;
     const int64_t nch = windows_scan_words(a.n_docs) - WIN_SCAN_HEAD;
     hipLaunchKernelGGL(td_win_count, dim3((unsigned)nch), dim3(WIN_THREADS), 0, stream, a);
     hipError_t e = hipGetLastError();
@@ -290,7 +306,8 @@ hipError_t launch_windows(const WindowArgs& a, hipStream_t stream) {
     if ((e = hipGetLastError()) != hipSuccess) return e;
     const int64_t tiles = (a.rows_cap * a.S + WIN_TILE - 1) / WIN_TILE;  // (the host keeps rows_cap * S far from overflow)
     const int grid = (int)(tiles < 1 ? 1 : tiles < WIN_MAX_GRID ? tiles : WIN_MAX_GRID);
-    hipLaunchKernelGGL(td_win_slots, dim3(grid), dim3(WIN_THREADS), 0, stream, a);
+    if (al.lab.src) hipLaunchKernelGGL(td_win_slots<WindowLabArgs>, dim3(grid), dim3(WIN_THREADS), 0, stream, al);
+    else hipLaunchKernelGGL(td_win_slots<WindowArgs>, dim3(grid), dim3(WIN_THREADS), 0, stream, a);
     return hipGetLastError();
 }
 

@@ -56,6 +56,13 @@ class WindowRows(NamedTuple):
     counts: np.ndarray              # int64 [4]: rows, real slots, documents with more than one window, the most windows of one
 
 
+class LabeledRows(NamedTuple):
+    """Trainer-ready rows: the id rows of a layout and the label rows placed beside them in the same pass
+    (Tokenizer.ids_to_labeled_rows / encode_batch_to_labeled_rows; the contract: include/tokendagger_hip.h, td_rows_labels)."""
+    rows: "Rows | PackedRows | WindowRows"  # the layout's own rows
+    labels: np.ndarray                      # int32 [rows, seq_len]
+
+
 class Labels(NamedTuple):
     """Loss labels for marked id spans (Tokenizer.ids_to_labels / encode_batch_to_labels; the contract:
     include/tokendagger_hip.h, td_labels_spec)."""
@@ -468,6 +475,76 @@ class Tokenizer:
                                                         trained_offsets=trained_offsets))
         except _capi.TokenDaggerHipError as ex:
             raise TokenDaggerError(f"Encoding failed: {ex}")
+
+    # ------------------------------------------------------------------ label rows -------------
+    # (input_ids, labels) rows in one pass: `labels` is a stream index-aligned with the ids (ids_to_labels gives one) and is placed by
+    # the placement of the ids.  Where the id rows hold the inserted BOS / EOS / a pad slot the label rows hold label_bos /
+    # label_eos (None: the EOS id itself, so that the model learns to stop) / label_pad.  mask_overlap (windows): the ids a window
+    # repeats from the one before are label_pad, so every id is trained in exactly one row.
+    _ROW_LAYOUTS = {"concat": 0, "pad": 1, "bestfit": 2, "windows": 3}
+
+    def _labeled_args(self, seq_len, layout, bos, eos, pad, label_bos, label_eos, label_pad, overlap, mask_overlap, drop_last, truncate):
+        if layout not in self._ROW_LAYOUTS:
+            raise ValueError(f"layout must be one of {sorted(self._ROW_LAYOUTS)}, not {layout!r}")
+        if mask_overlap and layout != "windows":
+            raise ValueError("mask_overlap is for layout='windows'")
+        if overlap and layout != "windows":
+            raise ValueError("overlap is for layout='windows'")
+        if drop_last and layout != "concat":
+            raise ValueError("drop_last is for layout='concat'")
+        if truncate and layout != "bestfit":
+            raise ValueError("truncate is for layout='bestfit'")
+        _, b, e, p, no_pad = self._rows_args(seq_len, "concat", bos, eos, pad)
+        lay = self._ROW_LAYOUTS[layout]
+        flags = (_capi.TD_ROWS_DROP_LAST if drop_last else 0) | (_capi.TD_ROWS_TRUNCATE if truncate else 0)
+        le = int(label_eos) if label_eos is not None else (e if e >= 0 else int(label_pad))
+        return lay, b, e, p, no_pad, flags, int(label_bos), le, int(label_pad), _capi.TD_ROWLAB_MASK_OVERLAP if mask_overlap else 0
+
+    def _labeled(self, lay: int, seq_len: int, no_pad: bool, r) -> LabeledRows:
+        *head, lab = r
+        rows = self._rows(head, lay, seq_len, no_pad) if lay < 2 else self._packed(head, no_pad) if lay == 2 else self._windows(head, no_pad)
+        return LabeledRows(rows, lab)
+
+    def ids_to_labeled_rows(self, ids: np.ndarray, labels: np.ndarray, tok_offsets: np.ndarray, seq_len: int, *, layout: str = "concat",
+                            bos=None, eos=None, pad=None, label_bos: int = -100, label_eos=None, label_pad: int = -100, overlap: int = 0,
+                            mask_overlap: bool = False, drop_last: bool = False, truncate: bool = False, positions: bool = False,
+                            cu_seqlens: bool = True, docs: bool = False) -> LabeledRows:
+        """Id rows and label rows from ids already encoded and a label stream aligned with them (one call, one pass)."""
+        lay, b, e, p, no_pad, flags, lb, le, lp, lflags = self._labeled_args(seq_len, layout, bos, eos, pad, label_bos, label_eos, label_pad,
+                                                                              overlap, mask_overlap, drop_last, truncate)
+        try:
+            r = self._core_bpe.ids_to_labeled_rows(np.asarray(ids, dtype=np.int32), np.asarray(labels, dtype=np.int32),
+                                                   np.asarray(tok_offsets, dtype=np.int64), seq_len, lay, int(overlap), b, e, p, flags, lb, le, lp,
+                                                   lflags, positions, cu_seqlens or lay == 1, True, docs or lay == 3, True)
+        except Exception as ex:
+            raise TokenDaggerError(f"Making labeled rows failed: {ex}")
+        return self._labeled(lay, seq_len, no_pad, r)
+
+    def encode_batch_to_labeled_rows(self, text: np.ndarray | bytes, offsets: np.ndarray, seq_len: int, *, layout: str = "concat", open, close,
+                                     allowed_special: Literal["all"] | AbstractSet[str] = "all", ignore_index: int = -100,
+                                     train_close: bool = True, bos=None, eos=None, pad=None, label_bos=None, label_eos=None, label_pad=None,
+                                     overlap: int = 0, mask_overlap: bool = False, drop_last: bool = False, truncate: bool = False,
+                                     positions: bool = False, cu_seqlens: bool = True, docs: bool = False) -> LabeledRows:
+        """Chat text straight to id rows and label rows (one call): encode_batch_to_labels then ids_to_labeled_rows, with the ids and
+        the labels staying on the device in between.  label_bos / label_pad default to ignore_index.  The exception of a capacity
+        error carries .counts (counts[0]: the rows needed)."""
+        hip, lspec = self._labels_spec(open, close, ignore_index, train_close)
+        lay, b, e, p, no_pad, flags, lb, le, lp, lflags = self._labeled_args(
+            seq_len, layout, bos, eos, pad, ignore_index if label_bos is None else label_bos, label_eos,
+            ignore_index if label_pad is None else label_pad, overlap, mask_overlap, drop_last, truncate)
+        allowed = sorted(self._special_tokens) if allowed_special == "all" else sorted(allowed_special)
+        buf = np.frombuffer(text, dtype=np.uint8) if isinstance(text, (bytes, bytearray)) else text
+        rspec = _capi.RowsSpec(lay, seq_len, b, e, p, flags)
+        lab = _capi.rows_labels(0, 0, lb, le, lp, flags=lflags)
+        try:
+            r = hip.encode_batch_span_label_rows(buf, np.asarray(offsets, dtype=np.int64), allowed, lspec, rspec, lab, overlap=int(overlap),
+                                                 positions=positions, aux=cu_seqlens or lay == 1, lengths=True, docs=docs or lay == 3,
+                                                 starts=True)
+        except _capi.TokenDaggerHipError as ex:
+            err = TokenDaggerError(f"Encoding failed: {ex}")
+            err.counts = getattr(ex, "counts", None)
+            raise err
+        return self._labeled(lay, seq_len, no_pad, r[:-1])
 
     # ------------------------------------------------------------------ decoding ---------------
     def decode_bytes(self, tokens: Sequence[int]) -> bytes:
