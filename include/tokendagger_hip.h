@@ -434,6 +434,59 @@ int td_window_rows_labeled_device(td_tokenizer* t, const void* d_ids, int64_t n_
                                   const td_rows_spec* spec, int64_t overlap, const td_window_outputs* dev_out, int64_t rows_capacity,
                                   void* d_counts, void* hip_stream, const td_rows_labels* lab);
 
+/* ---- document selection: choose, reorder, repeat and length-filter encoded documents (td_select.hip) ---------------------------
+ * Every call above consumes ids[n_tokens] + tok_offsets[n_docs + 1] "concatenated in document order".  This one changes the
+ * order and the choice without leaving the device, and its output is again ids + tok_offsets: it composes with every row layout
+ * and with the label stream.  A gather: no randomness is made here and no document is cut; the order is the caller's list, and
+ * the result is a pure function of the inputs.
+ *   L_d = tok_offsets[d + 1] - tok_offsets[d].
+ *   sel[n_sel] (int64): document indices in the order the output is to have them.  Repeats are allowed (a document listed twice
+ *   appears twice) and n_sel may exceed n_docs.  sel == NULL is the identity 0 .. n_docs - 1 and requires n_sel == n_docs.
+ *   Entry i is KEPT iff min_len <= L_sel[i] and (max_len < 0 or L_sel[i] <= max_len).  K = the kept entries, i_0 < ... < i_{K-1}.
+ *     out_docs[k] = sel[i_k]                                               int64, K written; the pointer may be NULL
+ *     out_offsets[0] = 0, out_offsets[k + 1] = out_offsets[k] + L_out_docs[k]   int64, room for n_sel + 1, K + 1 written
+ *     out_ids[out_offsets[k] + q] = ids[tok_offsets[out_docs[k]] + q]       int32, room for ids_capacity, T = out_offsets[K] written
+ *     out_labels[...] = labels[...] by the same indices: an optional second int32 stream labels[n_tokens] (e.g. td_span_labels'),
+ *                       both pointers NULL or both given; moved in the same pass by the same resolved source
+ *     counts[4] (int64) = {K, T, entries dropped below min_len, entries dropped above max_len}; [0] + [2] + [3] = n_sel.
+ *   Errors:
+ *     a bad spec (min_len < 0, max_len < -1, 0 <= max_len < min_len, flags != 0) and sel == NULL with n_sel != n_docs:
+ *       TD_E_INVALID before any launch;
+ *     sel[i] outside [0, n_docs), or offsets of document sel[i] that are not 0 <= lo <= hi <= n_tokens: TD_E_INVALID with
+ *       position i.  Only the offsets of listed documents are looked at; no id outside [0, n_tokens) is ever read;
+ *     T > ids_capacity: TD_E_CAPACITY with counts[1] = T.
+ *   On any error nothing is written to out_ids, out_labels, out_offsets or out_docs (the rule of the row calls).
+ *   out_ids must not alias ids (nor out_labels labels): selecting in place is not supported. */
+typedef struct td_select_spec {
+    int64_t min_len; /* >= 0: listed documents with L < min_len are dropped */
+    int64_t max_len; /* -1: no limit; otherwise >= min_len: listed documents with L > max_len are dropped */
+    int64_t flags;   /* 0 */
+} td_select_spec;
+
+/* The contract's executable statement, on the host, from tok_offsets alone (no handle, no device): counts, and out_offsets
+ * [n_sel + 1] and out_docs [n_sel] where not NULL.  Argument errors (a NULL tok_offsets / spec / counts, negative sizes, a bad
+ * spec, sel == NULL with n_sel != n_docs) are TD_E_INVALID with counts[0] = -1; a bad entry i (sel[i] outside [0, n_docs), or
+ * offsets of its document that are negative or decrease) is TD_E_INVALID with counts[0] = i.  Nothing else is written then. */
+int td_select_plan(const int64_t* tok_offsets, int64_t n_docs, const int64_t* sel, int64_t n_sel, const td_select_spec* spec,
+                   int64_t* counts, int64_t* out_offsets, int64_t* out_docs);
+/* DEVICE buffers, asynchronously on hip_stream: no synchronisation and no read-back.  d_counts (4 int64) is device memory.
+ * Errors surface through td_device_status: TD_E_INVALID with err_pos = a bad entry i, TD_E_CAPACITY with err_pos = T (and
+ * counts[1] = T). */
+int td_select_docs_device(td_tokenizer* t, const void* d_ids, const void* d_labels, int64_t n_tokens, const void* d_tok_offsets,
+                          int64_t n_docs, const void* d_sel, int64_t n_sel, const td_select_spec* spec, void* d_out_ids,
+                          void* d_out_labels, int64_t ids_capacity, void* d_out_offsets, void* d_out_docs, void* d_counts,
+                          void* hip_stream);
+/* Host buffers, synchronously.  tok_offsets is checked like every host entry point's offsets.  T is known on the host (the
+ * plan): a capacity below it fails before any launch.  td_last_error names a bad entry's position. */
+int td_select_docs(td_tokenizer* t, const int32_t* ids, const int32_t* labels, int64_t n_tokens, const int64_t* tok_offsets,
+                   int64_t n_docs, const int64_t* sel, int64_t n_sel, const td_select_spec* spec, int32_t* out_ids,
+                   int32_t* out_labels, int64_t ids_capacity, int64_t* out_offsets, int64_t* out_docs, int64_t* counts);
+/* td_encode_batch (TD_MODE_ENCODE / TD_MODE_ORDINARY, no allowed special tokens) and td_select_docs in one call, "tokenize, then
+ * drop what is too short": the ids stay on the device between the two.  sel indexes the documents of doc_offsets.  Synchronous. */
+int td_encode_batch_select(td_tokenizer* t, const uint8_t* text, const int64_t* doc_offsets, int64_t n_docs, int mode,
+                           const int64_t* sel, int64_t n_sel, const td_select_spec* spec, int32_t* out_ids, int64_t ids_capacity,
+                           int64_t* out_offsets, int64_t* out_docs, int64_t* counts);
+
 /* ---- loss labels: train only inside marked id spans (td_labels.hip) ----------------------------------------------------------
  * ids + per-document token offsets -> labels[i] = ids[i] where the loss applies, ignore_index everywhere else.  The rule knows
  * no chat template: a span is opened by an opener id SEQUENCE (e.g. the three ids of <|header_start|>assistant<|header_end|>)

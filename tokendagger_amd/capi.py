@@ -62,6 +62,7 @@ EXPORTS = [
     "td_span_labels", "td_span_labels_device", "td_encode_batch_span_labels",
     "td_make_rows_labeled", "td_make_rows_labeled_device", "td_pack_rows_labeled", "td_pack_rows_labeled_device",
     "td_window_rows_labeled", "td_window_rows_labeled_device", "td_encode_batch_span_label_rows",
+    "td_select_plan", "td_select_docs", "td_select_docs_device", "td_encode_batch_select",
 ]
 
 
@@ -153,6 +154,14 @@ def load_library():
         getattr(lib, fn).argtypes = [*base.argtypes, vp]  # (the counterpart's signature and a trailing td_rows_labels)
     lib.td_encode_batch_span_label_rows.restype = i32
     lib.td_encode_batch_span_label_rows.argtypes = [vp, vp, vp, i64, vp, vp, i64, vp, vp, i64, vp, vp, i64, vp, vp]
+    lib.td_select_plan.restype = i32
+    lib.td_select_plan.argtypes = [vp, i64, vp, i64, vp, vp, vp, vp]
+    lib.td_select_docs_device.restype = i32
+    lib.td_select_docs_device.argtypes = [vp, vp, vp, i64, vp, i64, vp, i64, vp, vp, vp, i64, vp, vp, vp, vp]
+    lib.td_select_docs.restype = i32
+    lib.td_select_docs.argtypes = [vp, vp, vp, i64, vp, i64, vp, i64, vp, vp, vp, i64, vp, vp, vp]
+    lib.td_encode_batch_select.restype = i32
+    lib.td_encode_batch_select.argtypes = [vp, vp, vp, i64, i32, vp, i64, vp, vp, i64, vp, vp, vp]
     lib.td_comm_unique_id.restype = i32
     lib.td_comm_unique_id.argtypes = [vp]
     lib.td_comm_create.restype = i32
@@ -346,6 +355,49 @@ class LabelRowsOutputs(ctypes.Structure):
 
 
 TD_LABELS_MAX_OPEN, TD_LABELS_MAX_OPEN_LEN, TD_LABELS_MAX_CLOSE, TD_LABELS_TRAIN_CLOSE = 8, 8, 16, 1
+
+
+class SelectSpec(ctypes.Structure):
+    """td_select_spec (include/tokendagger_hip.h)."""
+    _fields_ = [("min_len", ctypes.c_int64), ("max_len", ctypes.c_int64), ("flags", ctypes.c_int64)]
+
+
+def select_spec(min_len: int = 0, max_len: int | None = None, flags: int = 0) -> SelectSpec:
+    """Listed documents with fewer than min_len or more than max_len ids are dropped; max_len None (or -1): no limit."""
+    return SelectSpec(min_len, -1 if max_len is None else max_len, flags)
+
+
+def _sel_array(sel):
+    if sel is None:
+        return None
+    a = np.ascontiguousarray(sel, dtype=np.int64)
+    return a if a.size else np.zeros(1, dtype=np.int64)[:0]  # (an empty list is not the identity: its address is not NULL)
+
+
+def select_plan(tok_offsets, sel=None, spec: SelectSpec | None = None, outputs: bool = True):
+    """td_select_plan (host only, no device): counts int64[4] = kept entries K, kept ids T, entries dropped below min_len, above
+    max_len; with outputs=True also out_offsets int64[K + 1] and out_docs int64[K].  sel None: the identity.  An error carries
+    .counts ([0]: the position of a bad entry, -1 for an argument error)."""
+    lib = load_library()
+    spec = spec if spec is not None else select_spec()
+    o = np.ascontiguousarray(tok_offsets, dtype=np.int64)
+    n_docs = len(o) - 1
+    if n_docs < 0:
+        raise ValueError("tok_offsets must have n_docs + 1 entries")
+    sl = _sel_array(sel)
+    n_sel = n_docs if sl is None else len(sl)
+    counts = np.zeros(4, dtype=np.int64)
+    offs = np.empty(n_sel + 1, dtype=np.int64) if outputs else None
+    docs = np.empty(max(n_sel, 1), dtype=np.int64) if outputs else None
+    rc = lib.td_select_plan(o.ctypes.data, n_docs, sl.ctypes.data if sl is not None else None, n_sel, ctypes.byref(spec), counts.ctypes.data,
+                            offs.ctypes.data if outputs else None, docs.ctypes.data if outputs else None)
+    if rc != TD_OK:
+        ex = TokenDaggerHipError(rc, "td_select_plan: invalid spec or arguments" if counts[0] < 0 else
+                                 f"td_select_plan: sel[{int(counts[0])}] is not a document in 0 .. n_docs - 1 with valid offsets")
+        ex.counts = counts
+        raise ex
+    k = int(counts[0])
+    return (counts, offs[:k + 1], docs[:k]) if outputs else counts
 
 
 class LabelsSpec(ctypes.Structure):
@@ -928,6 +980,71 @@ class HipTokenizer:
         self._check_counts(rc, counts)
         r = int(counts[0])
         return (*self._rows_result(kind, rspec, b, counts, n_docs), dst[:r * S].reshape(r, S).copy(), lcounts)
+
+    # ---- document selection (td_select_spec) ------------------------------------------------------------------
+    def select_docs(self, ids, tok_offsets, sel=None, spec: SelectSpec | None = None, labels=None, docs: bool = True,
+                    ids_capacity: int | None = None):
+        """td_select_docs -> (ids int32[T], labels int32[T] | None, offsets int64[K + 1], docs int64[K] | None, counts int64[4]).
+        sel None: the identity; labels: a second int32 stream moved by the same indices.  The default capacity is the exact T
+        (td_select_plan).  An error carries .counts (TD_E_CAPACITY: counts[1] = the ids needed)."""
+        spec = spec if spec is not None else select_spec()
+        t = np.ascontiguousarray(ids, dtype=np.int32)
+        o = np.ascontiguousarray(tok_offsets, dtype=np.int64)
+        lab = None if labels is None else np.ascontiguousarray(labels, dtype=np.int32)
+        if lab is not None and len(lab) != len(t):
+            raise ValueError("labels must have one entry per id")
+        n_docs = len(o) - 1
+        sl = _sel_array(sel)
+        n_sel = n_docs if sl is None else len(sl)
+        cap = ids_capacity if ids_capacity is not None else int(select_plan(o, sl, spec, outputs=False)[1])
+        out = np.empty(max(cap, 1), dtype=np.int32)
+        out_lab = np.empty(max(cap, 1), dtype=np.int32) if lab is not None else None
+        offs = np.empty(n_sel + 1, dtype=np.int64)
+        dcs = np.empty(max(n_sel, 1), dtype=np.int64) if docs else None
+        counts = np.zeros(4, dtype=np.int64)
+        rc = self._lib.td_select_docs(self._h, t.ctypes.data if len(t) else None, lab.ctypes.data if lab is not None else None, len(t),
+                                      o.ctypes.data, n_docs, sl.ctypes.data if sl is not None else None, n_sel, ctypes.byref(spec),
+                                      out.ctypes.data, out_lab.ctypes.data if lab is not None else None, cap, offs.ctypes.data,
+                                      dcs.ctypes.data if docs else None, counts.ctypes.data)
+        self._check_counts(rc, counts)
+        k, n = int(counts[0]), int(counts[1])
+        return out[:n], (out_lab[:n] if lab is not None else None), offs[:k + 1], (dcs[:k] if docs else None), counts
+
+    def select_docs_device(self, d_ids: int, n_tokens: int, d_tok_offsets: int, n_docs: int, d_sel: int, n_sel: int, spec: SelectSpec,
+                           d_out_ids: int, ids_capacity: int, d_out_offsets: int, d_out_docs: int = 0, d_counts: int = 0, d_labels: int = 0,
+                           d_out_labels: int = 0, stream: int = 0):
+        """td_select_docs_device: raw device pointers (d_sel 0: the identity), asynchronous on `stream`; check with device_status(stream)."""
+        self._check(self._lib.td_select_docs_device(self._h, d_ids or None, d_labels or None, n_tokens, d_tok_offsets, n_docs, d_sel or None,
+                                                    n_sel, ctypes.byref(spec), d_out_ids or None, d_out_labels or None, ids_capacity,
+                                                    d_out_offsets or None, d_out_docs or None, d_counts or None, stream or None))
+
+    def encode_batch_select(self, text, doc_offsets, sel=None, spec: SelectSpec | None = None, mode: int = TD_MODE_ENCODE, docs: bool = True,
+                            ids_capacity: int | None = None):
+        """td_encode_batch_select: encode + td_select_docs in one call -> (ids, offsets, docs | None, counts).  The default capacity
+        is the most ids the listed documents can have (one per byte)."""
+        spec = spec if spec is not None else select_spec()
+        buf = _as_u8(text)
+        offs = np.ascontiguousarray(doc_offsets, dtype=np.int64)
+        n_docs = len(offs) - 1
+        sl = _sel_array(sel)
+        n_sel = n_docs if sl is None else len(sl)
+        if ids_capacity is not None:
+            cap = ids_capacity
+        elif sl is None:
+            cap = int(offs[-1]) if len(offs) else 0
+        else:
+            ok = sl[(sl >= 0) & (sl < n_docs)]
+            cap = int(np.diff(offs)[ok].sum())
+        out = np.empty(max(cap, 1), dtype=np.int32)
+        o_out = np.empty(n_sel + 1, dtype=np.int64)
+        dcs = np.empty(max(n_sel, 1), dtype=np.int64) if docs else None
+        counts = np.zeros(4, dtype=np.int64)
+        rc = self._lib.td_encode_batch_select(self._h, buf.ctypes.data if len(buf) else None, offs.ctypes.data, n_docs, mode,
+                                              sl.ctypes.data if sl is not None else None, n_sel, ctypes.byref(spec), out.ctypes.data, cap,
+                                              o_out.ctypes.data, dcs.ctypes.data if docs else None, counts.ctypes.data)
+        self._check_counts(rc, counts)
+        k, n = int(counts[0]), int(counts[1])
+        return out[:n], o_out[:k + 1], (dcs[:k] if docs else None), counts
 
     def device_status_pos(self, stream: int = 0) -> tuple[int, int]:
         """td_device_status without raising: (code, err_pos)."""

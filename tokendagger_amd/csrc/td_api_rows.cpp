@@ -1,10 +1,12 @@
-// Per-token starts (td_offsets.hip) and the four row layouts (td_rows.hip, td_pack.hip, td_windows.hip): one host path.
+// Per-token starts (td_offsets.hip), the four row layouts (td_rows.hip, td_pack.hip, td_windows.hip) and the document selection
+// in front of them (td_select.hip): one host path.
 #include <type_traits>
 
 #include "td_handle.h"
 #include "td_offsets.h"
 #include "td_pack.h"
 #include "td_rows.h"
+#include "td_select.h"
 #include "td_windows.h"
 
 namespace {
@@ -959,6 +961,193 @@ int td_encode_batch_window_rows(td_tokenizer* t, const uint8_t* text, const int6
         if (td_window_plan(toff.data(), n_docs, spec, overlap, plan, nullptr) != TD_OK) { t->err = "invalid token offsets"; return (int)TD_E_INVALID; }
         if (plan[0] > rows_capacity) return rows_capacity_fail(t, plan[0], counts);
         return window_to_host(t, t->d_tokens.p, dev_cap, t->d_offsets.p, n_docs, spec, overlap, *host_out, plan[0], counts, LabCall{}, s);
+    });
+}
+
+}  // extern "C"
+
+// ---- document selection (td_select.hip) ---------------------------------------------------------------------------------------
+namespace {
+
+const char* select_spec_error(const td_select_spec* sp, const void* sel, int64_t n_sel, int64_t n_docs) {
+    if (!sp) return "null td_select_spec";
+    if (sp->min_len < 0) return "min_len must be >= 0";
+    if (sp->max_len < -1) return "max_len must be -1 (no limit) or >= min_len";
+    if (sp->max_len >= 0 && sp->max_len < sp->min_len) return "max_len must be -1 (no limit) or >= min_len";
+    if (sp->flags != 0) return "flags must be 0";
+    if (!sel && n_sel != n_docs) return "a null sel is the identity: n_sel must be n_docs";
+    return nullptr;
+}
+
+// Enqueues the scan and the slot kernel; every pointer is device memory.  d_labels / d_out_labels: both null, or the second stream.
+int select_launch_locked(td_tokenizer* t, const void* d_ids, const void* d_labels, int64_t n_tokens, const void* d_toff, int64_t n_docs,
+                         const void* d_sel, int64_t n_sel, const td_select_spec* sp, void* d_out, void* d_out_labels, int64_t cap,
+                         void* d_out_off, void* d_out_docs, void* d_counts, hipStream_t s) {
+    int rc;
+    if ((rc = order_before(t, s))) return rc;  // (rows_last stays false: a capacity here counts ids)
+    SelectLabArgs a;
+    memset(&a, 0, sizeof a);
+    a.ids = (const int32_t*)d_ids;
+    a.n_tokens = n_tokens;
+    a.tok_off = (const int64_t*)d_toff;
+    a.n_docs = n_docs;
+    a.sel = (const int64_t*)d_sel;
+    a.n_sel = n_sel;
+    a.min_len = sp->min_len;
+    a.max_len = sp->max_len;
+    a.out = (int32_t*)d_out;
+    a.ids_cap = cap;
+    a.out_off = (int64_t*)d_out_off;
+    a.out_docs = (int64_t*)d_out_docs;
+    a.counts = (long long*)d_counts;
+    a.lab.src = (const int32_t*)d_labels;
+    a.lab.dst = (int32_t*)d_out_labels;
+    if ((rc = ensure(t, t->sel_scan, (size_t)select_scan_words(n_sel) * 8))) return rc;
+    if ((rc = ensure(t, t->sel_base, (size_t)std::max<int64_t>(n_sel, 1) * 8))) return rc;
+    a.scan = (unsigned long long*)t->sel_scan.p;
+    a.src_base = (int64_t*)t->sel_base.p;
+    HIP_TRY(t, hipMemsetAsync(a.scan, 0, SEL_SCAN_HEAD * 8, s));
+    Ctl* ctl = (Ctl*)t->ctl.p;
+    a.err = &ctl->err;
+    a.err_pos = &ctl->err_pos;
+    HIP_TRY(t, launch_select(a, s));
+    return order_after(t, s);
+}
+
+// Host entry points: the plan on the host offsets h_toff, counts and the errors before any launch.
+int select_plan_host(td_tokenizer* t, const int64_t* h_toff, int64_t n_docs, const int64_t* sel, int64_t n_sel, const td_select_spec* sp,
+                     const int32_t* out_ids, int64_t cap, int64_t* counts) {
+    if (td_select_plan(h_toff, n_docs, sel, n_sel, sp, counts, nullptr, nullptr) != TD_OK) {
+        t->err = "sel[" + std::to_string(counts[0]) + "] is not a document in 0 .. n_docs - 1 with valid offsets";
+        return TD_E_INVALID;
+    }
+    if (counts[1] > cap) {
+        t->err = "output capacity too small: " + std::to_string(counts[1]) + " tokens needed";
+        return TD_E_CAPACITY;
+    }
+    if (counts[1] > 0 && !out_ids) { t->err = "null out_ids"; return TD_E_INVALID; }
+    return TD_OK;
+}
+
+// ... and behind it and the staging: the list up, the selection (counts: the plan's K and T) from ids (and lc's label stream)
+// already on the device into the handle's buffers, then to the caller's.
+int select_to_host(td_tokenizer* t, const void* d_ids, int64_t n_ids, const void* d_toff, int64_t n_docs, const int64_t* sel, int64_t n_sel,
+                   const td_select_spec* sp, int32_t* out_ids, int64_t* out_offsets, int64_t* out_docs, int64_t* counts, const LabCall& lc,
+                   hipStream_t s) {
+    int rc;
+    const int64_t K = counts[0], T = counts[1];
+    if (sel) {
+        if ((rc = ensure(t, t->sel_in, (size_t)std::max<int64_t>(n_sel, 1) * 8))) return rc;
+        if (n_sel > 0) HIP_TRY(t, hipMemcpyAsync(t->sel_in.p, sel, (size_t)n_sel * 8, hipMemcpyHostToDevice, s));
+    }
+    const RowsOut o[] = {{true, out_ids, &t->rows_out, 4, T, T},
+                         {lc.spec != nullptr, lc.dst, &t->rows_lab, 4, T, T},
+                         {true, out_offsets, &t->sel_off, 8, n_sel + 1, K + 1},
+                         {out_docs != nullptr, out_docs, &t->sel_docs, 8, n_sel, K}};
+    if ((rc = rows_out_ensure(t, o, 4))) return rc;
+    if ((rc = ensure(t, t->rows_counts, 4 * sizeof(int64_t)))) return rc;
+    if ((rc = select_launch_locked(t, d_ids, lc.d_src, n_ids, d_toff, n_docs, sel ? t->sel_in.p : nullptr, n_sel, sp, o[0].p(), o[1].p(), T,
+                                   o[2].p(), o[3].p(), t->rows_counts.p, s)))
+        return rc;
+    if ((rc = device_status_locked(t, s, nullptr))) return rc;
+    if ((rc = copy_wait(t, counts, t->rows_counts.p, 4 * sizeof(int64_t), hipMemcpyDeviceToHost, s))) return rc;
+    return rows_out_copy(t, o, 4, s);
+}
+
+}  // namespace
+
+extern "C" {
+
+int td_select_plan(const int64_t* tok_offsets, int64_t n_docs, const int64_t* sel, int64_t n_sel, const td_select_spec* spec,
+                   int64_t* counts, int64_t* out_offsets, int64_t* out_docs) {
+    if (!counts) return TD_E_INVALID;
+    counts[0] = -1;
+    counts[1] = counts[2] = counts[3] = 0;
+    if (!tok_offsets || n_docs < 0 || n_sel < 0 || select_spec_error(spec, sel, n_sel, n_docs)) return TD_E_INVALID;
+    // the walk, twice: what is kept and every check first, so that an error leaves the outputs alone
+    for (int pass = 0; pass < 2; ++pass) {
+        int64_t K = 0, T = 0, n_short = 0, n_long = 0;
+        for (int64_t i = 0; i < n_sel; ++i) {
+            const int64_t d = sel ? sel[i] : i;
+            if (d < 0 || d >= n_docs || tok_offsets[d] < 0 || tok_offsets[d + 1] < tok_offsets[d]) {
+                counts[0] = i;
+                return TD_E_INVALID;
+            }
+            const int64_t L = tok_offsets[d + 1] - tok_offsets[d];
+            if (L < spec->min_len) { ++n_short; continue; }
+            if (spec->max_len >= 0 && L > spec->max_len) { ++n_long; continue; }
+            if (pass == 1) {
+                if (out_offsets) out_offsets[K] = T;
+                if (out_docs) out_docs[K] = d;
+            }
+            ++K;
+            T += L;
+        }
+        if (pass == 1 || (!out_offsets && !out_docs)) {
+            if (out_offsets) out_offsets[K] = T;
+            counts[0] = K;
+            counts[1] = T;
+            counts[2] = n_short;
+            counts[3] = n_long;
+            break;
+        }
+    }
+    return TD_OK;
+}
+
+int td_select_docs_device(td_tokenizer* t, const void* d_ids, const void* d_labels, int64_t n_tokens, const void* d_tok_offsets,
+                          int64_t n_docs, const void* d_sel, int64_t n_sel, const td_select_spec* spec, void* d_out_ids,
+                          void* d_out_labels, int64_t ids_capacity, void* d_out_offsets, void* d_out_docs, void* d_counts,
+                          void* hip_stream) {
+    if (!t || n_tokens < 0 || n_docs < 0 || n_sel < 0 || !d_tok_offsets || (n_tokens > 0 && !d_ids) || !d_counts || !d_out_offsets ||
+        ids_capacity < 0 || (ids_capacity > 0 && !d_out_ids) || (d_labels != nullptr) != (d_out_labels != nullptr))
+        return TD_E_INVALID;
+    if (const char* m = select_spec_error(spec, d_sel, n_sel, n_docs)) return fail_unlocked(t, TD_E_INVALID, std::string("td_select_docs_device: ") + m);
+    return locked(t, [&] {
+        return select_launch_locked(t, d_ids, d_labels, n_tokens, d_tok_offsets, n_docs, d_sel, n_sel, spec, d_out_ids, d_out_labels,
+                                    ids_capacity, d_out_offsets, d_out_docs, d_counts, (hipStream_t)hip_stream);
+    });
+}
+
+int td_select_docs(td_tokenizer* t, const int32_t* ids, const int32_t* labels, int64_t n_tokens, const int64_t* tok_offsets,
+                   int64_t n_docs, const int64_t* sel, int64_t n_sel, const td_select_spec* spec, int32_t* out_ids,
+                   int32_t* out_labels, int64_t ids_capacity, int64_t* out_offsets, int64_t* out_docs, int64_t* counts) {
+    if (!t || n_tokens < 0 || n_docs < 0 || n_sel < 0 || !tok_offsets || !counts || !out_offsets || ids_capacity < 0 ||
+        (labels != nullptr) != (out_labels != nullptr))
+        return TD_E_INVALID;
+    if (const char* m = select_spec_error(spec, sel, n_sel, n_docs)) return fail_unlocked(t, TD_E_INVALID, std::string("td_select_docs: ") + m);
+    return locked(t, [&] {
+        int rc;
+        if ((rc = rows_check_host_ids(t, ids, n_tokens, tok_offsets, n_docs))) return rc;
+        if ((rc = select_plan_host(t, tok_offsets, n_docs, sel, n_sel, spec, out_ids, ids_capacity, counts))) return rc;
+        hipStream_t s;
+        LabCall lc;
+        const td_rows_labels lab{labels, out_labels, 0, 0, 0, 0};
+        if ((rc = rows_stage_host_ids(t, ids, tok_offsets, n_docs, s))) return rc;
+        if ((rc = rows_stage_host_src(t, labels ? &lab : nullptr, tok_offsets[n_docs], lc, s))) return rc;
+        return select_to_host(t, t->dec_tokens.p, tok_offsets[n_docs], t->d_offsets.p, n_docs, sel, n_sel, spec, out_ids, out_offsets, out_docs,
+                              counts, lc, s);
+    });
+}
+
+int td_encode_batch_select(td_tokenizer* t, const uint8_t* text, const int64_t* doc_offsets, int64_t n_docs, int mode,
+                           const int64_t* sel, int64_t n_sel, const td_select_spec* spec, int32_t* out_ids, int64_t ids_capacity,
+                           int64_t* out_offsets, int64_t* out_docs, int64_t* counts) {
+    if (!t || !doc_offsets || n_docs < 0 || n_sel < 0 || !counts || !out_offsets || ids_capacity < 0 ||
+        (mode != TD_MODE_ENCODE && mode != TD_MODE_ORDINARY))
+        return TD_E_INVALID;
+    if (const char* m = select_spec_error(spec, sel, n_sel, n_docs)) return fail_unlocked(t, TD_E_INVALID, std::string("td_encode_batch_select: ") + m);
+    return locked(t, [&] {
+        int rc;
+        int64_t dev_cap;
+        hipStream_t s;
+        if ((rc = rows_encode_locked(t, text, doc_offsets, n_docs, mode, dev_cap, s))) return rc;
+        // what is kept is known from the token offsets: they come back (8 bytes a document) and are planned on the host
+        std::vector<int64_t> toff((size_t)n_docs + 1);
+        if ((rc = copy_wait(t, toff.data(), t->d_offsets.p, (size_t)(n_docs + 1) * 8, hipMemcpyDeviceToHost, s))) return rc;
+        if ((rc = select_plan_host(t, toff.data(), n_docs, sel, n_sel, spec, out_ids, ids_capacity, counts))) return rc;
+        return select_to_host(t, t->d_tokens.p, dev_cap, t->d_offsets.p, n_docs, sel, n_sel, spec, out_ids, out_offsets, out_docs, counts,
+                              LabCall{}, s);
     });
 }
 

@@ -246,6 +246,8 @@ struct td_tokenizer {
     DevBuf rows_lab_src, rows_lab;  // the labeled host entry points: the caller's label stream, the label rows
     // window rows (td_windows.hip): the scan words and first_row, the host entry points' per-row outputs on the device
     DevBuf win_scan, win_first, win_len, win_docs, win_starts;
+    // document selection (td_select.hip): the scan words and src_base, the host entry points' list, offsets and documents on the device
+    DevBuf sel_scan, sel_base, sel_in, sel_off, sel_docs;
     bool rows_last = false;  // the last call launched the rows kernels (the unit of a TD_E_CAPACITY position)
     // loss labels (td_labels.hip): the counts and flags, the document-start bitmap, the tiles' events / states, their trained ids
     // and the lanes' (trained_offsets only); the host entry points' outputs on the device

@@ -1,6 +1,6 @@
-// Device helpers and launch constants the row layouts share (td_rows.hip, td_pack.hip, td_windows.hip): each of the three
-// finds a slot's document in its own way, and all of them store, sum, divide and raise errors the same way.  Device code only:
-// the host library sees td_rows.h, td_pack.h and td_windows.h.
+// Device helpers and launch constants the row layouts (td_rows.hip, td_pack.hip, td_windows.hip) and the document selection
+// (td_select.hip) share: each of the four finds a slot's document in its own way, and all of them store, sum, scan, divide and
+// raise errors the same way.  Device code only: the host library sees td_rows.h, td_pack.h, td_windows.h and td_select.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -99,6 +99,26 @@ __device__ __forceinline__ long long block_max(long long v, long long* s_red) {
     for (int w = 0; w < RC_THREADS / 64; ++w) r = max(r, s_red[w]);
     __syncthreads();
     return r;
+}
+
+// the exclusive scan of `sum` over the workgroup's RC_THREADS lanes, and its total; s_wave: RC_THREADS / 64 words of LDS
+__device__ __forceinline__ long long block_excl(long long sum, long long* s_wave, long long& total) {
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    long long incl = sum;
+    for (int dd = 1; dd < 64; dd <<= 1) {
+        const long long o = __shfl_up(incl, dd);
+        if (lane >= dd) incl += o;
+    }
+    __syncthreads();  // (the readers of an earlier call are done)
+    if (lane == 63) s_wave[wv] = incl;
+    __syncthreads();
+    long long before = 0;
+    total = 0;
+    for (int w = 0; w < RC_THREADS / 64; ++w) {
+        if (w < wv) before += s_wave[w];
+        total += s_wave[w];
+    }
+    return before + incl - sum;
 }
 
 }  // namespace td

@@ -47,26 +47,6 @@ __device__ __forceinline__ int64_t win_count(const WindowArgs& a, int64_t L) {
     return L <= a.C ? 1 : div_magic(L - a.overlap + a.step - 1, a.step, a.step_magic);
 }
 
-// the exclusive scan of `sum` over the workgroup's lanes, and its total
-__device__ __forceinline__ long long block_excl(long long sum, long long* s_wave, long long& total) {
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    long long incl = sum;
-    for (int dd = 1; dd < 64; dd <<= 1) {
-        const long long o = __shfl_up(incl, dd);
-        if (lane >= dd) incl += o;
-    }
-    __syncthreads();  // (the readers of an earlier call are done)
-    if (lane == 63) s_wave[wv] = incl;
-    __syncthreads();
-    long long before = 0;
-    total = 0;
-    for (int w = 0; w < WIN_THREADS / 64; ++w) {
-        if (w < wv) before += s_wave[w];
-        total += s_wave[w];
-    }
-    return before + incl - sum;
-}
-
 __global__ __launch_bounds__(WIN_THREADS) void td_win_count(const WindowArgs a) {
     __shared__ long long s_red[4][WIN_THREADS / 64];
     __shared__ int s_bad;

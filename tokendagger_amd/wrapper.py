@@ -428,6 +428,33 @@ class Tokenizer:
             raise TokenDaggerError(f"Encoding failed: {ex}")
         return self._windows(r, no_pad)
 
+    # ------------------------------------------------------------------ document selection -----
+    # Choose, reorder, repeat and length-filter encoded documents on the device: `order` lists document indices in the order the
+    # result is to have them (None: as they are; a shuffle is rng.permutation(n_docs), a split a slice of it, up-sampling a list
+    # with repeats), and listed documents with fewer than min_len or more than max_len ids are dropped.  The result is again
+    # ids + offsets: feed it to ids_to_rows / ids_to_packed_rows / ids_to_window_rows / ids_to_labeled_rows.
+    def select_docs(self, ids: np.ndarray, tok_offsets: np.ndarray, order=None, *, min_len: int = 0, max_len: int | None = None, labels=None):
+        """-> (ids, offsets, docs), or (ids, labels, offsets, docs) with a label stream aligned with ids; docs[k]: the input
+        document that output document k is."""
+        hip = _capi.HipTokenizer.borrow(self._core_bpe.handle())
+        try:
+            i, l, o, d, _ = hip.select_docs(ids, tok_offsets, order, _capi.select_spec(int(min_len), max_len), labels=labels)
+        except _capi.TokenDaggerHipError as ex:
+            raise TokenDaggerError(f"Selecting documents failed: {ex}")
+        return (i, o, d) if labels is None else (i, l, o, d)
+
+    def encode_batch_select(self, text: np.ndarray | bytes, offsets: np.ndarray, order=None, *, min_len: int = 0, max_len: int | None = None,
+                            ordinary: bool = False):
+        """encode_batch_to_numpy and select_docs in one call (the ids never leave the device in between) -> (ids, offsets, docs)."""
+        hip = _capi.HipTokenizer.borrow(self._core_bpe.handle())
+        buf = np.frombuffer(text, dtype=np.uint8) if isinstance(text, (bytes, bytearray)) else text
+        try:
+            i, o, d, _ = hip.encode_batch_select(buf, np.asarray(offsets, dtype=np.int64), order, _capi.select_spec(int(min_len), max_len),
+                                                 mode=MODE_ORDINARY if ordinary else MODE_ENCODE)
+        except _capi.TokenDaggerHipError as ex:
+            raise TokenDaggerError(f"Encoding failed: {ex}")
+        return i, o, d
+
     # ------------------------------------------------------------------ loss labels ------------
     # labels[i] = ids[i] inside a span, ignore_index elsewhere.  A span starts behind an opener (a string, encoded once with every
     # special token allowed, or a list of ids: at most 8 openers of at most 8 ids) and ends with a closer (a special-token string
