@@ -142,6 +142,17 @@ def test_empty_documents_and_edges(tok):
     assert g[0].shape == (0, 8) and g[2].tolist() == [0] and g[3].tolist() == [0, 0, 0, 0]
 
 
+def test_concat_at_the_boundary_of_the_lds_table(tok):
+    """One tile whose documents fill the LDS table (4352 entries) to its last entry and just beyond: a document, E empty ones
+    and a document need E + 3 entries with the sentinel, so E = 4349 is the last that fits and 4350 the first that searches
+    global memory."""
+    rng = np.random.default_rng(9)
+    for E in (4348, 4349, 4350, 4351, 4352, 4353, 5000):
+        offs = np.concatenate([[0], np.cumsum([3] + [0] * E + [7])]).astype(np.int64)
+        ids = rng.integers(0, 1000, int(offs[-1])).astype(np.int32)
+        _check(tok, ids, offs, 8, rt.CONCAT, -1, -1, truth=rt.rows_numpy)
+
+
 def test_capacity_host_and_device(tok, golden):
     import torch
     from tokendagger_amd import capi

@@ -28,6 +28,9 @@
 //   td_lab_finish       counts[4]; with trained_offsets a lane a document boundary: the trained ids in front of the boundary's
 //                       tile + in front of its lane + the lane's trained bits below it (td_lab_apply left the last two, 4 B a
 //                       lane).  Empty documents are boundaries at one position like any other.
+//
+// Every scan over the lanes of a wavefront here (td_lab_carry, td_lab_apply's state and counts, td_lab_count_carry) is
+// td_rows_common.h's wave_incl_scan, with lab_combine or an add as the combine.
 #include <hip/hip_runtime.h>
 
 #include "td_labels_args.h"
@@ -122,12 +125,7 @@ __global__ __launch_bounds__(LAB_CARRY_THREADS) void td_lab_carry(const LabelArg
             ev[k] = c0 + k < ntiles ? (word[k >> 2] >> (8 * (k & 3))) & 3u : LAB_NONE;
             mine = lab_combine(mine, ev[k]);
         }
-        uint32_t incl = mine;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const uint32_t o = __shfl_up(incl, d);
-            if (lane >= d) incl = lab_combine(o, incl);
-        }
+        const uint32_t incl = wave_incl_scan(mine, lane, [](uint32_t x, uint32_t y) { return lab_combine(x, y); });
         __syncthreads();  // (the readers of the round before are done)
         if (lane == 63) s_wave[wv] = incl;
         __syncthreads();
@@ -204,12 +202,7 @@ __global__ __launch_bounds__(LAB_THREADS) void td_lab_apply(const LabelArgs a) {
         uint32_t ev = LAB_NONE;
         if (const uint32_t m = ob | cb | db) ev = (ob >> (31 - __clz(m))) & 1u ? LAB_IN : LAB_OUT;
         // ---- the state in front of the lane ---------------------------------------------------------------------------
-        uint32_t incl = ev;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const uint32_t o = __shfl_up(incl, d);
-            if (lane >= d) incl = lab_combine(o, incl);
-        }
+        const uint32_t incl = wave_incl_scan(ev, lane, [](uint32_t x, uint32_t y) { return lab_combine(x, y); });
         if (lane == 63) s_wave[wv] = incl;
         __syncthreads();  // (and every lane has read what it needs of its neighbour's ids)
         uint32_t st = a.tiles[t] ? LAB_IN : LAB_NONE;
@@ -244,12 +237,7 @@ __global__ __launch_bounds__(LAB_THREADS) void td_lab_apply(const LabelArgs a) {
         const long long packed = (long long)n_tr | (long long)n_sp << 16 | (long long)n_un << 32;
         long long sums;
         if (a.trained_off) {  // the lanes' exclusive sums too
-            long long incl2 = packed;
-#pragma unroll
-            for (int d = 1; d < 64; d <<= 1) {
-                const long long o = __shfl_up(incl2, d);
-                if (lane >= d) incl2 += o;
-            }
+            const long long incl2 = wave_incl_scan(packed, lane, [](long long x, long long y) { return x + y; });
             if (lane == 63) s_red[wv] = incl2;
             __syncthreads();
             long long before = 0;
@@ -300,12 +288,7 @@ __global__ __launch_bounds__(LAB_CARRY_THREADS) void td_lab_count_carry(const La
             v[k] = c0 + k < ntiles ? a.tile_cnt[c0 + k] : 0ull;
             mine += v[k];
         }
-        unsigned long long incl = mine;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const unsigned long long o = __shfl_up(incl, d);
-            if (lane >= d) incl += o;
-        }
+        const unsigned long long incl = wave_incl_scan(mine, lane, [](unsigned long long x, unsigned long long y) { return x + y; });
         __syncthreads();
         if (lane == 63) s_wave[wv] = incl;
         __syncthreads();

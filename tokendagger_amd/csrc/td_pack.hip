@@ -11,7 +11,8 @@
 //                     seg_docs and row_lengths come out of the same pass
 //   td_pack_slots     td_rows_concat's tile walk with segments in place of documents: a tile of 4096 output slots keeps the
 //                     starts of the segments that overlap it in LDS (at most 4097: no segment is empty), every lane searches
-//                     them once for its first slot and walks a cursor; ids are written as int4, positions only when asked for;
+//                     them once for its first slot (last_le, td_rows_common.h; the searches over global arrays here and in
+//                     td_pack_segments are its last_le_global) and walks a cursor; ids are written as int4, positions only when asked for;
 //                     <PackLabArgs>: the pair form, lab.src -> lab.dst beside the ids (td_rows_common.h), <PackArgs>: one stream
 #include <hip/hip_runtime.h>
 
@@ -156,24 +157,13 @@ __global__ __launch_bounds__(PACK_THREADS) void td_pack_segments(const PackArgs 
     for (int64_t idx = g; idx < n_work; idx += (int64_t)gridDim.x * PACK_THREADS) {
         int64_t x = idx;
         if (x < F) {  // full row f: the last document whose exclusive prefix of full chunks is <= f
-            int64_t lo = 0, hi = a.n_docs;
-            while (hi - lo > 1) {
-                const int64_t mid = lo + (hi - lo) / 2;
-                if (a.pref[mid] <= x) lo = mid;
-                else hi = mid;
-            }
+            const int64_t lo = last_le_global([pref = a.pref](int64_t d) { return pref[d]; }, 0, a.n_docs, x);
             pack_put(a, x, x * S, lo, (x - a.pref[lo]) * S);
             continue;
         }
         x -= F;
         if (x < a.n_items) {  // sorted remainder item i: the last placement whose first item is <= i
-            int64_t lo = 0, hi = a.n_pl;
-            while (hi - lo > 1) {
-                const int64_t mid = lo + (hi - lo) / 2;
-                if (a.pl[mid].first_item <= x) lo = mid;
-                else hi = mid;
-            }
-            const PackPlacement p = a.pl[lo];
+            const PackPlacement p = a.pl[last_le_global([pl = a.pl](int64_t i) { return pl[i].first_item; }, 0, a.n_pl, x)];
             const int64_t j = x - p.first_item, d = a.sorted_doc[x];
             const int64_t n = a.b + pack_body(a, a.tok_off[d + 1] - a.tok_off[d]) + a.e;
             pack_put(a, p.first_seg + j, p.row * S + p.slot + j * p.len, d, n - p.len);  // (truncate: n = len, q0 = 0)
@@ -192,13 +182,7 @@ __global__ __launch_bounds__(PACK_THREADS) void td_pack_segments(const PackArgs 
 
 // the last segment k in [0, segs) with seg_start[k] <= j
 __device__ __forceinline__ int64_t pack_seg_search(const PackArgs& a, int64_t j) {
-    int64_t lo = 0, hi = a.segs;
-    while (hi - lo > 1) {
-        const int64_t mid = lo + (hi - lo) / 2;
-        if (a.seg_start[mid] <= j) lo = mid;
-        else hi = mid;
-    }
-    return lo;
+    return last_le_global([st = a.seg_start](int64_t k) { return st[k]; }, 0, a.segs, j);
 }
 
 template <class A>
@@ -222,14 +206,7 @@ __global__ __launch_bounds__(PACK_THREADS) void td_pack_slots(const A a) {
         for (int it = 0; it < PACK_TILE / (4 * PACK_THREADS); ++it) {
             const int64_t j0 = t0 + (int64_t)it * 4 * PACK_THREADS + 4 * tid;
             if (j0 >= t1) break;
-            int lo = 0, hi = nk;
-            const int32_t x0 = (int32_t)(j0 - t0);
-            while (hi - lo > 1) {
-                const int mid = (lo + hi) >> 1;
-                if (s_rel[mid] <= x0) lo = mid;
-                else hi = mid;
-            }
-            int i = lo, cur = -1;
+            int i = last_le(s_rel, nk, (int32_t)(j0 - t0)), cur = -1;
             int64_t d = -1, start = 0, q0 = 0, base = 0, eos_at = 0;
             int32_t v[4], ps[4];
             [[maybe_unused]] int32_t lv[4];

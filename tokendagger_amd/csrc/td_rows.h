@@ -10,9 +10,6 @@
 
 namespace td {
 
-constexpr int ROWS_LDS_DOCS = 4352;   // relative document bases a CONCAT tile keeps in LDS (more: the tile searches global memory)
-constexpr int ROWS_SCAN_DOCS = 1024;  // documents per workgroup of the cu_seqlens scan (four a lane)
-
 struct RowsArgs {
     const int32_t* ids;       // [n_tokens]
     int64_t n_tokens;         // ids the buffer holds: tok_off[n_docs] above it is an error, no id at or above it is read

@@ -1,8 +1,9 @@
 // Training rows (td_make_rows*, td_encode_batch_rows): ids + per-document token offsets -> rows of S slots.
 //
 // CONCAT places document d's slots at base_d = tok_off[d] + d * (b + e), a closed form, so the rows need no scan: the slot
-// kernel owns contiguous tiles of OUTPUT slots, finds the tile's first document with one 256-way search over base_d and keeps
-// the bases of the documents that overlap the tile in LDS (more than fit: every slot searches global memory).  PAD places
+// kernel owns contiguous tiles of OUTPUT slots, finds the tile's first document by group_last_le over base_d and keeps the
+// bases of the documents that overlap the tile in LDS (tile_table, td_rows_common.h; more than fit: every slot searches global
+// memory, last_le_global).  PAD places
 // slot j in document j / S.  Either way the ids are read at a per-document shift, as four dwords (or two aligned int4 and a
 // funnel, funnel_src), and written as int4: nearly a copy.  A one-id document costs what its slots cost, and a PAD row of a
 // truncated giant document reads S ids of it, not its body.
@@ -85,27 +86,17 @@ __device__ __forceinline__ int4 rows_load4(const A& a, int64_t src) {
     return make_int4(p[src], p[src + 1], p[src + 2], p[src + 3]);
 }
 
-// last d in [lo, n_docs) with base_d <= j (base_lo <= j)
-__device__ int64_t doc_search(const RowsArgs& a, int64_t lo, int64_t j, int64_t k) {
-    int64_t hi = a.n_docs;
-    while (hi - lo > 1) {
-        const int64_t mid = lo + (hi - lo) / 2;
-        if (doc_base(a, mid, k) <= j) lo = mid;
-        else hi = mid;
-    }
-    return lo;
-}
-
 template <class A>
 __global__ __launch_bounds__(ROWS_THREADS) void td_rows_concat(const A a) {
     constexpr bool LAB = has_lab<A>;
-    __shared__ int32_t s_lb[ROWS_LDS_DOCS];  // bases of the tile's documents - s0, clamped to [-1, ROWS_TILE + 1]
+    __shared__ int32_t s_lb[RC_LDS_DOCS];  // bases of the tile's documents - s0, clamped to [-1, ROWS_TILE + 1]
     __shared__ long long s_red[ROWS_THREADS / 64];
     const int tid = threadIdx.x;
     const Plan p = rows_plan(a, blockIdx.x == 0 && tid == 0);
     if (!p.ok) return;
     const int64_t k = a.b + a.e, S = a.S, R = p.R;
     const int64_t ntiles = (p.total + ROWS_TILE - 1) / ROWS_TILE;
+    const auto base_of = [off = a.tok_off, k](int64_t d) { return off[d] + d * k; };  // doc_base
     long long segs = 0;
     for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
         const int64_t s0 = tile * ROWS_TILE;
@@ -116,30 +107,11 @@ __global__ __launch_bounds__(ROWS_THREADS) void td_rows_concat(const A a) {
         int nl = 0;  // documents that overlap [s0, r1): s_lb[0, nl), and s_lb[nl] the base of the next
         bool over = false;
         if (s0 < r1) {
-            // the last document with base <= s0 (base_0 = 0), 256 probes a step
-            int64_t lo = 0, hi = a.n_docs;
-            while (hi - lo > 1) {
-                const int64_t step = (hi - lo + ROWS_THREADS - 1) / ROWS_THREADS;
-                const int64_t q = lo + (int64_t)tid * step;
-                const int c = __syncthreads_count(tid > 0 && q < hi && doc_base(a, q, k) <= s0);
-                hi = hi < lo + (int64_t)(c + 1) * step ? hi : lo + (int64_t)(c + 1) * step;
-                lo += (int64_t)c * step;
-            }
-            d0 = lo;
+            d0 = group_last_le(base_of, 0, a.n_docs, s0);  // (base_0 = 0 <= s0)
             base0 = doc_base(a, d0, k);
-            for (int c0 = 0;; c0 += ROWS_THREADS) {
-                const int64_t d = d0 + c0 + tid;
-                int32_t v = ROWS_TILE + 1;
-                if (d <= a.n_docs) {
-                    const int64_t r = doc_base(a, d, k) - s0;
-                    v = r < 0 ? -1 : r > ROWS_TILE ? ROWS_TILE + 1 : (int32_t)r;
-                }
-                s_lb[c0 + tid] = v;
-                const int c = __syncthreads_count(v < r1 - s0);
-                nl += c;
-                if (c < ROWS_THREADS) break;
-                if (c0 + 2 * ROWS_THREADS > ROWS_LDS_DOCS) { over = true; break; }
-            }
+            bool fits;
+            nl = tile_table(s_lb, base_of, d0, a.n_docs, s0, -1, ROWS_TILE + 1, (int32_t)(r1 - s0), fits);
+            over = !fits;
             // segments: the row starts in [s0, r1), and the starts of non-empty documents there that are not row starts
             {  // (lane 0 counts the row starts; in vector registers, the scalar ones are taken by the tile's bounds)
                 const int64_t x0 = tid == 0 ? s0 + S - 1 : 0, x1 = tid == 0 ? r1 + S - 1 : 0;
@@ -171,21 +143,13 @@ __global__ __launch_bounds__(ROWS_THREADS) void td_rows_concat(const A a) {
             auto seek = [&](int64_t j) {  // j < r1
                 if (!over) {
                     const int32_t x = (int32_t)(j - s0);
-                    if (i < 0) {
-                        int lo = 0, hi = nl;
-                        while (hi - lo > 1) {
-                            const int mid = (lo + hi) >> 1;
-                            if (s_lb[mid] <= x) lo = mid;
-                            else hi = mid;
-                        }
-                        i = lo;
-                    }
+                    if (i < 0) i = last_le(s_lb, nl, x);
                     while (i + 1 < nl && s_lb[i + 1] <= x) ++i;
                     d = d0 + i;
                     base = i == 0 ? base0 : s0 + s_lb[i];
                     end = s0 + s_lb[i + 1];
                 } else if (d < 0 || j >= end) {
-                    d = doc_search(a, d < 0 ? d0 : d, j, k);
+                    d = last_le_global(base_of, d < 0 ? d0 : d, a.n_docs, j);
                     base = doc_base(a, d, k);
                     end = doc_base(a, d + 1, k);
                 }
@@ -339,8 +303,8 @@ __device__ __forceinline__ unsigned long long wave_u64(unsigned long long w) {  
 }
 
 __global__ __launch_bounds__(ROWS_THREADS) void td_rows_cu(const RowsArgs a) {
-    __shared__ long long s_w[ROWS_SCAN_DOCS + 1];  // the chunk's exclusive scan of c_d, then its total
-    __shared__ long long s_base[ROWS_SCAN_DOCS];
+    __shared__ long long s_w[RC_SCAN_CHUNK + 1];  // the chunk's exclusive scan of c_d, then its total
+    __shared__ long long s_base[RC_SCAN_CHUNK];
     __shared__ long long s_wave[ROWS_THREADS / 64];
     __shared__ long long s_excl;
     __shared__ unsigned long long s_chunk;
@@ -350,21 +314,17 @@ __global__ __launch_bounds__(ROWS_THREADS) void td_rows_cu(const RowsArgs a) {
     if (tid == 0) s_chunk = atomicAdd(&a.scan[0], 1ull);  // (tickets in launch order: every predecessor has started)
     __syncthreads();
     const int64_t c = (int64_t)s_chunk;
-    const int64_t nch = a.n_docs > 0 ? (a.n_docs + ROWS_SCAN_DOCS - 1) / ROWS_SCAN_DOCS : 1;
+    const int64_t nch = a.n_docs > 0 ? (a.n_docs + RC_SCAN_CHUNK - 1) / RC_SCAN_CHUNK : 1;
     const int64_t k = a.b + a.e, R = p.R;
     long long v[4], sum = 0;
     for (int q = 0; q < 4; ++q) {
-        const int64_t d = c * ROWS_SCAN_DOCS + tid * 4 + q;
+        const int64_t d = c * RC_SCAN_CHUNK + tid * 4 + q;
         int64_t base = 0;
         v[q] = d < a.n_docs ? doc_cuts(a, d, k, R, base) : 0;
         s_base[tid * 4 + q] = base;
         sum += v[q];
     }
-    long long incl = sum;
-    for (int dd = 1; dd < 64; dd <<= 1) {
-        const long long o = __shfl_up(incl, dd);
-        if (lane >= dd) incl += o;
-    }
+    const long long incl = wave_incl_scan(sum, lane, [](long long x, long long y) { return x + y; });
     if (lane == 63) s_wave[wv] = incl;
     __syncthreads();
     long long before = 0, agg = 0;
@@ -377,7 +337,7 @@ __global__ __launch_bounds__(ROWS_THREADS) void td_rows_cu(const RowsArgs a) {
         s_w[tid * 4 + q] = run;
         run += v[q];
     }
-    if (tid == 0) s_w[ROWS_SCAN_DOCS] = agg;
+    if (tid == 0) s_w[RC_SCAN_CHUNK] = agg;
     if (wv == 0) {  // look back 64 predecessors at a time: lane i reads chunk top - i
         unsigned long long* st = a.scan + 1;
         long long pre = 0;
@@ -394,8 +354,8 @@ __global__ __launch_bounds__(ROWS_THREADS) void td_rows_cu(const RowsArgs a) {
                     }
                     if ((w >> 62) == 0) {  // not published in time: this lane sums chunk q itself
                         long long part = 0;
-                        for (int r = 0; r < ROWS_SCAN_DOCS; ++r) {
-                            const int64_t d = q * ROWS_SCAN_DOCS + r;
+                        for (int r = 0; r < RC_SCAN_CHUNK; ++r) {
+                            const int64_t d = q * RC_SCAN_CHUNK + r;
                             int64_t base;
                             if (d < a.n_docs) part += doc_cuts(a, d, k, R, base);
                         }
@@ -418,12 +378,7 @@ __global__ __launch_bounds__(ROWS_THREADS) void td_rows_cu(const RowsArgs a) {
     __syncthreads();
     const long long ex = s_excl;
     for (long long q = tid; q < agg; q += ROWS_THREADS) {  // entry q of the chunk: in the last document whose scan is <= q
-        int lo = 0, hi = ROWS_SCAN_DOCS;
-        while (hi - lo > 1) {
-            const int mid = (lo + hi) >> 1;
-            if (s_w[mid] <= q) lo = mid;
-            else hi = mid;
-        }
+        const int lo = last_le(s_w, RC_SCAN_CHUNK, q);
         const long long m = q - s_w[lo], base = s_base[lo];
         const long long val = m == 0 ? base : (div_magic(base, a.S, a.s_magic) + m) * a.S;
         if (ex + q < a.aux_cap) a.aux[ex + q] = (int32_t)val;
@@ -437,7 +392,7 @@ __global__ __launch_bounds__(ROWS_THREADS) void td_rows_cu(const RowsArgs a) {
 
 }  // namespace
 
-int64_t rows_scan_words(int64_t n_docs) { return 1 + (n_docs > 0 ? (n_docs + ROWS_SCAN_DOCS - 1) / ROWS_SCAN_DOCS : 1); }
+int64_t rows_scan_words(int64_t n_docs) { return 1 + (n_docs > 0 ? (n_docs + RC_SCAN_CHUNK - 1) / RC_SCAN_CHUNK : 1); }
 
 hipError_t launch_rows(const RowsLabArgs& a, hipStream_t stream) {
     const int64_t tiles = (a.rows_cap * a.S + ROWS_TILE - 1) / ROWS_TILE;  // (the host keeps rows_cap * S far from overflow)

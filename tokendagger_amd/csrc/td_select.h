@@ -11,8 +11,6 @@
 
 namespace td {
 
-constexpr int SEL_LDS_DOCS = 4352;     // output offsets of a tile's documents kept in LDS (more, i.e. runs of empty ones: bisection over the offsets)
-constexpr int SEL_SCAN_ENTRIES = 1024; // selection entries per workgroup of the scan (four a lane)
 // scan words in front of the chunk sums (two a chunk: kept entries, kept ids)
 enum { SEL_SHORT = 0, SEL_LONG = 1, SEL_BAD = 2, SEL_LEAVE = 3, SEL_K = 4, SEL_T = 5, SEL_SCAN_HEAD = 8 };
 

@@ -3,21 +3,22 @@
 // than min_len or more than max_len ids are dropped.  A gather: the output is again ids + tok_offsets.
 //
 // Entry i contributes keep_i documents and keep_i * L ids, and its place in the output is the exclusive prefix sum of both: no
-// closed form, nothing sequential.  td_windows.hip's shape: three small launches make out_offsets, out_docs and src_base, no
-// lane waits for another workgroup in any of them:
+// closed form, nothing sequential.  Three small launches make out_offsets, out_docs and src_base, no lane waits for another
+// workgroup in any of them; the chunk scan and the tile locator are td_rows_common.h's, shared with td_windows.hip:
 //
 //   td_sel_count    1024 entries a workgroup: sel[i] (or i) checked against n_docs, its two offsets against each other and
 //                   n_tokens, keep and keep * L; the chunk's two sums into the scan words, the dropped entries by one atomic
 //                   a workgroup and kind
-//   td_sel_chunks   one workgroup: the chunks' sums -> their exclusive prefixes; K, T, the capacity check, counts, and the
-//                   "leave" mark (a bad entry, or T above the capacity) the two kernels behind it read
+//   td_sel_chunks   one workgroup: the chunks' sums -> their exclusive prefixes (chunks_excl_scan<2>); K, T, the capacity check,
+//                   counts, and the "leave" mark (a bad entry, or T above the capacity) the two kernels behind it read
 //   td_sel_first    kept entry -> k: out_off[k], out_docs[k], src_base[k] = tok_off[sel[i]]; out_off[K] = T
 //   td_sel_slots    the slots.  Tiles of 4096 OUTPUT slots, four a lane stored as one int4, so a document of 100 000 ids is
 //                   written by as many lanes as it has slots.  Slot j belongs to the k with out_off[k] <= j < out_off[k + 1], an
 //                   upper-bound search: a run of kept empty documents shares one offset and is stepped over by the search,
-//                   never walked.  One 256-way search finds the tile's first k; the offsets behind it go to LDS until one
-//                   lies beyond the tile, and a lane bisects there.  A tile whose documents do not fit (thousands of empty
-//                   ones) finds its last k by a second 256-way search, and its lanes bisect over the offsets themselves.
+//                   never walked.  group_last_le finds the tile's first k; tile_table puts the offsets behind it into LDS until
+//                   one lies beyond the tile, and a lane bisects there (last_le).  A tile whose documents do not fit (thousands of
+//                   empty ones) finds its last k by a second group_last_le, and its lanes bisect over the offsets themselves
+//                   (last_le_global).
 //                   A lane resolves and loads its sixteen slots first and stores them afterwards.  <SelectLabArgs>: the pair
 //                   form, lab.src -> lab.dst by the same resolved source; <SelectArgs>: one stream.
 #include <hip/hip_runtime.h>
@@ -30,7 +31,6 @@ namespace td {
 namespace {
 
 constexpr int SEL_THREADS = RC_THREADS, SEL_TILE = RC_TILE, SEL_MAX_GRID = RC_MAX_GRID;
-static_assert(SEL_SCAN_ENTRIES == 4 * SEL_THREADS && SEL_LDS_DOCS % SEL_THREADS == 0 && SEL_TILE == 16 * SEL_THREADS, "td_select.hip");
 
 struct SelEntry {
     int64_t doc, lo, len;  // sel[i], tok_off[doc], L
@@ -64,7 +64,7 @@ __global__ __launch_bounds__(SEL_THREADS) void td_sel_count(const SelectArgs a) 
     long long kept = 0, kept_ids = 0, n_short = 0, n_long = 0, n_bad = 0;
     int64_t bad_at = 0;
     for (int q = 0; q < 4; ++q) {
-        const int64_t i = (int64_t)blockIdx.x * SEL_SCAN_ENTRIES + tid * 4 + q;
+        const int64_t i = (int64_t)blockIdx.x * RC_SCAN_CHUNK + tid * 4 + q;
         if (i >= a.n_sel) break;
         const SelEntry e = sel_entry(a, i);
         if (e.bad && !n_bad) bad_at = i;
@@ -92,33 +92,10 @@ __global__ __launch_bounds__(SEL_THREADS) void td_sel_count(const SelectArgs a) 
 __global__ __launch_bounds__(SEL_THREADS) void td_sel_chunks(const SelectArgs a, int64_t nch) {
     __shared__ long long s_wave[SEL_THREADS / 64];
     const int tid = threadIdx.x;
-    unsigned long long* cs = a.scan + SEL_SCAN_HEAD;
-    long long carry_k = 0, carry_t = 0;
-    for (int64_t base = 0; base < nch; base += 4 * SEL_THREADS) {
-        long long vk[4], vt[4], sum_k = 0, sum_t = 0;
-        for (int q = 0; q < 4; ++q) {
-            const int64_t c = base + tid * 4 + q;
-            vk[q] = c < nch ? (long long)cs[2 * c] : 0;
-            vt[q] = c < nch ? (long long)cs[2 * c + 1] : 0;
-            sum_k += vk[q];
-            sum_t += vt[q];
-        }
-        long long total_k, total_t;
-        long long run_k = carry_k + block_excl(sum_k, s_wave, total_k);
-        long long run_t = carry_t + block_excl(sum_t, s_wave, total_t);
-        for (int q = 0; q < 4; ++q) {
-            const int64_t c = base + tid * 4 + q;
-            if (c < nch) {
-                cs[2 * c] = (unsigned long long)run_k;
-                cs[2 * c + 1] = (unsigned long long)run_t;
-            }
-            run_k += vk[q];
-            run_t += vt[q];
-        }
-        carry_k += total_k;
-        carry_t += total_t;
-    }
+    long long carry[2];  // kept entries, kept ids
+    chunks_excl_scan<2>(a.scan + SEL_SCAN_HEAD, nch, s_wave, carry);
     if (tid == 0) {
+        const long long carry_k = carry[0], carry_t = carry[1];
         const bool bad = a.scan[SEL_BAD] != 0;
         const bool fits = !bad && carry_t <= a.ids_cap;
         if (!bad && !fits) rows_raise(a, TD_E_CAPACITY, carry_t);
@@ -139,7 +116,7 @@ __global__ __launch_bounds__(SEL_THREADS) void td_sel_first(const SelectArgs a) 
     SelEntry e[4];
     long long sum_k = 0, sum_t = 0;
     for (int q = 0; q < 4; ++q) {
-        const int64_t i = (int64_t)blockIdx.x * SEL_SCAN_ENTRIES + tid * 4 + q;
+        const int64_t i = (int64_t)blockIdx.x * RC_SCAN_CHUNK + tid * 4 + q;
         e[q] = i < a.n_sel ? sel_entry(a, i) : SelEntry{};
         sum_k += e[q].keep;
         sum_t += e[q].keep ? e[q].len : 0;
@@ -158,72 +135,32 @@ __global__ __launch_bounds__(SEL_THREADS) void td_sel_first(const SelectArgs a) 
     if (blockIdx.x == 0 && tid == 0) a.out_off[a.scan[SEL_K]] = (int64_t)a.scan[SEL_T];
 }
 
-// The last index q in [lo, hi) with p[q] <= x, given p[lo] <= x and p non-decreasing: 256 probes a step, the same in every lane.
-__device__ __forceinline__ int64_t sel_search(const int64_t* p, int64_t lo, int64_t hi, int64_t x) {
-    const int tid = threadIdx.x;
-    while (hi - lo > 1) {
-        const int64_t stp = (hi - lo + SEL_THREADS - 1) / SEL_THREADS;
-        const int64_t q = lo + (int64_t)tid * stp;
-        const int c = __syncthreads_count(tid > 0 && q < hi && p[q] <= x);
-        hi = hi < lo + (int64_t)(c + 1) * stp ? hi : lo + (int64_t)(c + 1) * stp;
-        lo += (int64_t)c * stp;
-    }
-    return lo;
-}
-
 template <class A>
 __global__ __launch_bounds__(SEL_THREADS) void td_sel_slots(const A a) {
     constexpr bool LAB = has_lab<A>;
     constexpr int ITERS = SEL_TILE / (4 * SEL_THREADS);
-    __shared__ int32_t s_off[SEL_LDS_DOCS];  // out_off[k0 + i] - s0, clamped to [0, SEL_TILE + 1]
+    __shared__ int32_t s_off[RC_LDS_DOCS];  // out_off[k0 + i] - s0, clamped to [0, SEL_TILE + 1]
     const int tid = threadIdx.x;
     if (a.scan[SEL_LEAVE]) return;
     const int64_t K = (int64_t)a.scan[SEL_K], T = (int64_t)a.scan[SEL_T];
     const int64_t ntiles = (T + SEL_TILE - 1) / SEL_TILE;
+    const auto off_of = [off = a.out_off](int64_t k) { return off[k]; };
     for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
         const int64_t s0 = tile * SEL_TILE;
         const int64_t s1 = s0 + SEL_TILE < T ? s0 + SEL_TILE : T;
         const int32_t span = (int32_t)(s1 - s0);
         __syncthreads();  // (the previous tile's readers of s_off are done)
         // k0: the document of slot s0 (out_off[0] = 0 <= s0 < T = out_off[K])
-        const int64_t k0 = sel_search(a.out_off, 0, K, s0);
+        const int64_t k0 = group_last_le(off_of, 0, K, s0);
         const int64_t o0 = a.out_off[k0];
-        int64_t nk = 0;  // documents [k0, k0 + nk) begin below s1; in LDS: s_off[0, nk], the last the end of them all
-        bool lds = false;
-        for (int c0 = 0; c0 < SEL_LDS_DOCS; c0 += SEL_THREADS) {
-            const int64_t k = k0 + c0 + tid;
-            int32_t v = SEL_TILE + 1;
-            if (k <= K) {
-                const int64_t r = a.out_off[k] - s0;
-                v = r < 0 ? 0 : r > SEL_TILE ? SEL_TILE + 1 : (int32_t)r;
-            }
-            s_off[c0 + tid] = v;
-            const int c = __syncthreads_count(k < K && v < span);
-            nk += c;
-            if (c < SEL_THREADS) {
-                lds = true;
-                break;
-            }
-        }
-        if (!lds) nk = sel_search(a.out_off, k0, K, s1 - 1) - k0 + 1;
+        bool lds;
+        // documents [k0, k0 + nk) begin below s1 (out_off[K] = T >= s1 does not); in LDS: s_off[0, nk], the last the end of them all
+        int64_t nk = tile_table(s_off, off_of, k0, K, s0, 0, SEL_TILE + 1, span, lds);
+        if (!lds) nk = group_last_le(off_of, k0, K, s1 - 1) - k0 + 1;
         // i: the last of the tile's documents that begins at or below slot j
         auto find = [&](int64_t j) -> int64_t {
-            int64_t l = 0, h = nk;
-            if (lds) {
-                const int32_t x = (int32_t)(j - s0);
-                while (h - l > 1) {
-                    const int64_t mid = (l + h) >> 1;
-                    if (s_off[mid] <= x) l = mid;
-                    else h = mid;
-                }
-            } else {
-                while (h - l > 1) {
-                    const int64_t mid = (l + h) >> 1;
-                    if (a.out_off[k0 + mid] <= j) l = mid;
-                    else h = mid;
-                }
-            }
-            return l;
+            if (lds) return last_le(s_off, nk, (int32_t)(j - s0));
+            return last_le_global([off = a.out_off + k0](int64_t i) { return off[i]; }, 0, nk, j);
         };
         int32_t v[ITERS][4] = {};
         [[maybe_unused]] int32_t lv[ITERS][4] = {};
@@ -272,7 +209,7 @@ __global__ __launch_bounds__(SEL_THREADS) void td_sel_slots(const A a) {
 
 }  // namespace
 
-int64_t select_scan_words(int64_t n_sel) { return SEL_SCAN_HEAD + 2 * (n_sel > 0 ? (n_sel + SEL_SCAN_ENTRIES - 1) / SEL_SCAN_ENTRIES : 1); }
+int64_t select_scan_words(int64_t n_sel) { return SEL_SCAN_HEAD + 2 * (n_sel > 0 ? (n_sel + RC_SCAN_CHUNK - 1) / RC_SCAN_CHUNK : 1); }
 
 hipError_t launch_select(const SelectLabArgs& al, hipStream_t stream) {
     const SelectArgs& a = al;

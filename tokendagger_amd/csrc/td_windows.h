@@ -11,8 +11,6 @@
 
 namespace td {
 
-constexpr int WIN_LDS_DOCS = 4352;    // first rows of a tile's documents kept in LDS (a tile has at most WIN_TILE + 1 rows)
-constexpr int WIN_SCAN_DOCS = 1024;   // documents per workgroup of the window-count scan (four a lane)
 constexpr int WIN_SCAN_HEAD = 4;      // scan words in front of the chunk sums: real slots, split documents, largest w_d, bad offsets
 
 struct WindowArgs {

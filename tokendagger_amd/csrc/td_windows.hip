@@ -8,16 +8,17 @@
 //
 //   td_win_count    w_d of 1024 documents a workgroup (the division by a host-computed multiplier), the offsets checks, the
 //                   chunk's rows into the scan words, the counts by one atomic a workgroup
-//   td_win_chunks   one workgroup: the chunks' rows -> their exclusive prefixes, first_row[n_docs] = rows (-1: bad offsets),
-//                   the capacity check, counts
+//   td_win_chunks   one workgroup: the chunks' rows -> their exclusive prefixes (chunks_excl_scan<1>, td_rows_common.h),
+//                   first_row[n_docs] = rows (-1: bad offsets), the capacity check, counts
 //   td_win_first    first_row[d] = the chunk's prefix + the scan inside the chunk
 //   td_win_slots    the slots.  td_rows_pad's shape: tiles of 4096 OUTPUT slots, four a lane stored as one int4, so a document of
 //                   a quarter of a million ids is written by as many lanes as its rows have slots.  The rows of a tile are
-//                   consecutive and their documents ascend: one 256-way search over first_row finds the document of the tile's
+//                   consecutive and their documents ascend: group_last_le over first_row finds the document of the tile's
 //                   first row (inside [r - (rows - n_docs), r]: first_row[d] - d never decreases, so without a split document
-//                   the search is no step at all), the first rows of the tile's documents go to LDS, and a lane finds its row's
-//                   document there.  The tile in which a row starts writes the row's length, document and start.  <WindowLabArgs>:
-//                   the pair form, lab.src -> lab.dst beside the ids and the overlap mask (td_rows_common.h); <WindowArgs>: one stream.
+//                   the search is no step at all), tile_table puts the first rows of the tile's documents into LDS, and a lane
+//                   finds its row's document there (last_le; all three in td_rows_common.h).  The tile in which a row starts
+//                   writes the row's length, document and start.  <WindowLabArgs>: the pair form, lab.src -> lab.dst beside the
+//                   ids and the overlap mask (td_rows_common.h); <WindowArgs>: one stream.
 //
 // td_win_slots reads first_row[n_docs] itself (a kernel boundary lies behind td_win_chunks): above the capacity, or -1, it
 // leaves without a store.
@@ -48,15 +49,13 @@ __device__ __forceinline__ int64_t win_count(const WindowArgs& a, int64_t L) {
 }
 
 __global__ __launch_bounds__(WIN_THREADS) void td_win_count(const WindowArgs a) {
-    __shared__ long long s_red[4][WIN_THREADS / 64];
-    __shared__ int s_bad;
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    if (tid == 0) s_bad = 0;
+    __shared__ long long s_red[WIN_THREADS / 64];
+    const int tid = threadIdx.x;
     long long rows = 0, real = 0, multi = 0, mx = 0;
     bool bad = false;
     int64_t bad_at = 0;
     for (int q = 0; q < 4; ++q) {
-        const int64_t d = (int64_t)blockIdx.x * WIN_SCAN_DOCS + tid * 4 + q;
+        const int64_t d = (int64_t)blockIdx.x * RC_SCAN_CHUNK + tid * 4 + q;
         if (d >= a.n_docs) break;
         bool bd = false;
         const int64_t L = win_len(a, d, bd), w = win_count(a, L);
@@ -71,65 +70,29 @@ __global__ __launch_bounds__(WIN_THREADS) void td_win_count(const WindowArgs a) 
         const int64_t o = a.tok_off[0];
         bad = o < 0 || o > a.n_tokens;
     }
-    for (int dd = 32; dd >= 1; dd >>= 1) {
-        rows += __shfl_xor(rows, dd);
-        real += __shfl_xor(real, dd);
-        multi += __shfl_xor(multi, dd);
-        const long long o = __shfl_xor(mx, dd);
-        mx = o > mx ? o : mx;
-    }
-    if (lane == 0) {
-        s_red[0][wv] = rows;
-        s_red[1][wv] = real;
-        s_red[2][wv] = multi;
-        s_red[3][wv] = mx;
-    }
-    __syncthreads();
-    if (bad) {
-        rows_raise(a, TD_E_INVALID, bad_at);
-        s_bad = 1;
-    }
-    __syncthreads();
+    if (bad) rows_raise(a, TD_E_INVALID, bad_at);
+    rows = block_sum(rows, s_red);
+    real = block_sum(real, s_red);
+    multi = block_sum(multi, s_red);
+    mx = block_max(mx, s_red);
+    const long long any_bad = block_max(bad, s_red);
     if (tid == 0) {
-        rows = real = multi = mx = 0;
-        for (int w = 0; w < WIN_THREADS / 64; ++w) {
-            rows += s_red[0][w];
-            real += s_red[1][w];
-            multi += s_red[2][w];
-            mx = s_red[3][w] > mx ? s_red[3][w] : mx;
-        }
         a.scan[WIN_SCAN_HEAD + blockIdx.x] = (unsigned long long)rows;
         if (real) atomicAdd(&a.scan[0], (unsigned long long)real);
         if (multi) atomicAdd(&a.scan[1], (unsigned long long)multi);
         if (mx) atomicMax(&a.scan[2], (unsigned long long)mx);
-        if (s_bad) atomicAdd(&a.scan[3], 1ull);
+        if (any_bad) atomicAdd(&a.scan[3], 1ull);
     }
 }
 
 __global__ __launch_bounds__(WIN_THREADS) void td_win_chunks(const WindowArgs a, int64_t nch) {
     __shared__ long long s_wave[WIN_THREADS / 64];
     const int tid = threadIdx.x;
-    unsigned long long* cs = a.scan + WIN_SCAN_HEAD;
-    long long carry = 0;
-    for (int64_t base = 0; base < nch; base += 4 * WIN_THREADS) {
-        long long v[4], sum = 0;
-        for (int q = 0; q < 4; ++q) {
-            const int64_t c = base + tid * 4 + q;
-            v[q] = c < nch ? (long long)cs[c] : 0;
-            sum += v[q];
-        }
-        long long total;
-        long long run = carry + block_excl(sum, s_wave, total);
-        for (int q = 0; q < 4; ++q) {
-            const int64_t c = base + tid * 4 + q;
-            if (c < nch) cs[c] = (unsigned long long)run;
-            run += v[q];
-        }
-        carry += total;
-    }
+    long long carry[1];
+    chunks_excl_scan<1>(a.scan + WIN_SCAN_HEAD, nch, s_wave, carry);
     if (tid == 0) {
         const bool bad = a.scan[3] != 0;
-        const int64_t rows = a.n_docs > 0 ? carry : 0;
+        const int64_t rows = a.n_docs > 0 ? carry[0] : 0;
         a.first_row[a.n_docs] = bad ? -1 : rows;
         const bool fits = !bad && rows <= a.rows_cap;
         if (!bad && !fits) rows_raise(a, TD_E_CAPACITY, rows);
@@ -145,7 +108,7 @@ __global__ __launch_bounds__(WIN_THREADS) void td_win_first(const WindowArgs a) 
     const int tid = threadIdx.x;
     long long v[4], sum = 0;
     for (int q = 0; q < 4; ++q) {
-        const int64_t d = (int64_t)blockIdx.x * WIN_SCAN_DOCS + tid * 4 + q;
+        const int64_t d = (int64_t)blockIdx.x * RC_SCAN_CHUNK + tid * 4 + q;
         bool bd = false;
         v[q] = d < a.n_docs ? win_count(a, win_len(a, d, bd)) : 0;
         sum += v[q];
@@ -153,7 +116,7 @@ __global__ __launch_bounds__(WIN_THREADS) void td_win_first(const WindowArgs a) 
     long long total;
     long long run = (long long)a.scan[WIN_SCAN_HEAD + blockIdx.x] + block_excl(sum, s_wave, total);
     for (int q = 0; q < 4; ++q) {
-        const int64_t d = (int64_t)blockIdx.x * WIN_SCAN_DOCS + tid * 4 + q;
+        const int64_t d = (int64_t)blockIdx.x * RC_SCAN_CHUNK + tid * 4 + q;
         if (d < a.n_docs) a.first_row[d] = run;
         run += v[q];
     }
@@ -162,56 +125,32 @@ __global__ __launch_bounds__(WIN_THREADS) void td_win_first(const WindowArgs a) 
 template <class A>
 __global__ __launch_bounds__(WIN_THREADS) void td_win_slots(const A a) {
     constexpr bool LAB = has_lab<A>;
-    __shared__ int32_t s_fr[WIN_LDS_DOCS];  // first rows of the tile's documents - r0, clamped to [-1, WIN_TILE + 2]
+    // (rows ascend by one and a document has at least one: at most WIN_TILE + 1 documents have a row in the tile, and the step of
+    // the table that holds the one behind them ends below RC_LDS_DOCS; tile_table always fits)
+    static_assert(RC_LDS_DOCS >= WIN_TILE + 1 + WIN_THREADS - 1, "td_win_slots has no path for a table that does not fit");
+    __shared__ int32_t s_fr[RC_LDS_DOCS];  // first rows of the tile's documents - r0, clamped to [-1, WIN_TILE + 2]
     const int tid = threadIdx.x;
     const int64_t rows = a.first_row[a.n_docs];
     if (rows < 0 || rows > a.rows_cap) return;
     const int64_t S = a.S, total = rows * S, extra = rows - a.n_docs;
     const int64_t ntiles = (total + WIN_TILE - 1) / WIN_TILE;
+    const auto first_of = [fr = a.first_row](int64_t d) { return fr[d]; };
     for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
         const int64_t s0 = tile * WIN_TILE;
         const int64_t s1 = s0 + WIN_TILE < total ? s0 + WIN_TILE : total;
         const int64_t r0 = div_magic(s0, S, a.s_magic);
         const int nr = (int)(div_magic(s1 - 1, S, a.s_magic) - r0) + 1;  // rows [r0, r0 + nr) have slots in the tile
         __syncthreads();  // (the previous tile's readers of s_fr are done)
-        // d0: the last document with first_row[d] <= r0.  d <= first_row[d] <= d + extra bounds it; 256 probes a step
-        int64_t lo = r0 > extra ? r0 - extra : 0, hi = (r0 < a.n_docs - 1 ? r0 : a.n_docs - 1) + 1;
-        while (hi - lo > 1) {
-            const int64_t stp = (hi - lo + WIN_THREADS - 1) / WIN_THREADS;
-            const int64_t q = lo + (int64_t)tid * stp;
-            const int c = __syncthreads_count(tid > 0 && q < hi && a.first_row[q] <= r0);
-            hi = hi < lo + (int64_t)(c + 1) * stp ? hi : lo + (int64_t)(c + 1) * stp;
-            lo += (int64_t)c * stp;
-        }
-        const int64_t d0 = lo, fr0 = a.first_row[d0];
-        int nl = 0;  // documents with rows in the tile: s_fr[0, nl), and s_fr[nl] the first row of the next (>= nr)
-        for (int c0 = 0; c0 + WIN_THREADS <= WIN_LDS_DOCS; c0 += WIN_THREADS) {
-            const int64_t d = d0 + c0 + tid;
-            int32_t v = WIN_TILE + 2;
-            if (d <= a.n_docs) {
-                const int64_t r = a.first_row[d] - r0;
-                v = r < 0 ? -1 : r > WIN_TILE + 1 ? WIN_TILE + 2 : (int32_t)r;
-            }
-            s_fr[c0 + tid] = v;
-            const int c = __syncthreads_count(v < nr);
-            nl += c;
-            if (c < WIN_THREADS) break;
-        }
+        // d0: the last document with first_row[d] <= r0.  d <= first_row[d] <= d + extra bounds it
+        const int64_t d0 = group_last_le(first_of, r0 > extra ? r0 - extra : 0, (r0 < a.n_docs - 1 ? r0 : a.n_docs - 1) + 1, r0);
+        const int64_t fr0 = a.first_row[d0];
+        // documents with rows in the tile: s_fr[0, nl), and s_fr[nl] the first row of the next (>= nr)
+        const int nl = tile_table(s_fr, first_of, d0, a.n_docs, r0, -1, WIN_TILE + 2, nr);
         for (int it = 0; it < WIN_TILE / (4 * WIN_THREADS); ++it) {
             const int64_t j0 = s0 + (int64_t)it * 4 * WIN_THREADS + 4 * tid;
             if (j0 >= s1) break;
             int64_t r = div_magic(j0, S, a.s_magic), o = j0 - r * S;
-            int i;
-            {  // the row's document: the last of the tile's with first row <= r
-                const int32_t x = (int32_t)(r - r0);
-                int l2 = 0, h2 = nl;
-                while (h2 - l2 > 1) {
-                    const int mid = (l2 + h2) >> 1;
-                    if (s_fr[mid] <= x) l2 = mid;
-                    else h2 = mid;
-                }
-                i = l2;
-            }
+            int i = last_le(s_fr, nl, (int32_t)(r - r0));  // the row's document: the last of the tile's with first row <= r
             int64_t d = 0, tlo = 0, start = 0, body = 0, len = 0;
             auto load_row = [&] {
                 d = d0 + i;
@@ -272,7 +211,7 @@ __global__ __launch_bounds__(WIN_THREADS) void td_win_slots(const A a) {
 
 }  // namespace
 
-int64_t windows_scan_words(int64_t n_docs) { return WIN_SCAN_HEAD + (n_docs > 0 ? (n_docs + WIN_SCAN_DOCS - 1) / WIN_SCAN_DOCS : 1); }
+int64_t windows_scan_words(int64_t n_docs) { return WIN_SCAN_HEAD + (n_docs > 0 ? (n_docs + RC_SCAN_CHUNK - 1) / RC_SCAN_CHUNK : 1); }
 
 hipError_t launch_windows(const WindowLabArgs& al, hipStream_t stream) {
     const WindowArgs& a = al;

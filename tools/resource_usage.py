@@ -15,7 +15,7 @@ cc = subprocess.run(["/opt/rocm/bin/hipcc", "--version"], capture_output=True, t
 out = [f"# {cc[0] if cc else 'hipcc'}; {cc[1] if len(cc) > 1 else ''}",
        f"# hipcc --offload-arch=gfx950 -O3 -Rpass-analysis=kernel-resource-usage on these sources (kernel source sha {bench.kernel_source_sha()})",
        "# kernel | VGPRs | spilled VGPRs | scratch B/lane | waves/SIMD | LDS B/workgroup | SGPRs | spilled SGPRs"]
-for src in ("td_kernels.hip", "td_generic.hip", "td_special.hip", "td_rows.hip", "td_pack.hip", "td_windows.hip", "td_labels.hip", "td_select.hip"):
+for src in ("td_kernels.hip", "td_generic.hip", "td_special.hip", "td_rows.hip", "td_pack.hip", "td_windows.hip", "td_labels.hip", "td_select.hip", "td_offsets.hip"):
     p = subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", f"-I{ROOT / 'include'}", "-c",
                         str(ROOT / "tokendagger_amd" / "csrc" / src), "-o", "/dev/null", "-Rpass-analysis=kernel-resource-usage"],
                        capture_output=True, text=True)
