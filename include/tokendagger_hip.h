@@ -568,6 +568,91 @@ int td_encode_batch_span_label_rows(td_tokenizer* t, const uint8_t* text, const 
                                     const td_label_rows_outputs* host_out, int64_t rows_capacity, int64_t* row_counts,
                                     int64_t* label_counts);
 
+/* ---- loss labels from byte ranges: train only on marked text ranges (td_ranges.hip) -------------------------------------------
+ * For data whose trained regions are known as offsets into the TEXT (plain-text templates, prompt / completion pairs, field
+ * values of tool traces), where td_labels_spec's id events do not exist.  Inputs beside ids[n_tokens] and tok_offsets[n_docs + 1]:
+ *   range_offsets[n_docs + 1] (int64): the first range of every document; starts at 0, never decreases, ends at n_ranges;
+ *   ranges[n_ranges][2] (int64, interleaved begin, end): byte offsets RELATIVE TO THE DOCUMENT'S FIRST BYTE, half-open.
+ * Per document the ranges must satisfy 0 <= begin <= end and be sorted and disjoint: begin[r + 1] >= end[r].  Touching ranges
+ * and empty ranges are legal; an empty range marks nothing.
+ *
+ * Byte p of document d is MARKED iff some range of d has begin <= p < end.  Id i of d occupies the bytes [s_i, e_i),
+ * e_i = s_i + len(ids[i]) (the length of the id's bytes in the vocabulary, special tokens included); m_i is the number of marked
+ * bytes among them.  trained(i) by td_range_spec.rule:
+ *   TD_RANGE_OVERLAP   m_i > 0
+ *   TD_RANGE_INSIDE    m_i == e_i - s_i
+ *   TD_RANGE_START     byte s_i is marked
+ * Because the rule is by bytes, two touching ranges behave as one and empty ranges need no special case.
+ *
+ * Outputs, as td_span_labels':
+ *   labels[i] = trained(i) ? ids[i] : ignore_index                                   (int32, required)
+ *   mask[i] = trained(i)                                                             (uint8, optional)
+ *   trained_offsets[n_docs + 1]: the trained ids in front of every document start, the total last   (int64, optional)
+ *   counts[4] = {trained ids, partially marked ids (0 < m_i < e_i - s_i: they straddle an edge of a range),
+ *                marked bytes (the sum of end - begin), 0}                           (int64, required)
+ * Slots at or above tok_offsets[n_docs] are not written.
+ *
+ * Where s_i comes from:
+ *   starts == NULL   the COVERED rule of td_token_starts: every document's bytes are its ids' bytes concatenated, s_i is the sum of
+ *                    the lengths in front of i in its document.  The starts are scanned on the fly and never stored.  An id
+ *                    outside the vocabulary is TD_E_BAD_TOKEN with its index (the lowest), as in td_token_starts.  A range that
+ *                    ends beyond the document's covered bytes is TD_E_INVALID with err_pos = the global index of the first such
+ *                    range (the lowest); a document without ids may have no range with end > 0.
+ *   starts != NULL   int64 byte starts, one per id, as td_encode_*_with_starts produce them (TD_UNIT_BYTES; they do not decrease
+ *                    inside a document): the way in for generic patterns that skip text.  len still comes from the vocabulary (an
+ *                    id outside it: TD_E_BAD_TOKEN); the upper bound of the ranges is not checked, the document's length is unknown.
+ *
+ * Errors.  Spec errors (unknown rule, flags != 0, ignore_index outside int32) are TD_E_INVALID with a message, before any launch.
+ * tok_offsets or range_offsets that do not start at 0, decrease, are negative or end above n_tokens / differ from n_ranges at the
+ * end: TD_E_INVALID with err_pos = the document.  A range that is negative, reversed, or begins in front of the end of the one
+ * before it in its document: TD_E_INVALID with err_pos = the global range index, the lowest.  These structural errors are found
+ * before anything is written: no output is touched.  The covered form finds a range beyond its document during the labelling pass:
+ * the outputs are then unspecified and the error is reported. */
+#define TD_RANGE_OVERLAP 0
+#define TD_RANGE_INSIDE 1
+#define TD_RANGE_START 2
+typedef struct td_range_spec {
+    int64_t rule;         /* TD_RANGE_* */
+    int64_t ignore_index; /* any int32, e.g. -100 */
+    int64_t flags;        /* 0 */
+} td_range_spec;
+
+/* The structural checks alone, on the host (no handle, no device): range_offsets, then every range in order.  doc_lens[n_docs]
+ * (may be NULL): the documents' byte lengths, a range may not end above its document's.  counts[2] = {non-empty ranges, marked
+ * bytes}.  TD_E_INVALID with *bad = the first bad document (range_offsets) or the first bad global range index; *bad = -1 for a
+ * NULL argument or n_docs < 0.  counts and bad may be NULL. */
+int td_range_plan(const int64_t* range_offsets, const int64_t* ranges, int64_t n_docs, const int64_t* doc_lens, int64_t* counts,
+                  int64_t* bad);
+/* Device buffers, asynchronously on hip_stream (no synchronisation, no read-back); errors through td_device_status.  d_starts,
+ * d_mask and d_trained_offsets may be NULL; d_ranges must be 8-byte aligned. */
+int td_range_labels_device(td_tokenizer* t, const void* d_ids, int64_t n_tokens, const void* d_tok_offsets, int64_t n_docs,
+                           const void* d_starts, const void* d_range_offsets, const void* d_ranges, int64_t n_ranges,
+                           const td_range_spec* spec, void* d_labels, void* d_mask, void* d_trained_offsets, void* d_counts,
+                           void* hip_stream);
+/* Host buffers, synchronous; the offsets and the ranges' order are checked on the host first (td_range_plan).  starts, mask and
+ * trained_offsets may be NULL. */
+int td_range_labels(td_tokenizer* t, const int32_t* ids, int64_t n_tokens, const int64_t* tok_offsets, int64_t n_docs,
+                    const int64_t* starts, const int64_t* range_offsets, const int64_t* ranges, const td_range_spec* spec,
+                    int32_t* labels, uint8_t* mask, int64_t* trained_offsets, int64_t* counts);
+/* td_encode_batch_with_special_strs (the same ids and offsets) and the covered form in one call, from text and byte ranges into it
+ * to ids + labels: where the encode leaves its ids on the device they are labelled there.  Range ends are checked against
+ * doc_offsets as well (td_range_plan with the documents' lengths).  A document whose ids cover fewer bytes than it has (a generic
+ * split pattern that skipped text) fails with TD_E_INVALID: use td_encode_batch_with_starts and the explicit-starts form.
+ * out_labels (and out_mask) have room for out_capacity entries.  *n_tokens = ids needed (also on TD_E_CAPACITY).  Synchronous. */
+int td_encode_batch_range_labels(td_tokenizer* t, const uint8_t* text, const int64_t* doc_offsets, int64_t n_docs,
+                                 const uint8_t* allowed_bytes, const int64_t* allowed_offsets, int64_t n_allowed,
+                                 const int64_t* range_offsets, const int64_t* ranges, const td_range_spec* spec, int32_t* out_tokens,
+                                 int64_t out_capacity, int64_t* out_offsets, int32_t* out_labels, uint8_t* out_mask,
+                                 int64_t* out_trained_offsets, int64_t* counts, int64_t* n_tokens);
+/* td_encode_batch_span_label_rows with byte ranges in place of id spans: td_encode_batch_range_labels followed by the labeled row
+ * call of rspec->layout.  Ids and labels stay on the device between the steps; everything else as there. */
+int td_encode_batch_range_label_rows(td_tokenizer* t, const uint8_t* text, const int64_t* doc_offsets, int64_t n_docs,
+                                     const uint8_t* allowed_bytes, const int64_t* allowed_offsets, int64_t n_allowed,
+                                     const int64_t* range_offsets, const int64_t* ranges, const td_range_spec* rgspec,
+                                     const td_rows_spec* rspec, int64_t overlap, const td_rows_labels* lab,
+                                     const td_label_rows_outputs* host_out, int64_t rows_capacity, int64_t* row_counts,
+                                     int64_t* label_counts);
+
 /* Options. */
 #define TD_OPT_LONG_POOL_BYTES 1 /* scratch for pieces longer than 64 bytes (default max(64 MiB, 2 x input)) */
 #define TD_OPT_PROFILE 2         /* 1: bracket the kernels of every td_encode_device call with HIP events on the

@@ -63,6 +63,7 @@ EXPORTS = [
     "td_make_rows_labeled", "td_make_rows_labeled_device", "td_pack_rows_labeled", "td_pack_rows_labeled_device",
     "td_window_rows_labeled", "td_window_rows_labeled_device", "td_encode_batch_span_label_rows",
     "td_select_plan", "td_select_docs", "td_select_docs_device", "td_encode_batch_select",
+    "td_range_plan", "td_range_labels", "td_range_labels_device", "td_encode_batch_range_labels", "td_encode_batch_range_label_rows",
 ]
 
 
@@ -162,6 +163,16 @@ def load_library():
     lib.td_select_docs.argtypes = [vp, vp, vp, i64, vp, i64, vp, i64, vp, vp, vp, i64, vp, vp, vp]
     lib.td_encode_batch_select.restype = i32
     lib.td_encode_batch_select.argtypes = [vp, vp, vp, i64, i32, vp, i64, vp, vp, i64, vp, vp, vp]
+    lib.td_range_plan.restype = i32
+    lib.td_range_plan.argtypes = [vp, vp, i64, vp, vp, ctypes.POINTER(i64)]
+    lib.td_range_labels_device.restype = i32
+    lib.td_range_labels_device.argtypes = [vp, vp, i64, vp, i64, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp]
+    lib.td_range_labels.restype = i32
+    lib.td_range_labels.argtypes = [vp, vp, i64, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.td_encode_batch_range_labels.restype = i32
+    lib.td_encode_batch_range_labels.argtypes = [vp, vp, vp, i64, vp, vp, i64, vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, ctypes.POINTER(i64)]
+    lib.td_encode_batch_range_label_rows.restype = i32
+    lib.td_encode_batch_range_label_rows.argtypes = [vp, vp, vp, i64, vp, vp, i64, vp, vp, vp, vp, i64, vp, vp, i64, vp, vp]
     lib.td_comm_unique_id.restype = i32
     lib.td_comm_unique_id.argtypes = [vp]
     lib.td_comm_create.restype = i32
@@ -427,6 +438,86 @@ def labels_spec(open, close, ignore_index: int = -100, train_close: bool = True)
     for k, c in enumerate(close):
         sp.close_ids[k] = c
     return sp
+
+
+TD_RANGE_OVERLAP, TD_RANGE_INSIDE, TD_RANGE_START = 0, 1, 2
+RANGE_RULES = {"overlap": TD_RANGE_OVERLAP, "inside": TD_RANGE_INSIDE, "start": TD_RANGE_START}
+
+
+class RangeSpec(ctypes.Structure):
+    """td_range_spec (include/tokendagger_hip.h): the rule, ignore_index, flags."""
+    _fields_ = [("rule", ctypes.c_int64), ("ignore_index", ctypes.c_int64), ("flags", ctypes.c_int64)]
+
+
+def range_spec(rule="overlap", ignore_index: int = -100, flags: int = 0) -> RangeSpec:
+    """rule: "overlap" (an id with a marked byte is trained), "inside" (all of its bytes), "start" (its first byte), or a TD_RANGE_*
+    value; what fits the struct is passed on as it is, the library checks it."""
+    if isinstance(rule, str):
+        if rule not in RANGE_RULES:
+            raise ValueError(f"rule must be one of {sorted(RANGE_RULES)}, not {rule!r}")
+        rule = RANGE_RULES[rule]
+    return RangeSpec(int(rule), int(ignore_index), int(flags))
+
+
+def as_ranges(ranges, n_docs: int | None = None):
+    """Byte ranges in either form -> (range_offsets int64[n_docs + 1], ranges int64[n, 2], both contiguous): a pair
+    (range_offsets, array[n, 2]), or one sequence of (begin, end) pairs per document."""
+    if isinstance(ranges, tuple) and len(ranges) == 2 and isinstance(ranges[1], np.ndarray) and ranges[1].ndim == 2:
+        ro = np.ascontiguousarray(ranges[0], dtype=np.int64)
+        rg = np.ascontiguousarray(ranges[1], dtype=np.int64)
+    else:
+        per = [np.asarray(r, dtype=np.int64).reshape(-1, 2) for r in ranges]
+        ro = np.zeros(len(per) + 1, dtype=np.int64)
+        if per:
+            np.cumsum([len(r) for r in per], out=ro[1:])
+        rg = np.ascontiguousarray(np.concatenate(per) if per else np.zeros((0, 2), dtype=np.int64))
+    if rg.ndim != 2 or rg.shape[1] != 2:
+        raise ValueError("ranges must have the shape [n, 2]")
+    if len(ro) < 1 or (n_docs is not None and len(ro) != n_docs + 1):
+        raise ValueError("ranges must have an entry (range_offsets: n_docs + 1 entries) for every document")
+    if len(ro) and int(ro[-1]) > len(rg):
+        raise ValueError("range_offsets end above the number of ranges")
+    return ro, rg
+
+
+def range_plan(ranges, doc_lens=None):
+    """td_range_plan (host only, no device): the structural checks of byte ranges -> counts int64[2] = non-empty ranges, marked
+    bytes.  doc_lens: the documents' byte lengths (a range may not end above its document's).  An error carries .bad: the first
+    bad document (range_offsets) or the first bad global range index."""
+    lib = load_library()
+    ro, rg = as_ranges(ranges)
+    n_docs = len(ro) - 1
+    dl = None if doc_lens is None else np.ascontiguousarray(doc_lens, dtype=np.int64)
+    if dl is not None and len(dl) != n_docs:
+        raise ValueError("doc_lens must have an entry for every document")
+    counts = np.zeros(2, dtype=np.int64)
+    bad = ctypes.c_int64(-1)
+    rc = lib.td_range_plan(ro.ctypes.data, rg.ctypes.data if len(rg) else None, n_docs, dl.ctypes.data if dl is not None else None,
+                           counts.ctypes.data, ctypes.byref(bad))
+    if rc != TD_OK:
+        ex = TokenDaggerHipError(rc, f"td_range_plan: invalid range_offsets or ranges at index {bad.value}")
+        ex.bad = bad.value
+        raise ex
+    return counts
+
+
+def chars_to_bytes(text, doc_offsets, ranges):
+    """Ranges in characters -> the same in bytes, on the host (one numpy pass over the text): index k of a document is its k-th
+    byte that is not a UTF-8 continuation byte, k equal to their number is the document's end.  Returns (range_offsets, ranges)."""
+    buf = _as_u8(text)
+    offs = np.ascontiguousarray(doc_offsets, dtype=np.int64)
+    ro, rg = as_ranges(ranges, len(offs) - 1)
+    lead = np.flatnonzero((buf[:int(offs[-1])] & 0xC0) != 0x80).astype(np.int64)  # the positions of the characters' first bytes
+    first = np.searchsorted(lead, offs)  # characters in front of every document (and of the text's end)
+    doc = np.repeat(np.arange(len(offs) - 1), np.diff(ro))
+    k = rg[:int(ro[-1])]
+    n_chars = (first[1:] - first[:-1])[doc][:, None]
+    if ((k < 0) | (k > n_chars)).any():
+        raise ValueError("a character range lies outside its document")
+    g = first[doc][:, None] + k
+    table = np.concatenate([lead, [0]])
+    out = np.where(k == n_chars, offs[1:][doc][:, None], table[np.minimum(g, len(lead))]) - offs[:-1][doc][:, None]
+    return ro, np.ascontiguousarray(out, dtype=np.int64)
 
 
 def _as_u8(data) -> np.ndarray:
@@ -862,6 +953,64 @@ class HipTokenizer:
         k = ntok.value
         return toks[:k].copy(), out_offs, lab[:k].copy(), m[:k].copy() if mask else None, to, counts
 
+    # ---- loss labels from byte ranges (td_range_spec) ------------------------------------------------------------
+    range_spec = staticmethod(range_spec)
+    range_plan = staticmethod(range_plan)
+
+    def range_labels(self, ids, tok_offsets, ranges, spec: RangeSpec, mask: bool = False, trained_offsets: bool = False, starts=None,
+                     n_tokens: int | None = None):
+        """td_range_labels -> (labels int32[total], mask uint8[total] | None, trained_offsets int64[n_docs + 1] | None,
+        counts int64[4] = trained ids, partially marked ids, marked bytes, 0).  ranges: see as_ranges.  starts None: the covered
+        form; else int64 byte starts, one per id."""
+        t = np.ascontiguousarray(ids, dtype=np.int32)
+        o = np.ascontiguousarray(tok_offsets, dtype=np.int64)
+        n_docs, total = len(o) - 1, int(o[-1])
+        ro, rg = as_ranges(ranges, n_docs)
+        st = None if starts is None else np.ascontiguousarray(starts, dtype=np.int64)
+        if st is not None and len(st) < total:
+            raise ValueError("starts must have an entry for every id")
+        lab = np.empty(max(total, 1), dtype=np.int32)
+        m = np.empty(max(total, 1), dtype=np.uint8) if mask else None
+        to = np.empty(n_docs + 1, dtype=np.int64) if trained_offsets else None
+        counts = np.zeros(4, dtype=np.int64)
+        self._check(self._lib.td_range_labels(self._h, t.ctypes.data if len(t) else None, len(t) if n_tokens is None else n_tokens, o.ctypes.data,
+                                              n_docs, st.ctypes.data if st is not None and len(st) else None, ro.ctypes.data,
+                                              rg.ctypes.data if len(rg) else None, ctypes.byref(spec), lab.ctypes.data,
+                                              m.ctypes.data if mask else None, to.ctypes.data if trained_offsets else None, counts.ctypes.data))
+        return lab[:total], m[:total] if mask else None, to, counts
+
+    def range_labels_device(self, d_ids: int, n_tokens: int, d_tok_offsets: int, n_docs: int, d_range_offsets: int, d_ranges: int, n_ranges: int,
+                            spec: RangeSpec, d_labels: int, d_mask: int = 0, d_trained_offsets: int = 0, d_counts: int = 0, d_starts: int = 0,
+                            stream: int = 0):
+        """td_range_labels_device: raw device pointers, asynchronous on `stream`; check with device_status(stream)."""
+        self._check(self._lib.td_range_labels_device(self._h, d_ids or None, n_tokens, d_tok_offsets, n_docs, d_starts or None, d_range_offsets,
+                                                     d_ranges or None, n_ranges, ctypes.byref(spec), d_labels or None, d_mask or None,
+                                                     d_trained_offsets or None, d_counts or None, stream or None))
+
+    def encode_batch_range_labels(self, text, doc_offsets, allowed, ranges, spec: RangeSpec, mask: bool = False, trained_offsets: bool = False):
+        """td_encode_batch_range_labels: encode_batch_with_special_strs + range_labels (covered form) in one call ->
+        (tokens int32[total], offsets int64[n_docs + 1], labels, mask | None, trained_offsets | None, counts)."""
+        buf = _as_u8(text)
+        offs = np.ascontiguousarray(doc_offsets, dtype=np.int64)
+        ab, ao = self._pack_strs(list(allowed))
+        n_docs = len(offs) - 1
+        ro, rg = as_ranges(ranges, n_docs)
+        n = int(offs[-1]) if len(offs) else 0
+        cap = n + 16
+        out_offs = np.empty(n_docs + 1, dtype=np.int64)
+        toks, lab = np.empty(cap, dtype=np.int32), np.empty(cap, dtype=np.int32)
+        m = np.empty(cap, dtype=np.uint8) if mask else None
+        to = np.empty(n_docs + 1, dtype=np.int64) if trained_offsets else None
+        counts = np.zeros(4, dtype=np.int64)
+        ntok = ctypes.c_int64(0)
+        self._check(self._lib.td_encode_batch_range_labels(self._h, buf.ctypes.data if n else None, offs.ctypes.data, n_docs, ab.ctypes.data,
+                                                           ao.ctypes.data, len(ao) - 1, ro.ctypes.data, rg.ctypes.data if len(rg) else None,
+                                                           ctypes.byref(spec), toks.ctypes.data, cap, out_offs.ctypes.data, lab.ctypes.data,
+                                                           m.ctypes.data if mask else None, to.ctypes.data if trained_offsets else None,
+                                                           counts.ctypes.data, ctypes.byref(ntok)))
+        k = ntok.value
+        return toks[:k].copy(), out_offs, lab[:k].copy(), m[:k].copy() if mask else None, to, counts
+
     # ---- label rows (td_rows_labels): the labeled form of the row calls ---------------------------------------------
     def _check_counts(self, rc: int, counts):
         try:
@@ -942,12 +1091,9 @@ class HipTokenizer:
                                                             overlap, ctypes.byref(outs), rows_capacity, d_counts or None, stream or None,
                                                             ctypes.byref(lab)))
 
-    def encode_batch_span_label_rows(self, text, doc_offsets, allowed, lspec: LabelsSpec, rspec: RowsSpec, lab: RowsLabels, overlap: int = 0,
-                                     positions: bool = False, aux: bool = True, lengths: bool = True, docs: bool = True, starts: bool = True,
-                                     rows_capacity: int | None = None):
-        """td_encode_batch_span_label_rows: chat text -> the layout's result tuple (as make_rows / pack_rows / window_rows give it,
-        counts = the row counts), then the label rows int32[rows, S] and the labels' counts int64[4].  The default capacity is the
-        most rows the text can need (one id per byte)."""
+    def _encode_label_rows(self, fn, text, doc_offsets, allowed, lspec_args, rspec: RowsSpec, lab: RowsLabels, overlap, positions, aux, lengths,
+                           docs, starts, rows_capacity):
+        """The body of the two text-to-label-rows calls; lspec_args: what `fn` takes between the allowed strings and the rows spec."""
         buf = _as_u8(text)
         offs = np.ascontiguousarray(doc_offsets, dtype=np.int64)
         ab, ao = self._pack_strs(list(allowed))
@@ -974,12 +1120,29 @@ class HipTokenizer:
                 "pack": lambda: LabelRowsOutputs(addr[0], dst.ctypes.data, addr[1], addr[2], addr[3], addr[4], none, none),
                 "windows": lambda: LabelRowsOutputs(addr[0], dst.ctypes.data, addr[1], none, addr[2], none, addr[3], addr[4])}[kind]()
         lcounts = np.zeros(4, dtype=np.int64)
-        rc = self._lib.td_encode_batch_span_label_rows(self._h, buf.ctypes.data if n else None, offs.ctypes.data, n_docs, ab.ctypes.data,
-                                                       ao.ctypes.data, len(ao) - 1, ctypes.byref(lspec), ctypes.byref(rspec), overlap,
-                                                       ctypes.byref(lab), ctypes.byref(outs), rows, counts.ctypes.data, lcounts.ctypes.data)
+        rc = fn(self._h, buf.ctypes.data if n else None, offs.ctypes.data, n_docs, ab.ctypes.data, ao.ctypes.data, len(ao) - 1, *lspec_args,
+                ctypes.byref(rspec), overlap, ctypes.byref(lab), ctypes.byref(outs), rows, counts.ctypes.data, lcounts.ctypes.data)
         self._check_counts(rc, counts)
         r = int(counts[0])
         return (*self._rows_result(kind, rspec, b, counts, n_docs), dst[:r * S].reshape(r, S).copy(), lcounts)
+
+    def encode_batch_span_label_rows(self, text, doc_offsets, allowed, lspec: LabelsSpec, rspec: RowsSpec, lab: RowsLabels, overlap: int = 0,
+                                     positions: bool = False, aux: bool = True, lengths: bool = True, docs: bool = True, starts: bool = True,
+                                     rows_capacity: int | None = None):
+        """td_encode_batch_span_label_rows: chat text -> the layout's result tuple (as make_rows / pack_rows / window_rows give it,
+        counts = the row counts), then the label rows int32[rows, S] and the labels' counts int64[4].  The default capacity is the
+        most rows the text can need (one id per byte)."""
+        return self._encode_label_rows(self._lib.td_encode_batch_span_label_rows, text, doc_offsets, allowed, (ctypes.byref(lspec),), rspec, lab,
+                                       overlap, positions, aux, lengths, docs, starts, rows_capacity)
+
+    def encode_batch_range_label_rows(self, text, doc_offsets, allowed, ranges, rgspec: RangeSpec, rspec: RowsSpec, lab: RowsLabels,
+                                      overlap: int = 0, positions: bool = False, aux: bool = True, lengths: bool = True, docs: bool = True,
+                                      starts: bool = True, rows_capacity: int | None = None):
+        """td_encode_batch_range_label_rows: text and byte ranges -> what encode_batch_span_label_rows returns."""
+        ro, rg = as_ranges(ranges, len(doc_offsets) - 1)
+        return self._encode_label_rows(self._lib.td_encode_batch_range_label_rows, text, doc_offsets, allowed,
+                                       (ro.ctypes.data, rg.ctypes.data if len(rg) else None, ctypes.byref(rgspec)), rspec, lab, overlap, positions,
+                                       aux, lengths, docs, starts, rows_capacity)
 
     # ---- document selection (td_select_spec) ------------------------------------------------------------------
     def select_docs(self, ids, tok_offsets, sel=None, spec: SelectSpec | None = None, labels=None, docs: bool = True,

@@ -79,15 +79,24 @@ int labels_launch_locked(td_tokenizer* t, const void* d_ids, int64_t n_tokens, c
 // Host entry points: `total` ids already on the device (with their offsets) on `s` -> the handle's buffers -> the caller's.
 int labels_to_host(td_tokenizer* t, const void* d_ids, int64_t total, const void* d_toff, int64_t n_docs, const LabSpec& sp, int32_t* labels,
                    uint8_t* mask, int64_t* trained_offsets, int64_t* counts, hipStream_t s) {
+    return labels_outputs_to_host(t, total, n_docs, labels, mask, trained_offsets, counts, s, [&](void* d_lab, void* d_mask, void* d_to, void* d_cnt) {
+        return labels_launch_locked(t, d_ids, total, d_toff, n_docs, sp, d_lab, d_mask, d_to, d_cnt, s);
+    });
+}
+
+}  // namespace
+
+// The host end of a labelling call (td_span_labels*, td_range_labels*): the handle's output buffers, launch(d_labels, d_mask,
+// d_trained_offsets, d_counts) on `s`, the status, then what was asked for to the caller.
+int td::labels_outputs_to_host(td_tokenizer* t, int64_t total, int64_t n_docs, int32_t* labels, uint8_t* mask, int64_t* trained_offsets,
+                               int64_t* counts, hipStream_t s, const std::function<int(void*, void*, void*, void*)>& launch) {
     int rc;
     const size_t n1 = (size_t)std::max<int64_t>(total, 1);
     if ((rc = ensure(t, t->lab_out, n1 * 4))) return rc;
     if (mask && (rc = ensure(t, t->lab_mask, n1))) return rc;
     if (trained_offsets && (rc = ensure(t, t->lab_toff, (size_t)(n_docs + 1) * 8))) return rc;
     if ((rc = ensure(t, t->lab_counts, 4 * sizeof(int64_t)))) return rc;
-    if ((rc = labels_launch_locked(t, d_ids, total, d_toff, n_docs, sp, t->lab_out.p, mask ? t->lab_mask.p : nullptr,
-                                   trained_offsets ? t->lab_toff.p : nullptr, t->lab_counts.p, s)))
-        return rc;
+    if ((rc = launch(t->lab_out.p, mask ? t->lab_mask.p : nullptr, trained_offsets ? t->lab_toff.p : nullptr, t->lab_counts.p))) return rc;
     if ((rc = device_status_locked(t, s, nullptr))) return rc;
     if ((rc = copy_wait(t, counts, t->lab_counts.p, 4 * sizeof(int64_t), hipMemcpyDeviceToHost, s))) return rc;
     if (trained_offsets && (rc = copy_wait(t, trained_offsets, t->lab_toff.p, (size_t)(n_docs + 1) * 8, hipMemcpyDeviceToHost, s))) return rc;
@@ -95,8 +104,6 @@ int labels_to_host(td_tokenizer* t, const void* d_ids, int64_t total, const void
     if (mask && (rc = copy_wait(t, mask, t->lab_mask.p, (size_t)total, hipMemcpyDeviceToHost, s))) return rc;
     return copy_wait(t, labels, t->lab_out.p, (size_t)total * 4, hipMemcpyDeviceToHost, s);
 }
-
-}  // namespace
 
 extern "C" {
 

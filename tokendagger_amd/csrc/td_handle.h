@@ -9,6 +9,7 @@
 #include <chrono>
 #include <condition_variable>
 #include <deque>
+#include <functional>
 #include <memory>
 #include <mutex>
 #include <string>
@@ -252,6 +253,10 @@ struct td_tokenizer {
     // loss labels (td_labels.hip): the counts and flags, the document-start bitmap, the tiles' events / states, their trained ids
     // and the lanes' (trained_offsets only); the host entry points' outputs on the device
     DevBuf lab_head, lab_bits, lab_tiles, lab_cnt, lab_aux, lab_out, lab_mask, lab_toff, lab_counts;
+    // loss labels from byte ranges (td_ranges.hip; the rest of its scratch is the labels'): the first-range bitmap, the ranges' marked
+    // bytes in front of them inside their chunk and the chunks', the carries into the tiles; the host entry points' range offsets,
+    // ranges, starts and text offsets on the device
+    DevBuf rng_bits, rng_cum, rng_chunks, rng_sums, rng_off, rng_ranges, rng_starts, rng_docs;
     // best-fit packing (td_pack.hip): the items, the sort's and the scan's scratch, the header + runs read back, the plan uploaded,
     // the segments; the host entry points' row lengths and segment documents on the device
     DevBuf pack_key, pack_val, pack_key2, pack_val2, pack_full, pack_pref, pack_tmp, pack_hdr, pack_plan, pack_seg, pack_len, pack_docs;
@@ -372,6 +377,9 @@ int label_rows_check(td_tokenizer* t, const char* fn, const td_rows_spec* sp, in
 int label_rows_to_host(td_tokenizer* t, const void* d_ids, const void* d_src, const void* d_toff, const int64_t* h_toff, int64_t n_docs,
                        const td_rows_spec* sp, int64_t overlap, const td_rows_labels* lab, const td_label_rows_outputs& o,
                        int64_t rows_capacity, int64_t* counts, hipStream_t s);
+// ---- defined in td_api_labels.cpp ---------------------------------------------------------------------------------------------------
+int labels_outputs_to_host(td_tokenizer* t, int64_t total, int64_t n_docs, int32_t* labels, uint8_t* mask, int64_t* trained_offsets,
+                           int64_t* counts, hipStream_t s, const std::function<int(void*, void*, void*, void*)>& launch);
 int encode_starts_locked(td_tokenizer* t, const void* d_text, int64_t n, const void* d_offs, int64_t n_docs, const void* d_tokens, int64_t cap,
                          const void* d_out_offs, int unit, void* d_starts, hipStream_t stream);
 

@@ -356,9 +356,16 @@ hipError_t launch_labels(const LabelArgs& a, hipStream_t stream) {
     if ((e = hipGetLastError()) != hipSuccess) return e;
     hipLaunchKernelGGL(td_lab_apply, dim3(g_tiles), dim3(LAB_THREADS), 0, stream, a);
     if ((e = hipGetLastError()) != hipSuccess) return e;
+    return launch_labels_finish(a, stream);
+}
+
+hipError_t launch_labels_finish(const LabelArgs& a, hipStream_t stream) {
+    const int64_t g = (a.n_docs + 1 + LAB_THREADS - 1) / LAB_THREADS;
+    const unsigned g_docs = (unsigned)(g < 4096 ? g : 4096);
     if (a.trained_off) {
         hipLaunchKernelGGL(td_lab_count_carry, dim3(1), dim3(LAB_CARRY_THREADS), 0, stream, a);
-        if ((e = hipGetLastError()) != hipSuccess) return e;
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
     }
     hipLaunchKernelGGL(td_lab_finish, dim3(a.trained_off ? g_docs : 1u), dim3(LAB_THREADS), 0, stream, a);
     return hipGetLastError();

@@ -37,5 +37,9 @@ int64_t labels_tiles(int64_t n_tokens);         // tiles of a call (at least one
 int64_t labels_tiles_rounded(int64_t n_tokens);  // entries of LabelArgs::tiles / tile_cnt
 // td_lab_docs, td_lab_tiles, td_lab_carry, td_lab_apply, [td_lab_count_carry,] td_lab_finish
 hipError_t launch_labels(const LabelArgs& a, hipStream_t stream);
+// Its last two alone, for another labelling pass (td_ranges.hip) that left td_lab_apply's results: head (LAB_H_TRAINED, LAB_H_SPANS,
+// LAB_H_UNTERM as counts[0 .. 2]; LAB_H_BAD: nothing is written), and with trained_off tile_cnt and aux.  Reads tok_off, n_docs,
+// counts, trained_off and those.
+hipError_t launch_labels_finish(const LabelArgs& a, hipStream_t stream);
 
 }  // namespace td

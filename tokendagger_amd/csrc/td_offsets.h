@@ -50,6 +50,9 @@ struct StartsArgs {
 
 // td_token_starts: the covered rule on ids alone (heads, chunk scan, chunk carries, starts)
 hipError_t launch_token_starts(const StartsArgs& a, hipStream_t stream);
+// its middle alone, on a.heads already filled: the chunk totals, then in their place the carry into every chunk (a.chunk_sum[c] =
+// the bytes of chunk c's first document in front of the chunk; ids that are no tokens raise TD_E_BAD_TOKEN).  a.out is not touched.
+hipError_t launch_chunk_carries(const StartsArgs& a, hipStream_t stream);
 // behind launch_token_starts inside an encode: every document checked against its byte length; for generic patterns the
 // documents with skipped text mapped to source positions; OFF_PAIR unpacked
 hipError_t launch_encode_starts(const StartsArgs& a, hipStream_t stream);

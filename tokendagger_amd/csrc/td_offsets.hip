@@ -4,53 +4,30 @@
 // fewer bytes than it has is mapped back through a bitmap of the covered bytes, built from the generic engine's piece-start
 // and skipped-stretch bitmaps of the same call, with a two-level (tile, word) rank / select structure.
 //
-//   launch_token_starts   td_off_heads (bit per document start), td_off_scan<0> (chunk totals), td_off_carry (one workgroup:
-//                         carries into the chunks), td_off_scan<1> (the starts)
+//   launch_token_starts   td_off_heads (bit per document start), launch_chunk_carries, td_off_scan<1> (the starts)
+//   launch_chunk_carries  td_off_scan<0> (chunk totals), td_off_carry (one workgroup: carries into the chunks); td_ranges.hip
+//                         launches it too, on a bitmap of its own, and redoes the scan inside a chunk in registers
 //   launch_encode_starts  td_off_docs (ids against document lengths), for generic patterns td_off_rank_words / td_off_rank_tiles /
 //                         td_off_cov_words / td_off_rank_tiles (covered bytes, characters), td_off_finish (gap documents, packed pairs)
 #include <hip/hip_runtime.h>
 
 #include "td_common.h"
 #include "td_offsets.h"
+#include "td_offsets_dev.h"  // Seg, seg_op, wave_scan, off_bad_token, tok_len
 
 namespace td {
 
 namespace {
 
-struct Seg {  // a run of the segmented scan: f = a document starts inside it, s = sum since its last document start
-    uint32_t f;
-    unsigned long long s;
-};
-__device__ __forceinline__ Seg seg_op(Seg x, Seg y) { return Seg{x.f | y.f, y.f ? y.s : x.s + y.s}; }
-
 __device__ __forceinline__ void off_raise(const StartsArgs& a, int code, int64_t pos) {
     if (atomicCAS(a.err, 0, code) == 0) *a.err_pos = pos;
-}
-__device__ __forceinline__ void off_bad_token(const StartsArgs& a, int64_t i) {  // the lowest index wins (as td_decode_len)
-    const int was = atomicCAS(a.err, 0, TD_E_BAD_TOKEN);
-    if (was == 0 || was == TD_E_BAD_TOKEN)
-        atomicMax(reinterpret_cast<unsigned long long*>(a.err_pos), (unsigned long long)(0x7FFFFFFFFFFFFFFFll - i));
 }
 __device__ __forceinline__ int64_t off_total(const StartsArgs& a) {
     const int64_t t = a.tok_off[a.n_docs];
     return t < 0 ? 0 : (t < a.n_bound ? t : a.n_bound);
 }
-__device__ __forceinline__ uint32_t tok_len(const StartsArgs& a, int32_t id) {
-    return (id >= 0 && id <= a.max_id) ? a.len_off[id + 1] - a.len_off[id] : 0u;
-}
 __device__ __forceinline__ uint32_t tok_chars(const StartsArgs& a, int32_t id) {
     return (id >= 0 && id <= a.max_id) ? a.ctab[id] : 0u;
-}
-
-// 64-lane inclusive segmented scan
-__device__ __forceinline__ Seg wave_scan(Seg x, int lane) {
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t f = __shfl_up(x.f, d);
-        const unsigned long long s = __shfl_up(x.s, d);
-        if (lane >= d) x = seg_op(Seg{f, s}, x);
-    }
-    return x;
 }
 
 // A chunk of OFF_CHUNK ids, four a lane: the segmented scan inside the chunk.  Pass 0 writes the chunk's total, pass 1 the
@@ -427,15 +404,21 @@ void off_rank_layout(StartsArgs& a, void* base, int64_t n) {
     a.nc_wpref = (uint16_t*)p;
 }
 
+hipError_t launch_chunk_carries(const StartsArgs& a, hipStream_t stream) {
+    if (a.n_bound <= 0) return hipSuccess;
+    hipLaunchKernelGGL(td_off_scan<0>, dim3(off_blocks(a.n_bound, OFF_CHUNK, 2048)), dim3(1024), 0, stream, a);
+    hipLaunchKernelGGL(td_off_carry, dim3(1), dim3(1024), 0, stream, a);
+    return hipGetLastError();
+}
+
 hipError_t launch_token_starts(const StartsArgs& a, hipStream_t stream) {
     const hipError_t me = hipMemsetAsync(a.heads, 0, (size_t)(a.n_bound / 32 + 2) * 4, stream);
     if (me != hipSuccess) return me;
     hipLaunchKernelGGL(td_off_heads, dim3(off_blocks(a.n_docs, 256, 4096)), dim3(256), 0, stream, a);
     if (a.n_bound <= 0) return hipGetLastError();
-    const int cb = off_blocks(a.n_bound, OFF_CHUNK, 2048);
-    hipLaunchKernelGGL(td_off_scan<0>, dim3(cb), dim3(1024), 0, stream, a);
-    hipLaunchKernelGGL(td_off_carry, dim3(1), dim3(1024), 0, stream, a);
-    hipLaunchKernelGGL(td_off_scan<1>, dim3(cb), dim3(1024), 0, stream, a);
+    const hipError_t ce = launch_chunk_carries(a, stream);
+    if (ce != hipSuccess) return ce;
+    hipLaunchKernelGGL(td_off_scan<1>, dim3(off_blocks(a.n_bound, OFF_CHUNK, 2048)), dim3(1024), 0, stream, a);
     return hipGetLastError();
 }
 

@@ -65,7 +65,8 @@ class LabeledRows(NamedTuple):
 
 class Labels(NamedTuple):
     """Loss labels for marked id spans (Tokenizer.ids_to_labels / encode_batch_to_labels; the contract:
-    include/tokendagger_hip.h, td_labels_spec)."""
+    include/tokendagger_hip.h, td_labels_spec) or for byte ranges (ids_to_range_labels / encode_batch_to_range_labels;
+    td_range_spec: counts = trained ids, partially marked ids, marked bytes, 0)."""
     ids: np.ndarray                     # int32 [total]
     tok_offsets: np.ndarray             # int64 [n_docs + 1]
     labels: np.ndarray                  # int32 [total]: the id where the loss applies, ignore_index elsewhere
@@ -503,6 +504,49 @@ class Tokenizer:
         except _capi.TokenDaggerHipError as ex:
             raise TokenDaggerError(f"Encoding failed: {ex}")
 
+    # ------------------------------------------------------------------ loss labels from byte ranges ---
+    # For data whose trained regions are known as offsets into the text (plain-text templates, prompt / completion pairs, field
+    # values): per document a sorted list of disjoint half-open byte ranges, relative to the document's first byte.  `ranges` is
+    # (range_offsets, array[n, 2]) or one sequence of (begin, end) per document.  rule: "overlap" trains an id with any marked byte,
+    # "inside" one whose bytes are all marked, "start" one whose first byte is marked.  counts[1] is the number of ids that straddle
+    # an edge of a range.  unit="chars" (the text forms only): the ranges count code points; they are converted to bytes on the
+    # host, one numpy pass over the text, before the call.
+    def _range_args(self, rule, ignore_index: int):
+        return _capi.HipTokenizer.borrow(self._core_bpe.handle()), _capi.range_spec(rule, ignore_index)
+
+    @staticmethod
+    def _text_ranges(buf, offs, ranges, unit: str):
+        if unit not in ("bytes", "chars"):
+            raise ValueError("unit must be 'bytes' or 'chars'")
+        return _capi.chars_to_bytes(buf, offs, ranges) if unit == "chars" else _capi.as_ranges(ranges, len(offs) - 1)
+
+    def ids_to_range_labels(self, ids: np.ndarray, tok_offsets: np.ndarray, ranges, *, rule: str = "overlap", ignore_index: int = -100,
+                            mask: bool = False, trained_offsets: bool = False, starts=None) -> Labels:
+        """Loss labels from ids already encoded and byte ranges.  starts None: every document's bytes are its ids' bytes
+        concatenated; else int64 byte starts per id (encode_batch_to_numpy_with_offsets), for patterns that skip text."""
+        hip, spec = self._range_args(rule, ignore_index)
+        ids = np.ascontiguousarray(ids, dtype=np.int32)
+        offs = np.ascontiguousarray(tok_offsets, dtype=np.int64)
+        try:
+            lab, m, to, counts = hip.range_labels(ids, offs, ranges, spec, mask=mask, trained_offsets=trained_offsets, starts=starts)
+        except _capi.TokenDaggerHipError as ex:
+            raise TokenDaggerError(f"Making labels failed: {ex}")
+        return Labels(ids[:len(lab)], offs, lab, m, to, counts)
+
+    def encode_batch_to_range_labels(self, text: np.ndarray | bytes, offsets: np.ndarray, ranges, *, rule: str = "overlap", unit: str = "bytes",
+                                     allowed_special: Literal["all"] | AbstractSet[str] = "all", ignore_index: int = -100, mask: bool = False,
+                                     trained_offsets: bool = False) -> Labels:
+        """Text and ranges into it straight to ids + labels (one call): the ids are labelled on the device where the encode leaves them."""
+        hip, spec = self._range_args(rule, ignore_index)
+        allowed = sorted(self._special_tokens) if allowed_special == "all" else sorted(allowed_special)
+        buf = np.frombuffer(text, dtype=np.uint8) if isinstance(text, (bytes, bytearray)) else text
+        offs = np.asarray(offsets, dtype=np.int64)
+        rg = self._text_ranges(buf, offs, ranges, unit)
+        try:
+            return Labels(*hip.encode_batch_range_labels(buf, offs, allowed, rg, spec, mask=mask, trained_offsets=trained_offsets))
+        except _capi.TokenDaggerHipError as ex:
+            raise TokenDaggerError(f"Encoding failed: {ex}")
+
     # ------------------------------------------------------------------ label rows -------------
     # (input_ids, labels) rows in one pass: `labels` is a stream index-aligned with the ids (ids_to_labels gives one) and is placed by
     # the placement of the ids.  Where the id rows hold the inserted BOS / EOS / a pad slot the label rows hold label_bos /
@@ -567,6 +611,33 @@ class Tokenizer:
             r = hip.encode_batch_span_label_rows(buf, np.asarray(offsets, dtype=np.int64), allowed, lspec, rspec, lab, overlap=int(overlap),
                                                  positions=positions, aux=cu_seqlens or lay == 1, lengths=True, docs=docs or lay == 3,
                                                  starts=True)
+        except _capi.TokenDaggerHipError as ex:
+            err = TokenDaggerError(f"Encoding failed: {ex}")
+            err.counts = getattr(ex, "counts", None)
+            raise err
+        return self._labeled(lay, seq_len, no_pad, r[:-1])
+
+    def encode_batch_to_range_labeled_rows(self, text: np.ndarray | bytes, offsets: np.ndarray, ranges, seq_len: int, *, layout: str = "concat",
+                                           rule: str = "overlap", unit: str = "bytes",
+                                           allowed_special: Literal["all"] | AbstractSet[str] = "all", ignore_index: int = -100, bos=None,
+                                           eos=None, pad=None, label_bos=None, label_eos=None, label_pad=None, overlap: int = 0,
+                                           mask_overlap: bool = False, drop_last: bool = False, truncate: bool = False,
+                                           positions: bool = False, cu_seqlens: bool = True, docs: bool = False) -> LabeledRows:
+        """encode_batch_to_labeled_rows with byte ranges in place of id spans: encode_batch_to_range_labels then ids_to_labeled_rows,
+        with the ids and the labels staying on the device in between."""
+        hip, rgspec = self._range_args(rule, ignore_index)
+        lay, b, e, p, no_pad, flags, lb, le, lp, lflags = self._labeled_args(
+            seq_len, layout, bos, eos, pad, ignore_index if label_bos is None else label_bos, label_eos,
+            ignore_index if label_pad is None else label_pad, overlap, mask_overlap, drop_last, truncate)
+        allowed = sorted(self._special_tokens) if allowed_special == "all" else sorted(allowed_special)
+        buf = np.frombuffer(text, dtype=np.uint8) if isinstance(text, (bytes, bytearray)) else text
+        offs = np.asarray(offsets, dtype=np.int64)
+        rg = self._text_ranges(buf, offs, ranges, unit)
+        rspec = _capi.RowsSpec(lay, seq_len, b, e, p, flags)
+        lab = _capi.rows_labels(0, 0, lb, le, lp, flags=lflags)
+        try:
+            r = hip.encode_batch_range_label_rows(buf, offs, allowed, rg, rgspec, rspec, lab, overlap=int(overlap), positions=positions,
+                                                  aux=cu_seqlens or lay == 1, lengths=True, docs=docs or lay == 3, starts=True)
         except _capi.TokenDaggerHipError as ex:
             err = TokenDaggerError(f"Encoding failed: {ex}")
             err.counts = getattr(ex, "counts", None)
