@@ -653,6 +653,59 @@ int td_encode_batch_range_label_rows(td_tokenizer* t, const uint8_t* text, const
                                      const td_label_rows_outputs* host_out, int64_t rows_capacity, int64_t* row_counts,
                                      int64_t* label_counts);
 
+/* ---- token counts: histograms of ids per document group (td_counts.hip) ----------------------------------------------------------
+ * What is in the ids a call made: counts[g * n_bins + v] = the visited positions of group g whose value is v, without copying the
+ * ids to the host.  ids[n_tokens] (int32) is any stream aligned with ids: passing the labels of td_span_labels / td_range_labels
+ * gives the histogram of the TRAINED tokens, their negative ignore_index falls out by the rule below.
+ *   n_groups == 1: positions [0, n_tokens) are visited; tok_offsets, n_docs and doc_group are ignored and may be NULL / 0.
+ *   n_groups > 1:  tok_offsets[n_docs + 1] (int64) and doc_group[n_docs] (int32) are required; positions [tok_offsets[0],
+ *                  tok_offsets[n_docs]) are visited, position i belongs to the document d with tok_offsets[d] <= i < tok_offsets[d + 1]
+ *                  and to group doc_group[d] (a source, a language, a split).
+ *   counts[n_groups * n_bins] (int64, row-major by group).  Without TD_COUNTS_ACCUMULATE it is zeroed first; with it the call adds to
+ *                  what is there (several calls, several shards).
+ *   info[4] (int64), always overwritten: every visited position falls into exactly one of, in this order of precedence,
+ *     info[3] bad_group  its document's group is outside [0, n_groups)
+ *     info[1] negative   v < 0
+ *     info[2] too_large  v >= n_bins
+ *     info[0] counted    added to counts
+ *   so the four add up to the visited positions.  A value is never an error and never moves a write outside counts.  Integer sums
+ *   are exact in any order: results are bitwise reproducible.
+ *   Errors:
+ *     a bad spec (n_bins < 1, n_groups < 1, n_groups * n_bins > 2^28, flags other than TD_COUNTS_ACCUMULATE, n_groups > 1 with a
+ *       NULL tok_offsets or doc_group): TD_E_INVALID before any launch;
+ *     host forms: tok_offsets (where n_groups > 1) are checked like the row calls' offsets, and a doc_group[d] outside
+ *       [0, n_groups) is TD_E_INVALID naming d; both before any launch, counts untouched;
+ *     device form: a document WITH visited positions whose group is bad raises TD_E_INVALID with err_pos = d through
+ *       td_device_status, and info[3] tells how many positions such documents held; the other documents are counted.  Offsets that
+ *       decrease, begin below 0 or end above n_tokens raise TD_E_INVALID where the kernel meets them; counts is then unspecified,
+ *       but nothing outside ids[0, n_tokens) is read and nothing outside counts / info is written. */
+#define TD_COUNTS_ACCUMULATE 1
+typedef struct td_counts_spec {
+    int64_t n_bins;   /* >= 1: values v with 0 <= v < n_bins are counted */
+    int64_t n_groups; /* >= 1; n_groups * n_bins <= 2^28 */
+    int64_t flags;    /* 0 or TD_COUNTS_ACCUMULATE */
+} td_counts_spec;
+
+/* The contract's executable statement, on the host (no handle, no device).  tok_offsets (n_groups > 1) must be non-negative and
+ * non-decreasing and end at or below n_tokens; tok_offsets[0] may be above 0.  Argument errors (a NULL spec / counts / info, a bad
+ * spec, negative sizes, bad offsets, NULL ids with positions to visit) are TD_E_INVALID with info[0] = -1; a doc_group[d] outside
+ * [0, n_groups) is TD_E_INVALID with info[0] = d, the lowest.  counts is untouched then. */
+int td_token_counts_host(const int32_t* ids, int64_t n_tokens, const int64_t* tok_offsets, int64_t n_docs, const int32_t* doc_group,
+                         const td_counts_spec* spec, int64_t* counts, int64_t* info);
+/* DEVICE buffers, asynchronously on hip_stream: no synchronisation and no read-back; the zeroing of d_counts, when asked for, is
+ * enqueued on the same stream.  d_counts (n_groups * n_bins int64) and d_info (4 int64) are device memory, 8-byte aligned. */
+int td_token_counts_device(td_tokenizer* t, const void* d_ids, int64_t n_tokens, const void* d_tok_offsets, int64_t n_docs,
+                           const void* d_doc_group, const td_counts_spec* spec, void* d_counts, void* d_info, void* hip_stream);
+/* Host buffers, synchronously.  With TD_COUNTS_ACCUMULATE the device's result is added to the caller's array on the host. */
+int td_token_counts(td_tokenizer* t, const int32_t* ids, int64_t n_tokens, const int64_t* tok_offsets, int64_t n_docs,
+                    const int32_t* doc_group, const td_counts_spec* spec, int64_t* counts, int64_t* info);
+/* td_encode_batch (TD_MODE_ENCODE / TD_MODE_ORDINARY, no allowed special tokens) and the counts in one call, "statistics at encode
+ * speed": the ids never leave the device, only counts, info and *n_tokens_out (the ids made; may be NULL) come back.  doc_group
+ * (n_groups > 1) indexes the documents of doc_offsets.  Synchronous. */
+int td_encode_batch_token_counts(td_tokenizer* t, const uint8_t* text, const int64_t* doc_offsets, int64_t n_docs, int mode,
+                                 const int32_t* doc_group, const td_counts_spec* spec, int64_t* counts, int64_t* info,
+                                 int64_t* n_tokens_out);
+
 /* Options. */
 #define TD_OPT_LONG_POOL_BYTES 1 /* scratch for pieces longer than 64 bytes (default max(64 MiB, 2 x input)) */
 #define TD_OPT_PROFILE 2         /* 1: bracket the kernels of every td_encode_device call with HIP events on the
@@ -702,6 +755,11 @@ int td_encode_batch_range_label_rows(td_tokenizer* t, const uint8_t* text, const
                                     results either way — td_tail walks every phase the dense sequence has kernels for; TD_SPARSE in the
                                     environment at td_create time sets it too. */
 #define TD_OPT_PIPE_THREADS 4     /* host threads that fill / drain the pinned bounce buffers of that pipeline (default 16) */
+#define TD_OPT_COUNTS_SEATS 15     /* seats of the on-chip table of td_token_counts*: a power of two from 2 to the production size
+                                    (4096), or 0 (default) for that.  Same results whatever it is; tests force the conflict path with 2. */
+#define TD_OPT_COUNTS_FLUSH_TILES 16 /* tiles (4096 ids) a workgroup of td_token_counts* counts between two flushes of that table: 1 to the
+                                    production interval (64), or 0 (default) for that.  Same results whatever it is; tests shrink it, a call
+                                    needs more than 268 M ids to reach the production interval. */
 int td_set_option(td_tokenizer* t, int what, int64_t value);
 
 /* Sums (ms) of the pre-tokenizer kernel and token kernel (probe + merge) durations and the number of calls recorded

@@ -40,6 +40,9 @@ TD_OPT_DEDUPE = 11
 TD_OPT_OVERLAP = 12
 TD_OPT_GIANT_COOP_MIN = 13
 TD_OPT_SPARSE = 14
+TD_OPT_COUNTS_SEATS = 15
+TD_OPT_COUNTS_FLUSH_TILES = 16
+TD_COUNTS_ACCUMULATE = 1
 TD_INFO_DEFERRED_TILES, TD_INFO_FLAGGED_TILES = 9, 10
 TD_INFO_DIRECT_TILES = 11
 TD_INFO_LB_TIMEOUTS = 12
@@ -64,6 +67,7 @@ EXPORTS = [
     "td_window_rows_labeled", "td_window_rows_labeled_device", "td_encode_batch_span_label_rows",
     "td_select_plan", "td_select_docs", "td_select_docs_device", "td_encode_batch_select",
     "td_range_plan", "td_range_labels", "td_range_labels_device", "td_encode_batch_range_labels", "td_encode_batch_range_label_rows",
+    "td_token_counts_host", "td_token_counts", "td_token_counts_device", "td_encode_batch_token_counts",
 ]
 
 
@@ -173,6 +177,14 @@ def load_library():
     lib.td_encode_batch_range_labels.argtypes = [vp, vp, vp, i64, vp, vp, i64, vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, ctypes.POINTER(i64)]
     lib.td_encode_batch_range_label_rows.restype = i32
     lib.td_encode_batch_range_label_rows.argtypes = [vp, vp, vp, i64, vp, vp, i64, vp, vp, vp, vp, i64, vp, vp, i64, vp, vp]
+    lib.td_token_counts_host.restype = i32
+    lib.td_token_counts_host.argtypes = [vp, i64, vp, i64, vp, vp, vp, vp]
+    lib.td_token_counts_device.restype = i32
+    lib.td_token_counts_device.argtypes = [vp, vp, i64, vp, i64, vp, vp, vp, vp, vp]
+    lib.td_token_counts.restype = i32
+    lib.td_token_counts.argtypes = [vp, vp, i64, vp, i64, vp, vp, vp, vp]
+    lib.td_encode_batch_token_counts.restype = i32
+    lib.td_encode_batch_token_counts.argtypes = [vp, vp, vp, i64, i32, vp, vp, vp, vp, ctypes.POINTER(i64)]
     lib.td_comm_unique_id.restype = i32
     lib.td_comm_unique_id.argtypes = [vp]
     lib.td_comm_create.restype = i32
@@ -409,6 +421,58 @@ def select_plan(tok_offsets, sel=None, spec: SelectSpec | None = None, outputs: 
         raise ex
     k = int(counts[0])
     return (counts, offs[:k + 1], docs[:k]) if outputs else counts
+
+
+class CountsSpec(ctypes.Structure):
+    """td_counts_spec (include/tokendagger_hip.h)."""
+    _fields_ = [("n_bins", ctypes.c_int64), ("n_groups", ctypes.c_int64), ("flags", ctypes.c_int64)]
+
+
+def counts_spec(n_bins: int, n_groups: int = 1, accumulate: bool = False, flags: int = 0) -> CountsSpec:
+    """Values 0 .. n_bins - 1 are counted, per group 0 .. n_groups - 1; accumulate: add to the counts that are there."""
+    return CountsSpec(n_bins, n_groups, flags | (TD_COUNTS_ACCUMULATE if accumulate else 0))
+
+
+def _counts_args(ids, tok_offsets, groups, spec: CountsSpec, counts):
+    """The arrays of a host counts call: ids, offsets | None, groups | None, n_docs, counts (int64[n_groups * n_bins]: the caller's
+    with TD_COUNTS_ACCUMULATE, else a new one), info."""
+    t = np.ascontiguousarray(ids, dtype=np.int32)
+    o = None if tok_offsets is None else np.ascontiguousarray(tok_offsets, dtype=np.int64)
+    g = None if groups is None else np.ascontiguousarray(groups, dtype=np.int32)
+    n_docs = 0 if o is None else len(o) - 1
+    if g is not None and len(g) != n_docs:
+        raise ValueError("groups must have one entry per document")
+    size = max(int(spec.n_bins) * int(spec.n_groups), 0)
+    if spec.flags & TD_COUNTS_ACCUMULATE:
+        if counts is None or counts.dtype != np.int64 or not counts.flags.c_contiguous or counts.size != size:
+            raise ValueError("TD_COUNTS_ACCUMULATE needs counts: a contiguous int64 array of n_groups * n_bins entries")
+    else:
+        counts = np.empty(min(size, 1 << 28) or 1, dtype=np.int64)
+    if g is not None and g.size == 0:
+        g = np.zeros(1, dtype=np.int32)[:0]  # (an empty list's address is not NULL)
+    return t, o, g, n_docs, counts, np.zeros(4, dtype=np.int64)
+
+
+def _counts_shape(counts, spec: CountsSpec):
+    return counts.reshape(int(spec.n_groups), int(spec.n_bins))
+
+
+def token_counts_host(ids, tok_offsets=None, groups=None, spec: CountsSpec | None = None, counts=None, n_tokens: int | None = None):
+    """td_token_counts_host (host only, no device) -> (counts int64[n_groups, n_bins], info int64[4] = counted, negative, too_large,
+    0).  An error carries .info ([0]: the document of a bad group, -1 for an argument error)."""
+    lib = load_library()
+    if spec is None:
+        raise ValueError("a counts_spec is required")
+    t, o, g, n_docs, counts, info = _counts_args(ids, tok_offsets, groups, spec, counts)
+    rc = lib.td_token_counts_host(t.ctypes.data if len(t) else None, len(t) if n_tokens is None else n_tokens,
+                                  o.ctypes.data if o is not None else None, n_docs, g.ctypes.data if g is not None else None,
+                                  ctypes.byref(spec), counts.ctypes.data, info.ctypes.data)
+    if rc != TD_OK:
+        ex = TokenDaggerHipError(rc, "td_token_counts_host: invalid spec, offsets or arguments" if info[0] < 0 else
+                                 f"td_token_counts_host: doc_group[{int(info[0])}] is outside [0, n_groups)")
+        ex.info = info
+        raise ex
+    return _counts_shape(counts, spec), info
 
 
 class LabelsSpec(ctypes.Structure):
@@ -1208,6 +1272,38 @@ class HipTokenizer:
         self._check_counts(rc, counts)
         k, n = int(counts[0]), int(counts[1])
         return out[:n], o_out[:k + 1], (dcs[:k] if docs else None), counts
+
+    # ---- token counts (td_counts_spec) ------------------------------------------------------------------------
+    def token_counts(self, ids, tok_offsets=None, groups=None, spec: CountsSpec | None = None, counts=None, n_tokens: int | None = None):
+        """td_token_counts -> (counts int64[n_groups, n_bins], info int64[4] = counted, negative, too_large, bad_group).  With
+        TD_COUNTS_ACCUMULATE in the spec, `counts` is the array that is added to (and returned, reshaped)."""
+        if spec is None:
+            raise ValueError("a counts_spec is required")
+        t, o, g, n_docs, counts, info = _counts_args(ids, tok_offsets, groups, spec, counts)
+        self._check(self._lib.td_token_counts(self._h, t.ctypes.data if len(t) else None, len(t) if n_tokens is None else n_tokens,
+                                              o.ctypes.data if o is not None else None, n_docs, g.ctypes.data if g is not None else None,
+                                              ctypes.byref(spec), counts.ctypes.data, info.ctypes.data))
+        return _counts_shape(counts, spec), info
+
+    def token_counts_device(self, d_ids: int, n_tokens: int, d_tok_offsets: int, n_docs: int, d_doc_group: int, spec: CountsSpec, d_counts: int,
+                            d_info: int, stream: int = 0):
+        """td_token_counts_device: raw device pointers (d_tok_offsets, d_doc_group 0 with one group), asynchronous on `stream`; check
+        with device_status(stream)."""
+        self._check(self._lib.td_token_counts_device(self._h, d_ids or None, n_tokens, d_tok_offsets or None, n_docs, d_doc_group or None,
+                                                     ctypes.byref(spec), d_counts or None, d_info or None, stream or None))
+
+    def encode_batch_token_counts(self, text, doc_offsets, groups=None, spec: CountsSpec | None = None, mode: int = TD_MODE_ENCODE, counts=None):
+        """td_encode_batch_token_counts: encode + token counts in one call, the ids stay on the device -> (counts, info, n_tokens)."""
+        if spec is None:
+            raise ValueError("a counts_spec is required")
+        buf = _as_u8(text)
+        offs = np.ascontiguousarray(doc_offsets, dtype=np.int64)
+        _, _, g, n_docs, counts, info = _counts_args(np.zeros(0, dtype=np.int32), offs, groups, spec, counts)
+        total = ctypes.c_int64(0)
+        self._check(self._lib.td_encode_batch_token_counts(self._h, buf.ctypes.data if len(buf) else None, offs.ctypes.data, n_docs, mode,
+                                                           g.ctypes.data if g is not None else None, ctypes.byref(spec), counts.ctypes.data,
+                                                           info.ctypes.data, ctypes.byref(total)))
+        return _counts_shape(counts, spec), info, int(total.value)
 
     def device_status_pos(self, stream: int = 0) -> tuple[int, int]:
         """td_device_status without raising: (code, err_pos)."""

@@ -1,6 +1,7 @@
 // C-ABI host library (include/tokendagger_hip.h) over the gfx950 kernels.
 // Host code is C++; it owns the device tables, the per-call workspace and stream-ordered launches.
 // There is deliberately NO CPU tokenization path in this file: if HIP is unusable, td_create fails.
+#include "td_counts_args.h"
 #include "td_handle.h"
 #include "td_regex.h"
 
@@ -1133,6 +1134,15 @@ int td_set_option(td_tokenizer* t, int what, int64_t value) {
         case TD_OPT_PIPE_CHUNK_BYTES: if (value < 4096) break; o.pipe_chunk_bytes = value; return TD_OK;
         case TD_OPT_SMALL_PATH: o.small_enabled = value != 0; return TD_OK;
         case TD_OPT_PIPE_THREADS: if (value < 1 || value > 256) break; o.pipe_threads = (int)value; return TD_OK;
+        case TD_OPT_COUNTS_FLUSH_TILES: if (value < 0 || value > CNT_FLUSH_TILES) break; o.counts_flush_tiles = (int)value; return TD_OK;
+        case TD_OPT_COUNTS_SEATS: {  // a power of two from 2 to the production size, or 0 for it
+            if (value == 0) { o.counts_seat_bits = 0; return TD_OK; }
+            if (value < 2 || value > CNT_SEATS || (value & (value - 1))) break;
+            int bits = 0;
+            while ((int64_t(1) << bits) < value) ++bits;
+            o.counts_seat_bits = bits;
+            return TD_OK;
+        }
     }
     return TD_E_INVALID;
 }

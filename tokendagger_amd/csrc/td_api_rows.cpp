@@ -289,9 +289,11 @@ int rows_stage_host_src(td_tokenizer* t, const td_rows_labels* lab, int64_t tota
     return TD_OK;
 }
 
+}  // namespace
+
 // td_encode_batch_rows, _pack_rows, _window_rows: the documents encoded on the handle's own stream `s` into d_tokens (room for
 // dev_cap ids) / d_offsets, and the encode's errors returned as such, before the rows read its ids.
-int rows_encode_locked(td_tokenizer* t, const uint8_t* text, const int64_t* doc_offsets, int64_t n_docs, int mode, int64_t& dev_cap,
+int td::rows_encode_locked(td_tokenizer* t, const uint8_t* text, const int64_t* doc_offsets, int64_t n_docs, int mode, int64_t& dev_cap,
                        hipStream_t& s) {
     int rc;
     if ((rc = check_offsets(t, "doc_offsets", doc_offsets, n_docs, text))) return rc;
@@ -313,6 +315,8 @@ int rows_encode_locked(td_tokenizer* t, const uint8_t* text, const int64_t* doc_
     }
     return device_status_locked(t, s, nullptr);
 }
+
+namespace {
 
 // ---- window rows (td_windows.hip) ---------------------------------------------------------------------------------------------
 // w_d = max(1, ceil((L - overlap) / step))

@@ -215,6 +215,8 @@ struct Options {
     int64_t pool_bytes_opt = 0;   // TD_OPT_LONG_POOL_BYTES
     int64_t pipe_chunk_bytes = 64ll << 20;  // TD_OPT_PIPE_CHUNK_BYTES (a GiB of English host to host: 16 MiB chunks 33 GB/s, 32 MiB 39, 64 MiB 40.5, profiles/r5_bench/e2e_sweep.txt)
     int pipe_threads = 16;        // TD_OPT_PIPE_THREADS
+    int counts_flush_tiles = 0;   // TD_OPT_COUNTS_FLUSH_TILES: tiles of a workgroup between two flushes of that table, 0 = CNT_FLUSH_TILES (tests shrink it)
+    int counts_seat_bits = 0;     // TD_OPT_COUNTS_SEATS: log2 of the seats of td_cnt_tiles' on-chip table, 0 = the production size (tests force conflicts with 2)
     static Options from_env();
 };
 
@@ -257,6 +259,8 @@ struct td_tokenizer {
     // bytes in front of them inside their chunk and the chunks', the carries into the tiles; the host entry points' range offsets,
     // ranges, starts and text offsets on the device
     DevBuf rng_bits, rng_cum, rng_chunks, rng_sums, rng_off, rng_ranges, rng_starts, rng_docs;
+    // token counts (td_counts.hip): the host entry points' counts, info and document groups on the device
+    DevBuf cnt_counts, cnt_info, cnt_groups;
     // best-fit packing (td_pack.hip): the items, the sort's and the scan's scratch, the header + runs read back, the plan uploaded,
     // the segments; the host entry points' row lengths and segment documents on the device
     DevBuf pack_key, pack_val, pack_key2, pack_val2, pack_full, pack_pref, pack_tmp, pack_hdr, pack_plan, pack_seg, pack_len, pack_docs;
@@ -377,6 +381,10 @@ int label_rows_check(td_tokenizer* t, const char* fn, const td_rows_spec* sp, in
 int label_rows_to_host(td_tokenizer* t, const void* d_ids, const void* d_src, const void* d_toff, const int64_t* h_toff, int64_t n_docs,
                        const td_rows_spec* sp, int64_t overlap, const td_rows_labels* lab, const td_label_rows_outputs& o,
                        int64_t rows_capacity, int64_t* counts, hipStream_t s);
+// td_encode_batch_rows, _pack_rows, _window_rows, _select, _token_counts: the documents encoded on the handle's own stream, which `s`
+// becomes, into d_tokens (room for dev_cap ids) / d_offsets; the encode's errors are returned as such before anything reads its ids.
+int rows_encode_locked(td_tokenizer* t, const uint8_t* text, const int64_t* doc_offsets, int64_t n_docs, int mode, int64_t& dev_cap,
+                       hipStream_t& s);
 // ---- defined in td_api_labels.cpp ---------------------------------------------------------------------------------------------------
 int labels_outputs_to_host(td_tokenizer* t, int64_t total, int64_t n_docs, int32_t* labels, uint8_t* mask, int64_t* trained_offsets,
                            int64_t* counts, hipStream_t s, const std::function<int(void*, void*, void*, void*)>& launch);

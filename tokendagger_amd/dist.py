@@ -43,3 +43,29 @@ def gather_counts(n_docs_local: int, n_tokens_local, device=None, group=None):
     t = table.view(world, 2).cpu().numpy()
     tok_base, doc_base, tok_total, doc_total = capi.comm_bases(t, rank)
     return doc_base, tok_base, doc_total, tok_total, t
+
+
+def sum_counts(counts, group=None, device=None):
+    """all-reduce SUM of a counts array (Tokenizer.ids_to_counts / encode_batch_to_counts, td_token_counts*) over the ranks: counts
+    are additive, so the histogram of a sharded corpus is the sum of its shards'.  `counts` is a numpy int64 array (-> a new array
+    of the same shape; it travels through `device`, default the CPU) or an int64 tensor (reduced in place where it lives and
+    returned).  RCCL with the "nccl" backend, gloo on the CPU, like gather_counts."""
+    import torch
+    import torch.distributed as dist
+    if torch.is_tensor(counts):
+        if counts.dtype != torch.int64:
+            raise TypeError("counts must be int64")
+        t = counts if device is None or counts.device == torch.device(device) else counts.to(device)
+        t = t.contiguous()
+        dist.all_reduce(t, op=dist.ReduceOp.SUM, group=group)
+        if t is not counts:
+            counts.copy_(t)
+        return counts
+    a = np.ascontiguousarray(counts)
+    if a.dtype != np.int64:
+        raise TypeError("counts must be int64")
+    t = torch.from_numpy(a.copy())
+    if device is not None:
+        t = t.to(device)
+    dist.all_reduce(t, op=dist.ReduceOp.SUM, group=group)
+    return t.cpu().numpy().reshape(a.shape)

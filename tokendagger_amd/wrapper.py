@@ -75,6 +75,23 @@ class Labels(NamedTuple):
     counts: np.ndarray                  # int64 [4]: trained ids, spans, unterminated documents, 0
 
 
+class TokenCounts(NamedTuple):
+    """Histograms of ids (Tokenizer.ids_to_counts; the contract: include/tokendagger_hip.h, td_counts_spec)."""
+    counts: np.ndarray  # int64 [n_groups, n_bins], or [n_bins] without groups
+    counted: int        # positions added to counts
+    negative: int       # positions with a negative value (the ignore_index of a label stream)
+    too_large: int      # positions with a value >= n_bins
+
+
+class EncodedTokenCounts(NamedTuple):
+    """Tokenizer.encode_batch_to_counts: TokenCounts and the ids the encode made."""
+    counts: np.ndarray
+    counted: int
+    negative: int
+    too_large: int
+    n_tokens: int
+
+
 class TokenDaggerError(Exception):
     """Base exception for TokenDagger errors (reference: wrapper.py:23-25)."""
 
@@ -455,6 +472,73 @@ class Tokenizer:
         except _capi.TokenDaggerHipError as ex:
             raise TokenDaggerError(f"Encoding failed: {ex}")
         return i, o, d
+
+    # ------------------------------------------------------------------ token counts -----------
+    # What is in the ids: counts[g, v] = how often id v occurs in the documents of group g (a source, a language, a split), on the
+    # device.  Any int32 stream aligned with ids counts as well: ids_to_counts(labels) is the histogram of the TRAINED tokens, the
+    # ignore_index shows in `negative`.  Counts add: out= accumulates over calls, dist.sum_counts over ranks.
+    def _counts_args(self, tok_offsets, groups, n_groups, n_bins, out, strict):
+        n_bins = self.n_vocab if n_bins is None else int(n_bins)
+        if groups is None:
+            if n_groups not in (None, 1):
+                raise TokenDaggerError("n_groups needs groups")
+            n_groups, g = 1, None
+        else:
+            if tok_offsets is None:
+                raise TokenDaggerError("groups needs tok_offsets")
+            g = np.ascontiguousarray(groups, dtype=np.int32)
+            n_groups = int(n_groups) if n_groups is not None else (int(g.max()) + 1 if g.size else 1)
+            # (one group is the contract's form without documents: the groups are checked here, the offsets bound nothing new)
+        if out is not None:
+            want = (n_bins,) if groups is None else (n_groups, n_bins)
+            if not isinstance(out, np.ndarray) or out.dtype != np.int64 or out.shape != want or not out.flags.c_contiguous:
+                raise TokenDaggerError(f"out must be a contiguous int64 array of shape {want}")
+        # (strict: the call counts into an array of its own, and `out` is added to only behind the check: a raise leaves it as it was)
+        direct = out is not None and not strict
+        spec = _capi.counts_spec(n_bins, n_groups, accumulate=direct)
+        return g, spec, (out.reshape(-1) if direct else None)
+
+    @staticmethod
+    def _counts_result(counts, info, grouped: bool, out, strict: bool):
+        if strict and int(info[2]) > 0:
+            raise TokenDaggerError(f"{int(info[2])} ids are at or above n_bins: these are not this vocabulary's ids (strict=False counts the rest)")
+        if out is not None and strict:
+            out += counts.reshape(out.shape)
+        c = out if out is not None else (counts if grouped else counts.reshape(-1))
+        return c, int(info[0]), int(info[1]), int(info[2])
+
+    def ids_to_counts(self, ids: np.ndarray, tok_offsets: np.ndarray | None = None, *, groups=None, n_groups: int | None = None,
+                      n_bins: int | None = None, out: np.ndarray | None = None, strict: bool = True) -> TokenCounts:
+        """Histogram of ids (n_bins: default n_vocab), per group of documents where groups[n_docs] is given (n_groups: default
+        max(groups) + 1).  out=: an int64 array of the result's shape that is added to.  strict: ids >= n_bins raise, and `out` is then left as it was."""
+        hip = _capi.HipTokenizer.borrow(self._core_bpe.handle())
+        g, spec, flat = self._counts_args(tok_offsets, groups, n_groups, n_bins, out, strict)
+        if g is not None and spec.n_groups == 1:
+            if g.size and (g.min() < 0 or g.max() > 0):
+                raise TokenDaggerError("Counting tokens failed: a group is outside [0, n_groups)")
+            o = np.asarray(tok_offsets, dtype=np.int64)
+            ids, tok_offsets, g = np.asarray(ids, dtype=np.int32)[int(o[0]):int(o[-1])], None, None
+        try:
+            counts, info = hip.token_counts(ids, tok_offsets if g is not None else None, g, spec, counts=flat)
+        except _capi.TokenDaggerHipError as ex:
+            raise TokenDaggerError(f"Counting tokens failed: {ex}")
+        return TokenCounts(*self._counts_result(counts, info, groups is not None, out, strict))
+
+    def encode_batch_to_counts(self, text: np.ndarray | bytes, offsets: np.ndarray, *, groups=None, n_groups: int | None = None,
+                               n_bins: int | None = None, out: np.ndarray | None = None, strict: bool = True,
+                               ordinary: bool = False) -> EncodedTokenCounts:
+        """encode_batch_to_numpy and ids_to_counts in one call: the ids never leave the device, only the counts come back."""
+        hip = _capi.HipTokenizer.borrow(self._core_bpe.handle())
+        buf = np.frombuffer(text, dtype=np.uint8) if isinstance(text, (bytes, bytearray)) else text
+        g, spec, flat = self._counts_args(offsets, groups, n_groups, n_bins, out, strict)
+        if g is not None and spec.n_groups == 1 and g.size and (g.min() < 0 or g.max() > 0):
+            raise TokenDaggerError("Counting tokens failed: a group is outside [0, n_groups)")
+        try:
+            counts, info, total = hip.encode_batch_token_counts(buf, np.asarray(offsets, dtype=np.int64), g if spec.n_groups > 1 else None, spec,
+                                                                mode=MODE_ORDINARY if ordinary else MODE_ENCODE, counts=flat)
+        except _capi.TokenDaggerHipError as ex:
+            raise TokenDaggerError(f"Encoding failed: {ex}")
+        return EncodedTokenCounts(*self._counts_result(counts, info, groups is not None, out, strict), total)
 
     # ------------------------------------------------------------------ loss labels ------------
     # labels[i] = ids[i] inside a span, ignore_index elsewhere.  A span starts behind an opener (a string, encoded once with every
