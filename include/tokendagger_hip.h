@@ -787,6 +787,65 @@ int td_decode_batch(td_tokenizer* t, const int32_t* tokens, const int64_t* tok_o
 int td_decode_device(td_tokenizer* t, const void* d_tokens, int64_t n_tokens, void* d_out, int64_t out_capacity,
                      void* d_n_bytes, void* hip_stream);
 
+/* ---- decode rows: segments, a skip set, a stop set, negative ids (td_decode_rows.hip) ---------------------------------------------
+ * ids[n_tokens] (int32) in n_segs segments -> the segments' bytes concatenated in `out`, out_offsets[n_segs + 1] (int64, the first
+ * 0), seg_ids[n_segs] (int64, may be NULL: the ids each segment consumed) and info[4] (int64: bytes, ids emitted, ids skipped,
+ * segments stopped).  What Hugging Face's batch_decode(skip_special_tokens=True) does to a generated batch, what turns PAD / WINDOWS /
+ * CONCAT / BESTFIT rows back into text, and what prints the text a label stream trains on.
+ *   Segments, offsets form (row_stride == 0): tok_offsets[n_segs + 1] (int64), non-decreasing, 0 <= tok_offsets[0],
+ *     tok_offsets[n_segs] <= n_tokens; segment d is ids[tok_offsets[d], tok_offsets[d + 1]).  seg_len is ignored.  Encoded
+ *     documents, cu_seqlens.
+ *   Segments, rows form (row_stride >= 1): n_segs * row_stride <= n_tokens; segment r is ids[r * row_stride, r * row_stride + len_r)
+ *     with len_r = seg_len ? seg_len[r] : row_stride (int32) and 0 <= len_r <= row_stride.  tok_offsets is ignored.  Generation
+ *     output, PAD / WINDOWS rows with their lengths.
+ *   The rule.  A segment is walked left to right and starts open:
+ *     1. once it has stopped no further id of it is looked at: what lies there emits nothing, raises nothing, counts in nothing;
+ *     2. id < 0: skipped under TD_DECODE_SKIP_NEGATIVE, otherwise TD_E_BAD_TOKEN at its index;
+ *     3. an id of the stop set stops the segment; its bytes are emitted only under TD_DECODE_KEEP_STOP and only if it is not also
+ *        skipped (by rule 4).  seg_ids[d] = the ids consumed, the stop id included; the segment's length if it never stopped;
+ *     4. an id of the skip set, and under TD_DECODE_SKIP_SPECIAL every special id of the handle's vocabulary, emits nothing;
+ *     5. any other id emits its token's bytes (a special token its literal); an id that is no token is TD_E_BAD_TOKEN.  A kept stop
+ *        id that is no token is one too.  The lowest index wins.
+ *     info[1] counts the consumed ids that emitted bytes, info[2] those that emitted none by rules 2 - 4; info[1] + info[2] is
+ *     the sum of seg_ids.
+ *   Listed ids must be >= 0 (TD_E_INVALID), may repeat, and may lie above the vocabulary (models pad with n_vocab); at most 65535
+ *     distinct listed ids may lie above it.
+ *   Capacity.  More bytes than out_capacity: TD_E_CAPACITY, position = the bytes needed; out_offsets, seg_ids and info are complete
+ *     and right, no byte is written.  A NULL out with capacity 0 is the sizing call.
+ *   Bounds.  Whatever the ids, offsets and lengths hold: nothing outside ids[0, n_tokens), tok_offsets[0 .. n_segs] and
+ *     seg_len[0, n_segs) is read, nothing outside the outputs is written.  Outputs of a call that raised TD_E_INVALID are unspecified. */
+#define TD_DECODE_KEEP_STOP 1
+#define TD_DECODE_SKIP_NEGATIVE 2
+#define TD_DECODE_SKIP_SPECIAL 4
+typedef struct td_decode_spec {
+    int64_t row_stride;      /* 0: segments come from tok_offsets; >= 1: segment r = ids[r*row_stride, r*row_stride + len_r) */
+    const int32_t* skip_ids; /* host pointers, read before the call returns; any order, duplicates allowed */
+    int64_t n_skip;
+    const int32_t* stop_ids;
+    int64_t n_stop;
+    int64_t flags;           /* TD_DECODE_KEEP_STOP | TD_DECODE_SKIP_NEGATIVE | TD_DECODE_SKIP_SPECIAL */
+} td_decode_spec;
+
+/* The argument checks, on the host (no handle, no device): TD_OK or TD_E_INVALID with *bad_pos (may be NULL) = the offending index:
+ * a segment (decreasing tok_offsets[d + 1] < tok_offsets[d]: d; tok_offsets[0] < 0: 0; tok_offsets[n_segs] > n_tokens: n_segs;
+ * a seg_len[r] outside [0, row_stride]: r), the index of a negative listed id in skip_ids followed by stop_ids (i, or n_skip + i),
+ * or -1 for everything else (a NULL spec, unknown flags, negative sizes, a NULL list with entries, a NULL tok_offsets in the
+ * offsets form, n_segs * row_stride > n_tokens). */
+int td_decode_rows_check(const td_decode_spec* spec, int64_t n_tokens, const int64_t* tok_offsets, const int32_t* seg_len,
+                         int64_t n_segs, int64_t* bad_pos);
+/* Host buffers, synchronously.  The arguments are checked with td_decode_rows_check before anything is launched.  *n_bytes (may be
+ * NULL) = the bytes needed, also on TD_E_CAPACITY, where out_offsets, seg_ids and info are filled as well. */
+int td_decode_rows(td_tokenizer* t, const int32_t* ids, int64_t n_tokens, const int64_t* tok_offsets, const int32_t* seg_len,
+                   int64_t n_segs, const td_decode_spec* spec, uint8_t* out, int64_t out_capacity, int64_t* out_offsets,
+                   int64_t* seg_ids, int64_t* info, int64_t* n_bytes);
+/* DEVICE buffers, asynchronously on hip_stream: no synchronisation and no read-back; errors surface through td_device_status
+ * (TD_E_BAD_TOKEN: the id's index; TD_E_CAPACITY: the bytes needed; TD_E_INVALID: the segment whose offset decreases or whose
+ * length is outside [0, row_stride]).  d_out_offsets, d_seg_ids (may be NULL) and d_info are 8-byte aligned device memory.  The
+ * spec's lists are host memory and are read before the call returns. */
+int td_decode_rows_device(td_tokenizer* t, const void* d_ids, int64_t n_tokens, const void* d_tok_offsets, const void* d_seg_len,
+                          int64_t n_segs, const td_decode_spec* spec, void* d_out, int64_t out_capacity, void* d_out_offsets,
+                          void* d_seg_ids, void* d_info, void* hip_stream);
+
 /* Vocabulary accessors (host tables, no launch): the bytes of one token id (tiktoken decode_single_token_bytes;
  * TD_E_BAD_TOKEN if the id is not in the vocabulary) and the id of one whole token (tiktoken encode_single_token:
  * regular tokens first, then special tokens; TD_E_UNKNOWN_BYTE if the bytes are not a token). */

@@ -68,6 +68,7 @@ EXPORTS = [
     "td_select_plan", "td_select_docs", "td_select_docs_device", "td_encode_batch_select",
     "td_range_plan", "td_range_labels", "td_range_labels_device", "td_encode_batch_range_labels", "td_encode_batch_range_label_rows",
     "td_token_counts_host", "td_token_counts", "td_token_counts_device", "td_encode_batch_token_counts",
+    "td_decode_rows_check", "td_decode_rows", "td_decode_rows_device",
 ]
 
 
@@ -183,6 +184,12 @@ def load_library():
     lib.td_token_counts_device.argtypes = [vp, vp, i64, vp, i64, vp, vp, vp, vp, vp]
     lib.td_token_counts.restype = i32
     lib.td_token_counts.argtypes = [vp, vp, i64, vp, i64, vp, vp, vp, vp]
+    lib.td_decode_rows_check.restype = i32
+    lib.td_decode_rows_check.argtypes = [vp, i64, vp, vp, i64, ctypes.POINTER(i64)]
+    lib.td_decode_rows.restype = i32
+    lib.td_decode_rows.argtypes = [vp, vp, i64, vp, vp, i64, vp, vp, i64, vp, vp, vp, ctypes.POINTER(i64)]
+    lib.td_decode_rows_device.restype = i32
+    lib.td_decode_rows_device.argtypes = [vp, vp, i64, vp, vp, i64, vp, vp, i64, vp, vp, vp, vp]
     lib.td_encode_batch_token_counts.restype = i32
     lib.td_encode_batch_token_counts.argtypes = [vp, vp, vp, i64, i32, vp, vp, vp, vp, ctypes.POINTER(i64)]
     lib.td_comm_unique_id.restype = i32
@@ -421,6 +428,57 @@ def select_plan(tok_offsets, sel=None, spec: SelectSpec | None = None, outputs: 
         raise ex
     k = int(counts[0])
     return (counts, offs[:k + 1], docs[:k]) if outputs else counts
+
+
+TD_DECODE_KEEP_STOP, TD_DECODE_SKIP_NEGATIVE, TD_DECODE_SKIP_SPECIAL = 1, 2, 4
+
+
+class DecodeSpec(ctypes.Structure):
+    """td_decode_spec (include/tokendagger_hip.h).  Build it with decode_spec: that keeps the lists alive beside the pointers."""
+    _fields_ = [("row_stride", ctypes.c_int64), ("skip_ids", ctypes.c_void_p), ("n_skip", ctypes.c_int64),
+                ("stop_ids", ctypes.c_void_p), ("n_stop", ctypes.c_int64), ("flags", ctypes.c_int64)]
+
+
+def decode_spec(row_stride: int = 0, skip=(), stop=(), keep_stop: bool = False, skip_negative: bool = False, skip_special: bool = False,
+                flags: int = 0) -> DecodeSpec:
+    """row_stride 0: segments by tok_offsets; >= 1: rows of that many ids.  skip / stop: iterables of ids."""
+    sk = np.ascontiguousarray(np.asarray(list(skip), dtype=np.int64).astype(np.int32))
+    st = np.ascontiguousarray(np.asarray(list(stop), dtype=np.int64).astype(np.int32))
+    flags |= (TD_DECODE_KEEP_STOP if keep_stop else 0) | (TD_DECODE_SKIP_NEGATIVE if skip_negative else 0) | (TD_DECODE_SKIP_SPECIAL if skip_special else 0)
+    spec = DecodeSpec(row_stride, sk.ctypes.data if len(sk) else None, len(sk), st.ctypes.data if len(st) else None, len(st), flags)
+    spec._keep = (sk, st)
+    return spec
+
+
+def _decode_rows_args(ids, tok_offsets, lengths, n_segs, spec: DecodeSpec):
+    """The arrays of a host decode-rows call -> (ids int32 (flat), offsets int64 | None, lengths int32 | None, n_segs)."""
+    t = np.ascontiguousarray(ids, dtype=np.int32)
+    if spec.row_stride == 0:
+        if tok_offsets is None:
+            raise ValueError("the offsets form (row_stride 0) needs tok_offsets")
+        o = np.ascontiguousarray(tok_offsets, dtype=np.int64)
+        return t.reshape(-1), o, None, len(o) - 1
+    ln = None if lengths is None else np.ascontiguousarray(lengths, dtype=np.int32)
+    if n_segs is None:
+        n_segs = len(ln) if ln is not None else (t.shape[0] if t.ndim == 2 else t.size // int(spec.row_stride))
+    return t.reshape(-1), None, ln, int(n_segs)
+
+
+def decode_rows_check(spec: DecodeSpec | None, n_tokens: int, tok_offsets=None, lengths=None, n_segs: int | None = None) -> None:
+    """td_decode_rows_check (host only, no device): raises TokenDaggerHipError(TD_E_INVALID) with .pos = the offending index (-1: an
+    argument as such)."""
+    lib = load_library()
+    o = None if tok_offsets is None else np.ascontiguousarray(tok_offsets, dtype=np.int64)
+    ln = None if lengths is None else np.ascontiguousarray(lengths, dtype=np.int32)
+    if n_segs is None:
+        n_segs = len(o) - 1 if o is not None else (len(ln) if ln is not None else 0)
+    pos = ctypes.c_int64(0)
+    rc = lib.td_decode_rows_check(ctypes.byref(spec) if spec is not None else None, n_tokens, o.ctypes.data if o is not None else None,
+                                  ln.ctypes.data if ln is not None else None, n_segs, ctypes.byref(pos))
+    if rc != TD_OK:
+        ex = TokenDaggerHipError(rc, f"td_decode_rows_check: invalid arguments (index {pos.value})")
+        ex.pos = int(pos.value)
+        raise ex
 
 
 class CountsSpec(ctypes.Structure):
@@ -1304,6 +1362,40 @@ class HipTokenizer:
                                                            g.ctypes.data if g is not None else None, ctypes.byref(spec), counts.ctypes.data,
                                                            info.ctypes.data, ctypes.byref(total)))
         return _counts_shape(counts, spec), info, int(total.value)
+
+    # ---- decode rows (td_decode_spec) ---------------------------------------------------------------------------
+    def decode_rows(self, ids, spec: DecodeSpec, tok_offsets=None, lengths=None, n_segs: int | None = None, capacity: int | None = None):
+        """td_decode_rows -> (bytes, out_offsets int64[n_segs + 1], seg_ids int64[n_segs], info int64[4] = bytes, ids emitted, ids
+        skipped, segments stopped).  ids: flat, or [rows, row_stride] in the rows form.  capacity None: sized by the call itself
+        (a second call when the first guess was short); given and too small: TokenDaggerHipError(TD_E_CAPACITY) that carries
+        .n_bytes, .out_offsets, .seg_ids and .info."""
+        t, o, ln, n = _decode_rows_args(ids, tok_offsets, lengths, n_segs, spec)
+        offs, seg, info = np.zeros(n + 1, dtype=np.int64), np.zeros(max(n, 1), dtype=np.int64), np.zeros(4, dtype=np.int64)
+        cap = max(64, 8 * len(t)) if capacity is None else capacity
+        nb = ctypes.c_int64(0)
+        for _ in range(2):
+            out = np.empty(max(cap, 1), dtype=np.uint8)
+            rc = self._lib.td_decode_rows(self._h, t.ctypes.data if len(t) else None, len(t), o.ctypes.data if o is not None else None,
+                                          ln.ctypes.data if ln is not None else None, n, ctypes.byref(spec), out.ctypes.data if cap else None,
+                                          cap, offs.ctypes.data, seg.ctypes.data, info.ctypes.data, ctypes.byref(nb))
+            if rc == TD_E_CAPACITY and capacity is None and nb.value > cap:
+                cap = nb.value
+                continue
+            break
+        if rc == TD_E_CAPACITY:
+            ex = TokenDaggerHipError(rc, self._lib.td_last_error(self._h).decode("utf-8", "replace"))
+            ex.n_bytes, ex.out_offsets, ex.seg_ids, ex.info = int(nb.value), offs, seg[:n], info
+            raise ex
+        self._check(rc)
+        return out[:nb.value].tobytes(), offs, seg[:n], info
+
+    def decode_rows_device(self, d_ids: int, n_tokens: int, d_tok_offsets: int, d_seg_len: int, n_segs: int, spec: DecodeSpec, d_out: int,
+                           out_capacity: int, d_out_offsets: int, d_seg_ids: int, d_info: int, stream: int = 0):
+        """td_decode_rows_device: raw device pointers (0 for the ones the form does not use), asynchronous on `stream`; check with
+        device_status(stream)."""
+        self._check(self._lib.td_decode_rows_device(self._h, d_ids or None, n_tokens, d_tok_offsets or None, d_seg_len or None, n_segs,
+                                                    ctypes.byref(spec), d_out or None, out_capacity, d_out_offsets or None, d_seg_ids or None,
+                                                    d_info or None, stream or None))
 
     def device_status_pos(self, stream: int = 0) -> tuple[int, int]:
         """td_device_status without raising: (code, err_pos)."""

@@ -261,6 +261,10 @@ struct td_tokenizer {
     DevBuf rng_bits, rng_cum, rng_chunks, rng_sums, rng_off, rng_ranges, rng_starts, rng_docs;
     // token counts (td_counts.hip): the host entry points' counts, info and document groups on the device
     DevBuf cnt_counts, cnt_info, cnt_groups;
+    // decode rows (td_decode_rows.hip): the per-id table (with the listed ids above max_id behind it) and what it was built for, the
+    // tiles' aggregates and bases; the host entry point's offsets, lengths, byte offsets, segment ids and info on the device
+    DevBuf dcr_table, dcr_tiles, dcr_off, dcr_len, dcr_out_off, dcr_seg_ids, dcr_info;
+    std::vector<int64_t> dcr_key;  // flags, then the distinct listed ids with their bits (sorted); empty: no table yet
     // best-fit packing (td_pack.hip): the items, the sort's and the scan's scratch, the header + runs read back, the plan uploaded,
     // the segments; the host entry points' row lengths and segment documents on the device
     DevBuf pack_key, pack_val, pack_key2, pack_val2, pack_full, pack_pref, pack_tmp, pack_hdr, pack_plan, pack_seg, pack_len, pack_docs;

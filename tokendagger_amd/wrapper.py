@@ -92,6 +92,16 @@ class EncodedTokenCounts(NamedTuple):
     n_tokens: int
 
 
+class DecodedRows(NamedTuple):
+    """Tokenizer.decode_rows_to_numpy (the contract: include/tokendagger_hip.h, td_decode_spec)."""
+    data: np.ndarray     # uint8: the segments' bytes, concatenated
+    offsets: np.ndarray  # int64 [n_segs + 1]: segment d is data[offsets[d]:offsets[d + 1]]
+    seg_ids: np.ndarray  # int64 [n_segs]: the ids each segment consumed, its stop id included
+    n_emitted: int       # ids that emitted bytes
+    n_skipped: int       # ids consumed that emitted none
+    n_stopped: int       # segments a stop id ended
+
+
 class TokenDaggerError(Exception):
     """Base exception for TokenDagger errors (reference: wrapper.py:23-25)."""
 
@@ -749,6 +759,44 @@ class Tokenizer:
             return [b.decode("utf-8", errors=errors) for b in self._core_bpe.decode_batch([list(t) for t in tokens])]
         except Exception as e:
             raise TokenDaggerError(f"Decoding failed: {e}")
+
+    # ------------------------------------------------------------------ decode rows ------------
+    # ids in segments back to text on the device (the contract: include/tokendagger_hip.h, td_decode_spec): a generated [B, S] batch
+    # (skip pad and BOS, stop at EOS: Hugging Face's batch_decode(skip_special_tokens=True)), PAD / WINDOWS rows with their lengths,
+    # cu_seqlens, a label stream (skip_negative: the text a model is trained on).
+    def decode_rows_to_numpy(self, ids: np.ndarray, *, tok_offsets: np.ndarray | None = None, lengths=None, skip_special_tokens: bool = False,
+                             skip=(), stop=(), keep_stop: bool = False, skip_negative: bool = False) -> DecodedRows:
+        """-> DecodedRows(data uint8[n], offsets int64[n_segs + 1], seg_ids int64[n_segs], n_emitted, n_skipped, n_stopped).  ids: 2-D
+        (one segment a row, lengths: the rows' real lengths) or 1-D with tok_offsets.  An id of `stop` ends its segment (and is emitted
+        with keep_stop); seg_ids are the ids each segment consumed, the stop id included."""
+        hip = _capi.HipTokenizer.borrow(self._core_bpe.handle())
+        a = np.asarray(ids)
+        if a.ndim == 2:
+            if tok_offsets is not None:
+                raise TokenDaggerError("tok_offsets goes with 1-D ids; rows take lengths")
+            if a.shape[1] == 0:
+                return DecodedRows(np.zeros(0, dtype=np.uint8), np.zeros(a.shape[0] + 1, dtype=np.int64), np.zeros(a.shape[0], dtype=np.int64), 0, 0, 0)
+            stride, n_segs = int(a.shape[1]), int(a.shape[0])
+        elif a.ndim == 1 and tok_offsets is not None:
+            if lengths is not None:
+                raise TokenDaggerError("lengths goes with 2-D ids")
+            stride, n_segs = 0, None
+        else:
+            raise TokenDaggerError("ids must be 2-D (rows), or 1-D with tok_offsets")
+        try:
+            spec = _capi.decode_spec(stride, skip, stop, keep_stop=keep_stop, skip_negative=skip_negative, skip_special=skip_special_tokens)
+            data, offs, seg, info = hip.decode_rows(a, spec, tok_offsets=tok_offsets, lengths=lengths, n_segs=n_segs)
+        except (_capi.TokenDaggerHipError, ValueError, OverflowError) as ex:
+            raise TokenDaggerError(f"Decoding failed: {ex}")
+        return DecodedRows(np.frombuffer(data, dtype=np.uint8), offs, seg, int(info[1]), int(info[2]), int(info[3]))
+
+    def decode_rows(self, ids: np.ndarray, *, tok_offsets: np.ndarray | None = None, lengths=None, skip_special_tokens: bool = False,
+                    skip=(), stop=(), keep_stop: bool = False, skip_negative: bool = False, errors: str = "replace") -> list[str]:
+        """One string per segment; the arguments of decode_rows_to_numpy."""
+        r = self.decode_rows_to_numpy(ids, tok_offsets=tok_offsets, lengths=lengths, skip_special_tokens=skip_special_tokens, skip=skip,
+                                      stop=stop, keep_stop=keep_stop, skip_negative=skip_negative)
+        data, o = r.data.tobytes(), r.offsets
+        return [data[int(o[d]):int(o[d + 1])].decode("utf-8", errors=errors) for d in range(len(o) - 1)]
 
     def decode_bytes_batch(self, tokens: Sequence[Sequence[int]]) -> list[bytes]:
         try:
