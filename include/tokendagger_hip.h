@@ -706,6 +706,80 @@ int td_encode_batch_token_counts(td_tokenizer* t, const uint8_t* text, const int
                                  const int32_t* doc_group, const td_counts_spec* spec, int64_t* counts, int64_t* info,
                                  int64_t* n_tokens_out);
 
+/* ---- n-gram matches: listed id sequences found in documents (td_ngrams.hip) ----------------------------------------------------------
+ * "Does this document contain any of these known token sequences?" without copying the ids to the host: benchmark decontamination
+ * (every 13-gram of an evaluation set), phrase blocklists, counting canary strings or tool-call markers.
+ * A SET holds n_pats id sequences ("patterns"): pat_ids (int32, flat) and pat_offsets[n_pats + 1] (int64, from 0, non-decreasing).
+ *   Every pattern's length k is in 1 .. TD_NGRAM_MAX_LEN, at most TD_NGRAM_MAX_LENGTHS distinct lengths occur, ids are >= 0, n_pats is
+ *   in 1 .. 2^24 and pat_offsets[n_pats] at most 2^28; anything else is TD_E_INVALID with a message, at creation.  Equal sequences
+ *   may repeat in the list: they are ONE pattern, known by the lowest of their indices.
+ * Per document [a, z) = [tok_offsets[d], tok_offsets[d + 1]):
+ *   an OCCURRENCE is a pair (q, k) with a <= q, q + k <= z and ids[q .. q + k) equal to some pattern of length k; it never reaches
+ *   across a document boundary.  Overlapping and nested occurrences all count: [7,7] occurs three times in 7,7,7,7.
+ *   covered(i) holds when some occurrence (q, k) has q <= i < q + k.
+ *   The ids of the data are not checked against a vocabulary: negative or huge values match nothing, so label streams may be searched.
+ * Outputs, all optional (NULL) except counts; slots at or above tok_offsets[n_docs] are never written:
+ *   cover[i]   (uint8)  covered(i)
+ *   labels[i]  (int32, IN PLACE) set to ignore_index where covered(i) holds, every other slot is not stored to: the caller passes a
+ *              copy of the ids or an existing label stream (never the buffer the call reads as ids)
+ *   doc_stats[d][2] (int64) = {occurrences starting in d, covered ids of d}
+ *   pattern_counts[n_pats] (int64) the occurrences of every pattern; a repeated sequence counts under its lowest index, its other
+ *              indices stay 0.  Zeroed first, or added to under TD_NGRAM_ACCUMULATE.
+ *   counts[4] (int64) = {occurrences, covered ids, documents with at least one occurrence, 0}
+ * The lookup hashes a window only to FIND a candidate and compares the ids before it reports anything: the results are a function of
+ * the inputs alone (not of the hash, the table size, TD_OPT_NGRAM_TAG_BITS or the launch shape), and all sums are integer sums:
+ * bitwise reproducible.
+ * Out of scope: a list of match positions (its order would depend on scheduling), patterns with wildcards, near-duplicate
+ * detection, sets that span several devices. */
+#define TD_NGRAM_MAX_LEN 64
+#define TD_NGRAM_MAX_LENGTHS 8
+#define TD_NGRAM_ACCUMULATE 1
+typedef struct td_ngram_spec {
+    int64_t ignore_index; /* what labels[i] becomes where covered(i) holds; an int32 */
+    int64_t flags;        /* 0 or TD_NGRAM_ACCUMULATE */
+} td_ngram_spec;
+typedef struct td_ngram_set td_ngram_set;
+
+/* Validates and de-duplicates the list, builds the lookup table on the host and uploads it to t's device (synchronous).  The set is
+ * immutable afterwards: any handle on that device, td_clone's included, may use it on any stream, concurrently.  It does not keep t.
+ * Errors: TD_E_INVALID with a message in td_last_error(t). */
+int td_ngram_set_create(td_tokenizer* t, const int32_t* pat_ids, const int64_t* pat_offsets, int64_t n_pats, td_ngram_set** out);
+/* Frees the set's device memory at once, like hipFree: the caller must have finished (synchronised) the work that uses the set. */
+void td_ngram_set_destroy(td_ngram_set* set);
+#define TD_NGRAM_INFO_PATTERNS 1     /* the patterns given */
+#define TD_NGRAM_INFO_DISTINCT 2     /* the distinct ones */
+#define TD_NGRAM_INFO_LENGTHS 3      /* the distinct lengths */
+#define TD_NGRAM_INFO_MAX_LEN 4      /* the longest */
+#define TD_NGRAM_INFO_SLOTS 5        /* the table's slots: a power of two, at least twice the distinct patterns */
+#define TD_NGRAM_INFO_MAX_PROBE 6    /* the longest distance between a pattern's first slot and its own: what bounds every lookup */
+#define TD_NGRAM_INFO_DEVICE_BYTES 7 /* the device memory the set holds */
+int64_t td_ngram_set_info(const td_ngram_set* set, int what); /* -1: no such value */
+
+/* The contract's executable statement, on the host (no handle, no device, no set: the list itself).  tok_offsets must start at 0, be
+ * non-decreasing and end at or below n_tokens.  Argument errors (a bad list, bad offsets, a bad spec, NULL counts, NULL ids with ids to
+ * visit) are TD_E_INVALID and nothing is written. */
+int td_ngram_matches_host(const int32_t* pat_ids, const int64_t* pat_offsets, int64_t n_pats, const int32_t* ids, int64_t n_tokens,
+                          const int64_t* tok_offsets, int64_t n_docs, const td_ngram_spec* spec, uint8_t* cover, int32_t* labels,
+                          int64_t* doc_stats, int64_t* pattern_counts, int64_t* counts);
+/* DEVICE buffers, asynchronously on hip_stream: no synchronisation and no read-back; the zeroing of the outputs is part of the
+ * launches.  d_doc_stats, d_pattern_counts and d_counts are 8-byte aligned.  Offsets that do not start at 0, decrease, are negative
+ * or end above n_tokens raise TD_E_INVALID through td_device_status with err_pos = the lowest such document, and then NOTHING is
+ * written to any output.  A bad spec (unknown flags, an ignore_index outside int32) and a set of another device are TD_E_INVALID
+ * before any launch. */
+int td_ngram_matches_device(td_tokenizer* t, const td_ngram_set* set, const void* d_ids, int64_t n_tokens, const void* d_tok_offsets,
+                            int64_t n_docs, const td_ngram_spec* spec, void* d_cover, void* d_labels, void* d_doc_stats,
+                            void* d_pattern_counts, void* d_counts, void* hip_stream);
+/* Host buffers, synchronously; the offsets are checked like every host entry point's, before any launch.  labels is read and written. */
+int td_ngram_matches(td_tokenizer* t, const td_ngram_set* set, const int32_t* ids, int64_t n_tokens, const int64_t* tok_offsets,
+                     int64_t n_docs, const td_ngram_spec* spec, uint8_t* cover, int32_t* labels, int64_t* doc_stats,
+                     int64_t* pattern_counts, int64_t* counts);
+/* td_encode_batch (TD_MODE_ENCODE / TD_MODE_ORDINARY, no allowed special tokens) and the matches in one call: the ids never leave
+ * the device, only doc_stats[n_docs][2], pattern_counts (both may be NULL), counts and *n_tokens_out (the ids made; may be NULL) come
+ * back.  Synchronous. */
+int td_encode_batch_ngram_matches(td_tokenizer* t, const uint8_t* text, const int64_t* doc_offsets, int64_t n_docs, int mode,
+                                  const td_ngram_set* set, const td_ngram_spec* spec, int64_t* doc_stats, int64_t* pattern_counts,
+                                  int64_t* counts, int64_t* n_tokens_out);
+
 /* Options. */
 #define TD_OPT_LONG_POOL_BYTES 1 /* scratch for pieces longer than 64 bytes (default max(64 MiB, 2 x input)) */
 #define TD_OPT_PROFILE 2         /* 1: bracket the kernels of every td_encode_device call with HIP events on the
@@ -760,6 +834,9 @@ int td_encode_batch_token_counts(td_tokenizer* t, const uint8_t* text, const int
 #define TD_OPT_COUNTS_FLUSH_TILES 16 /* tiles (4096 ids) a workgroup of td_token_counts* counts between two flushes of that table: 1 to the
                                     production interval (64), or 0 (default) for that.  Same results whatever it is; tests shrink it, a call
                                     needs more than 268 M ids to reach the production interval. */
+#define TD_OPT_NGRAM_TAG_BITS 17   /* the hash bits a lookup of td_ngram_matches* compares before it compares ids: 1 to 31, or 0 (default) for the
+                                    production width, all 32.  Same results whatever it is; tests set 1 to 4 so that lookups whose hash
+                                    bits agree and whose ids differ are walked. */
 int td_set_option(td_tokenizer* t, int what, int64_t value);
 
 /* Sums (ms) of the pre-tokenizer kernel and token kernel (probe + merge) durations and the number of calls recorded

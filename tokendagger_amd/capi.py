@@ -43,6 +43,10 @@ TD_OPT_SPARSE = 14
 TD_OPT_COUNTS_SEATS = 15
 TD_OPT_COUNTS_FLUSH_TILES = 16
 TD_COUNTS_ACCUMULATE = 1
+TD_OPT_NGRAM_TAG_BITS = 17
+TD_NGRAM_ACCUMULATE = 1
+TD_NGRAM_MAX_LEN, TD_NGRAM_MAX_LENGTHS = 64, 8
+TD_NGRAM_INFO = {"patterns": 1, "distinct": 2, "lengths": 3, "max_len": 4, "slots": 5, "max_probe": 6, "device_bytes": 7}
 TD_INFO_DEFERRED_TILES, TD_INFO_FLAGGED_TILES = 9, 10
 TD_INFO_DIRECT_TILES = 11
 TD_INFO_LB_TIMEOUTS = 12
@@ -69,6 +73,8 @@ EXPORTS = [
     "td_range_plan", "td_range_labels", "td_range_labels_device", "td_encode_batch_range_labels", "td_encode_batch_range_label_rows",
     "td_token_counts_host", "td_token_counts", "td_token_counts_device", "td_encode_batch_token_counts",
     "td_decode_rows_check", "td_decode_rows", "td_decode_rows_device",
+    "td_ngram_set_create", "td_ngram_set_destroy", "td_ngram_set_info", "td_ngram_matches_host", "td_ngram_matches_device",
+    "td_ngram_matches", "td_encode_batch_ngram_matches",
 ]
 
 
@@ -190,6 +196,20 @@ def load_library():
     lib.td_decode_rows.argtypes = [vp, vp, i64, vp, vp, i64, vp, vp, i64, vp, vp, vp, ctypes.POINTER(i64)]
     lib.td_decode_rows_device.restype = i32
     lib.td_decode_rows_device.argtypes = [vp, vp, i64, vp, vp, i64, vp, vp, i64, vp, vp, vp, vp]
+    lib.td_ngram_set_create.restype = i32
+    lib.td_ngram_set_create.argtypes = [vp, vp, vp, i64, ctypes.POINTER(vp)]
+    lib.td_ngram_set_destroy.restype = None
+    lib.td_ngram_set_destroy.argtypes = [vp]
+    lib.td_ngram_set_info.restype = i64
+    lib.td_ngram_set_info.argtypes = [vp, i32]
+    lib.td_ngram_matches_host.restype = i32
+    lib.td_ngram_matches_host.argtypes = [vp, vp, i64, vp, i64, vp, i64, vp, vp, vp, vp, vp, vp]
+    lib.td_ngram_matches_device.restype = i32
+    lib.td_ngram_matches_device.argtypes = [vp, vp, vp, i64, vp, i64, vp, vp, vp, vp, vp, vp, vp]
+    lib.td_ngram_matches.restype = i32
+    lib.td_ngram_matches.argtypes = [vp, vp, vp, i64, vp, i64, vp, vp, vp, vp, vp, vp]
+    lib.td_encode_batch_ngram_matches.restype = i32
+    lib.td_encode_batch_ngram_matches.argtypes = [vp, vp, vp, i64, i32, vp, vp, vp, vp, vp, ctypes.POINTER(i64)]
     lib.td_encode_batch_token_counts.restype = i32
     lib.td_encode_batch_token_counts.argtypes = [vp, vp, vp, i64, i32, vp, vp, vp, vp, ctypes.POINTER(i64)]
     lib.td_comm_unique_id.restype = i32
@@ -531,6 +551,111 @@ def token_counts_host(ids, tok_offsets=None, groups=None, spec: CountsSpec | Non
         ex.info = info
         raise ex
     return _counts_shape(counts, spec), info
+
+
+class NgramSpec(ctypes.Structure):
+    """td_ngram_spec (include/tokendagger_hip.h)."""
+    _fields_ = [("ignore_index", ctypes.c_int64), ("flags", ctypes.c_int64)]
+
+
+def ngram_spec(ignore_index: int = -100, accumulate: bool = False, flags: int = 0) -> NgramSpec:
+    """ignore_index: what a covered label becomes; accumulate: add to the pattern counts that are there."""
+    return NgramSpec(ignore_index, flags | (TD_NGRAM_ACCUMULATE if accumulate else 0))
+
+
+def ngram_patterns(sequences, offsets=None):
+    """A pattern list as the C ABI takes it -> (pat_ids int32, pat_offsets int64).  sequences: a list of id lists, or flat ids with
+    offsets[n_pats + 1].  Nothing is checked here: the library does that (TD_E_INVALID with a message)."""
+    if offsets is not None:
+        return np.ascontiguousarray(sequences, dtype=np.int32), np.ascontiguousarray(offsets, dtype=np.int64)
+    seqs = [np.asarray(q, dtype=np.int32).reshape(-1) for q in sequences]
+    offs = np.zeros(len(seqs) + 1, dtype=np.int64)
+    if seqs:
+        np.cumsum([len(q) for q in seqs], out=offs[1:])
+    ids = np.concatenate(seqs).astype(np.int32) if seqs else np.zeros(0, dtype=np.int32)
+    return np.ascontiguousarray(ids), offs
+
+
+def _ngram_outputs(total: int, n_docs: int, n_pats: int, spec: NgramSpec, cover: bool, labels, doc_stats: bool, pattern_counts):
+    """The host arrays of a matches call -> (cover | None, labels | None (a copy of the caller's), doc_stats | None, pattern_counts |
+    None, counts).  pattern_counts: True for a new array, an int64[n_pats] array to use (TD_NGRAM_ACCUMULATE adds to it), False / None."""
+    cv = np.zeros(max(total, 1), dtype=np.uint8) if cover else None
+    lb = None
+    if labels is not None:
+        lb = np.array(labels, dtype=np.int32, copy=True).reshape(-1)
+        if len(lb) < total:
+            raise ValueError("labels must have an entry for every id")
+    ds = np.zeros((max(n_docs, 1), 2), dtype=np.int64) if doc_stats else None
+    pc = None
+    if isinstance(pattern_counts, np.ndarray):
+        if pattern_counts.dtype != np.int64 or not pattern_counts.flags.c_contiguous or pattern_counts.size != n_pats:
+            raise ValueError("pattern_counts must be a contiguous int64 array with one entry per pattern")
+        pc = pattern_counts
+    elif pattern_counts:
+        if spec.flags & TD_NGRAM_ACCUMULATE:
+            raise ValueError("TD_NGRAM_ACCUMULATE needs the pattern_counts array to add to")
+        pc = np.zeros(n_pats, dtype=np.int64)
+    return cv, lb, ds, pc, np.zeros(4, dtype=np.int64)
+
+
+def _ngram_result(total, n_docs, cv, lb, ds, pc, counts):
+    return (cv[:total] if cv is not None else None, lb, ds[:n_docs] if ds is not None else None, pc, counts)
+
+
+def _ptr(a):
+    return a.ctypes.data if a is not None else None
+
+
+def ngram_matches_host(sequences, ids, tok_offsets, spec: NgramSpec | None = None, offsets=None, cover: bool = True, labels=None,
+                       doc_stats: bool = True, pattern_counts=True, n_tokens: int | None = None):
+    """td_ngram_matches_host (host only, no device) -> (cover uint8[total] | None, labels int32 | None, doc_stats int64[n_docs, 2] |
+    None, pattern_counts int64[n_pats] | None, counts int64[4] = occurrences, covered ids, documents with an occurrence, 0)."""
+    lib = load_library()
+    spec = spec if spec is not None else ngram_spec()
+    pi, po = ngram_patterns(sequences, offsets)
+    t = np.ascontiguousarray(ids, dtype=np.int32)
+    o = np.ascontiguousarray(tok_offsets, dtype=np.int64)
+    n_docs, n_pats = len(o) - 1, len(po) - 1
+    total = int(o[-1]) if 0 <= int(o[-1]) <= len(t) else 0
+    cv, lb, ds, pc, counts = _ngram_outputs(total, n_docs, max(n_pats, 1), spec, cover, labels, doc_stats, pattern_counts)
+    rc = lib.td_ngram_matches_host(pi.ctypes.data if len(pi) else None, po.ctypes.data, n_pats, t.ctypes.data if len(t) else None,
+                                   len(t) if n_tokens is None else n_tokens, o.ctypes.data, n_docs, ctypes.byref(spec), _ptr(cv), _ptr(lb),
+                                   _ptr(ds), _ptr(pc), counts.ctypes.data)
+    if rc != TD_OK:
+        raise TokenDaggerHipError(rc, "td_ngram_matches_host: invalid patterns, offsets, spec or arguments")
+    return _ngram_result(total, n_docs, cv, lb, ds, pc, counts)
+
+
+class NgramSet:
+    """Owns one td_ngram_set: a de-duplicated pattern list and its lookup table on a tokenizer's device.  Immutable; any handle on
+    that device may use it.  A context manager; close() frees the device memory at once, so the work that uses the set must be done."""
+
+    def __init__(self, tok: "HipTokenizer", sequences, offsets=None):
+        self._lib = tok._lib
+        self._h = None
+        pi, po = ngram_patterns(sequences, offsets)
+        h = ctypes.c_void_p()
+        tok._check(self._lib.td_ngram_set_create(tok._h, pi.ctypes.data if len(pi) else None, po.ctypes.data, len(po) - 1, ctypes.byref(h)))
+        self._h = h
+        self.n_pats = len(po) - 1
+
+    @property
+    def info(self) -> dict[str, int]:
+        """patterns, distinct, lengths, max_len, slots, max_probe, device_bytes."""
+        return {k: int(self._lib.td_ngram_set_info(self._h, v)) for k, v in TD_NGRAM_INFO.items()}
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.td_ngram_set_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
 
 
 class LabelsSpec(ctypes.Structure):
@@ -1362,6 +1487,49 @@ class HipTokenizer:
                                                            g.ctypes.data if g is not None else None, ctypes.byref(spec), counts.ctypes.data,
                                                            info.ctypes.data, ctypes.byref(total)))
         return _counts_shape(counts, spec), info, int(total.value)
+
+    # ---- n-gram matches (td_ngram_spec, td_ngram_set) ------------------------------------------------------------
+    def ngram_set(self, sequences, offsets=None) -> NgramSet:
+        """td_ngram_set_create: a list of id lists, or flat ids with offsets[n_pats + 1]."""
+        return NgramSet(self, sequences, offsets)
+
+    def ngram_matches(self, nset: NgramSet, ids, tok_offsets, spec: NgramSpec | None = None, cover: bool = True, labels=None,
+                      doc_stats: bool = True, pattern_counts=False, n_tokens: int | None = None):
+        """td_ngram_matches -> (cover | None, labels | None (the caller's, copied, with ignore_index where covered), doc_stats
+        int64[n_docs, 2] | None, pattern_counts int64[n_pats] | None, counts int64[4])."""
+        spec = spec if spec is not None else ngram_spec()
+        t = np.ascontiguousarray(ids, dtype=np.int32)
+        o = np.ascontiguousarray(tok_offsets, dtype=np.int64)
+        n_docs = len(o) - 1
+        total = int(o[-1]) if 0 <= int(o[-1]) <= len(t) else 0
+        cv, lb, ds, pc, counts = _ngram_outputs(total, n_docs, nset.n_pats, spec, cover, labels, doc_stats, pattern_counts)
+        self._check(self._lib.td_ngram_matches(self._h, nset._h, t.ctypes.data if len(t) else None, len(t) if n_tokens is None else n_tokens,
+                                               o.ctypes.data, n_docs, ctypes.byref(spec), _ptr(cv), _ptr(lb), _ptr(ds), _ptr(pc),
+                                               counts.ctypes.data))
+        return _ngram_result(total, n_docs, cv, lb, ds, pc, counts)
+
+    def ngram_matches_device(self, nset: NgramSet, d_ids: int, n_tokens: int, d_tok_offsets: int, n_docs: int, spec: NgramSpec, d_cover: int,
+                             d_labels: int, d_doc_stats: int, d_pattern_counts: int, d_counts: int, stream: int = 0):
+        """td_ngram_matches_device: raw device pointers (0: that output is not wanted), asynchronous on `stream`; check with
+        device_status(stream)."""
+        self._check(self._lib.td_ngram_matches_device(self._h, nset._h, d_ids or None, n_tokens, d_tok_offsets or None, n_docs, ctypes.byref(spec),
+                                                      d_cover or None, d_labels or None, d_doc_stats or None, d_pattern_counts or None,
+                                                      d_counts or None, stream or None))
+
+    def encode_batch_ngram_matches(self, text, doc_offsets, nset: NgramSet, spec: NgramSpec | None = None, mode: int = TD_MODE_ENCODE,
+                                   doc_stats: bool = True, pattern_counts=False):
+        """td_encode_batch_ngram_matches: encode + matches in one call, the ids stay on the device -> (doc_stats | None,
+        pattern_counts | None, counts, n_tokens)."""
+        spec = spec if spec is not None else ngram_spec()
+        buf = _as_u8(text)
+        offs = np.ascontiguousarray(doc_offsets, dtype=np.int64)
+        n_docs = len(offs) - 1
+        _, _, ds, pc, counts = _ngram_outputs(0, n_docs, nset.n_pats, spec, False, None, doc_stats, pattern_counts)
+        total = ctypes.c_int64(0)
+        self._check(self._lib.td_encode_batch_ngram_matches(self._h, buf.ctypes.data if len(buf) else None, offs.ctypes.data, n_docs, mode,
+                                                            nset._h, ctypes.byref(spec), _ptr(ds), _ptr(pc), counts.ctypes.data,
+                                                            ctypes.byref(total)))
+        return (ds[:n_docs] if ds is not None else None), pc, counts, int(total.value)
 
     # ---- decode rows (td_decode_spec) ---------------------------------------------------------------------------
     def decode_rows(self, ids, spec: DecodeSpec, tok_offsets=None, lengths=None, n_segs: int | None = None, capacity: int | None = None):

@@ -1135,6 +1135,7 @@ int td_set_option(td_tokenizer* t, int what, int64_t value) {
         case TD_OPT_SMALL_PATH: o.small_enabled = value != 0; return TD_OK;
         case TD_OPT_PIPE_THREADS: if (value < 1 || value > 256) break; o.pipe_threads = (int)value; return TD_OK;
         case TD_OPT_COUNTS_FLUSH_TILES: if (value < 0 || value > CNT_FLUSH_TILES) break; o.counts_flush_tiles = (int)value; return TD_OK;
+        case TD_OPT_NGRAM_TAG_BITS: if (value < 0 || value > 31) break; o.ngram_tag_bits = (int)value; return TD_OK;
         case TD_OPT_COUNTS_SEATS: {  // a power of two from 2 to the production size, or 0 for it
             if (value == 0) { o.counts_seat_bits = 0; return TD_OK; }
             if (value < 2 || value > CNT_SEATS || (value & (value - 1))) break;

@@ -217,6 +217,7 @@ struct Options {
     int pipe_threads = 16;        // TD_OPT_PIPE_THREADS
     int counts_flush_tiles = 0;   // TD_OPT_COUNTS_FLUSH_TILES: tiles of a workgroup between two flushes of that table, 0 = CNT_FLUSH_TILES (tests shrink it)
     int counts_seat_bits = 0;     // TD_OPT_COUNTS_SEATS: log2 of the seats of td_cnt_tiles' on-chip table, 0 = the production size (tests force conflicts with 2)
+    int ngram_tag_bits = 0;       // TD_OPT_NGRAM_TAG_BITS: hash bits td_ng_tiles compares before the ids, 0 = all 32 (tests force id compares with 1 to 4)
     static Options from_env();
 };
 
@@ -264,6 +265,9 @@ struct td_tokenizer {
     // decode rows (td_decode_rows.hip): the per-id table (with the listed ids above max_id behind it) and what it was built for, the
     // tiles' aggregates and bases; the host entry point's offsets, lengths, byte offsets, segment ids and info on the device
     DevBuf dcr_table, dcr_tiles, dcr_off, dcr_len, dcr_out_off, dcr_seg_ids, dcr_info;
+    // n-gram matches (td_ngrams.hip): the bad-offsets word, doc_stats where the caller has none; the host entry points' cover, labels,
+    // doc_stats, pattern counts and counts on the device
+    DevBuf ng_head, ng_stats, ng_cover, ng_labels, ng_doc_stats, ng_pats, ng_counts;
     std::vector<int64_t> dcr_key;  // flags, then the distinct listed ids with their bits (sorted); empty: no table yet
     // best-fit packing (td_pack.hip): the items, the sort's and the scan's scratch, the header + runs read back, the plan uploaded,
     // the segments; the host entry points' row lengths and segment documents on the device

@@ -92,6 +92,16 @@ class EncodedTokenCounts(NamedTuple):
     n_tokens: int
 
 
+class NgramMatches(NamedTuple):
+    """Listed id sequences found in documents (Tokenizer.ids_to_ngram_matches / encode_batch_to_ngram_matches; the contract:
+    include/tokendagger_hip.h, td_ngram_spec)."""
+    cover: np.ndarray | None           # uint8 [total]: 1 where the id lies inside an occurrence
+    labels: np.ndarray | None          # int32 [total]: the labels given, ignore_index where covered
+    doc_stats: np.ndarray | None       # int64 [n_docs, 2]: occurrences starting in the document, its covered ids
+    pattern_counts: np.ndarray | None  # int64 [n_pats]: occurrences of every pattern (a repeated one under its lowest index)
+    counts: np.ndarray                 # int64 [4]: occurrences, covered ids, documents with an occurrence, 0
+
+
 class DecodedRows(NamedTuple):
     """Tokenizer.decode_rows_to_numpy (the contract: include/tokendagger_hip.h, td_decode_spec)."""
     data: np.ndarray     # uint8: the segments' bytes, concatenated
@@ -549,6 +559,55 @@ class Tokenizer:
         except _capi.TokenDaggerHipError as ex:
             raise TokenDaggerError(f"Encoding failed: {ex}")
         return EncodedTokenCounts(*self._counts_result(counts, info, groups is not None, out, strict), total)
+
+    # ------------------------------------------------------------------ n-gram matches ---------
+    # "Does this document contain any of these known token sequences?" on the device: decontamination against an evaluation set
+    # (ngram_set_from_texts(benchmark, 13), then select_docs(ids, tok_offsets, np.flatnonzero(doc_stats[:, 0] == 0))), phrase
+    # blocklists, masking the covered ids of a label stream (labels=...).  A set holds up to 2^24 sequences of 1 .. 64 ids in at most 8
+    # distinct lengths; use it as a context manager or close() it when the work that uses it is done.
+    def ngram_set(self, sequences, offsets=None):
+        """A set of id sequences on this tokenizer's device: a list of id lists, or flat ids with offsets[n_pats + 1]."""
+        hip = _capi.HipTokenizer.borrow(self._core_bpe.handle())
+        try:
+            return hip.ngram_set(sequences, offsets)
+        except _capi.TokenDaggerHipError as ex:
+            raise TokenDaggerError(f"Building the n-gram set failed: {ex}")
+
+    def ngram_set_from_texts(self, texts: Sequence[str], n: int, stride: int = 1):
+        """Every n-gram (n ids) of every text, at every stride-th position, de-duplicated: the decontamination recipe.  Texts shorter
+        than n ids contribute nothing."""
+        if n < 1 or n > _capi.TD_NGRAM_MAX_LEN or stride < 1:
+            raise TokenDaggerError("n must be in 1 .. 64 and stride at least 1")
+        grams = [np.lib.stride_tricks.sliding_window_view(np.asarray(t, dtype=np.int32), n)[::stride]
+                 for t in self.encode_ordinary_batch(list(texts)) if len(t) >= n]
+        if not grams:
+            raise TokenDaggerError(f"no text has {n} ids: the set would be empty")
+        uniq = np.unique(np.concatenate(grams), axis=0)
+        return self.ngram_set(uniq.reshape(-1), np.arange(len(uniq) + 1, dtype=np.int64) * n)
+
+    def ids_to_ngram_matches(self, ids: np.ndarray, tok_offsets: np.ndarray, nset, *, cover: bool = True, labels=None,
+                             ignore_index: int = -100, pattern_counts: bool = False) -> NgramMatches:
+        """Where the sequences of `nset` occur in the documents.  labels: a stream aligned with ids (the ids themselves, or the labels
+        of ids_to_labels); a copy comes back with ignore_index at every covered id."""
+        hip = _capi.HipTokenizer.borrow(self._core_bpe.handle())
+        try:
+            return NgramMatches(*hip.ngram_matches(nset, ids, tok_offsets, _capi.ngram_spec(ignore_index), cover=cover, labels=labels,
+                                                   pattern_counts=pattern_counts))
+        except _capi.TokenDaggerHipError as ex:
+            raise TokenDaggerError(f"Matching n-grams failed: {ex}")
+
+    def encode_batch_to_ngram_matches(self, text: np.ndarray | bytes, offsets: np.ndarray, nset, *, pattern_counts: bool = False,
+                                      ordinary: bool = False):
+        """encode_batch_to_numpy and ids_to_ngram_matches in one call: the ids never leave the device -> (NgramMatches without cover
+        and labels, the ids made)."""
+        hip = _capi.HipTokenizer.borrow(self._core_bpe.handle())
+        buf = np.frombuffer(text, dtype=np.uint8) if isinstance(text, (bytes, bytearray)) else text
+        try:
+            ds, pc, counts, total = hip.encode_batch_ngram_matches(buf, np.asarray(offsets, dtype=np.int64), nset,
+                                                                   mode=MODE_ORDINARY if ordinary else MODE_ENCODE, pattern_counts=pattern_counts)
+        except _capi.TokenDaggerHipError as ex:
+            raise TokenDaggerError(f"Encoding failed: {ex}")
+        return NgramMatches(None, None, ds, pc, counts), total
 
     # ------------------------------------------------------------------ loss labels ------------
     # labels[i] = ids[i] inside a span, ignore_index elsewhere.  A span starts behind an opener (a string, encoded once with every
