@@ -171,7 +171,8 @@ int td_encode_batch_with_special_strs(td_tokenizer* t, const uint8_t* text, cons
 #define TD_INFO_LISTED_PIECES 14 /* ... and missed pieces of the same tiles that were merged themselves, last call */
 #define TD_INFO_CHAR_SEEDS 15    /* characters of 2..3 bytes this vocabulary allows to enter the merge of a long piece as one part (td_common.h) */
 #define TD_INFO_SPARSE 16        /* 1: the last td_encode_device call of the handle took the sparse launch sequence (TD_OPT_SPARSE), 0: the dense one */
-#define TD_INFO_DIRECT_TILES 11  /* pre-tokenizer tiles (8 KiB) whose ids the fused tile loop wrote straight to the output (TD_OPT_DIRECT), last call */
+#define TD_INFO_WS_FILLED_BYTES 17 /* bytes this handle has filled since it was made (TD_OPT_WS_FILL): at allocation and in front of steps */
+#define TD_INFO_DIRECT_TILES 11 /* pre-tokenizer tiles (8 KiB) whose ids the fused tile loop wrote straight to the output (TD_OPT_DIRECT), last call */
 int64_t td_info(const td_tokenizer* t, int what);
 
 /*
@@ -837,6 +838,14 @@ int td_encode_batch_ngram_matches(td_tokenizer* t, const uint8_t* text, const in
 #define TD_OPT_NGRAM_TAG_BITS 17   /* the hash bits a lookup of td_ngram_matches* compares before it compares ids: 1 to 31, or 0 (default) for the
                                     production width, all 32.  Same results whatever it is; tests set 1 to 4 so that lookups whose hash
                                     bits agree and whose ids differ are walked. */
+#define TD_OPT_WS_FILL 18          /* debugging: -1 (default) off; 0..255: every device buffer the handle allocates from now on is filled
+                                    with this byte over its whole capacity when it is allocated, and every buffer of the step workspace
+                                    (all but the control block's first 256 bytes) again in front of every step of td_encode_device and of
+                                    whatever ends in one, on the call's stream.  A kernel that reads a workspace word nobody wrote in this
+                                    call then reads this byte, not what the allocator or the last call left: results must not depend on
+                                    it.  TD_INFO_WS_FILLED_BYTES counts what was filled.  TD_WS_FILL in the environment at td_create time
+                                    sets it too (td_create's own allocations included); td_clone hands it on.  Off: one branch per
+                                    allocation and per step. */
 int td_set_option(td_tokenizer* t, int what, int64_t value);
 
 /* Sums (ms) of the pre-tokenizer kernel and token kernel (probe + merge) durations and the number of calls recorded

@@ -355,6 +355,23 @@ FUZZ_ALPHABET = [
 ]
 
 
+def char_seed_runs(rng: random.Random, n: int) -> list[str]:
+    """n runs of letters, 60..260 bytes each, in scripts whose characters are tokens (CJK, kana, hangul, Thai, Devanagari, Cyrillic,
+    accented Latin, Arabic): each is one piece, most are longer than 64 bytes (tests/test_gpu_char_seeds.py, test_gpu_determinism.py)."""
+    ranges = [(0x4E00, 0x9FFF), (0x3040, 0x30FF), (0xAC00, 0xD7A3), (0x0E01, 0x0E5B), (0x0900, 0x097F), (0x0400, 0x04FF), (0x00C0, 0x024F), (0x0600, 0x06FF)]
+    common = "的一是不了人我在有他这为之大来以个中上们到说国和地也子时道出而要于就下得可你年生こんにちはありがとう世界カタカナ한국어안녕하세요감사합니다"
+    out = []
+    for _ in range(n):
+        kind = rng.random()
+        lo, hi = rng.choice(ranges)
+        target = rng.randint(60, 260)
+        s = ""
+        while len(s.encode("utf-8")) < target:
+            s += rng.choice(common) if kind < 0.5 else chr(rng.randint(lo, hi)) if kind < 0.9 else rng.choice([chr(rng.randint(lo, hi)), rng.choice(common), "a", "é"])
+        out.append(s)
+    return out
+
+
 def fuzz_string(rng: random.Random, max_parts: int = 14) -> str:
     return "".join(rng.choice(FUZZ_ALPHABET) for _ in range(rng.randint(1, max_parts)))
 

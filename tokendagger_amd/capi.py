@@ -52,6 +52,8 @@ TD_INFO_DIRECT_TILES = 11
 TD_INFO_LB_TIMEOUTS = 12
 TD_INFO_REPEATS, TD_INFO_LISTED_PIECES, TD_INFO_CHAR_SEEDS = 13, 14, 15
 TD_INFO_SPARSE = 16
+TD_OPT_WS_FILL = 18  # debugging: -1 off, 0..255 the byte every workspace buffer is filled with at allocation and before every step
+TD_INFO_WS_FILLED_BYTES = 17
 
 EXPORTS = [
     "td_create", "td_clone", "td_destroy", "td_last_error", "td_encode_batch", "td_encode_device", "td_reserve",

@@ -49,6 +49,7 @@ Options Options::from_env() {
     if (const char* e = getenv("TD_DD_MINLEN")) o.dd_minlen = (uint32_t)std::max(2, atoi(e));
     if (const char* e = getenv("TD_DD_ENTRIES")) { const long v = atol(e); if (v >= 2 && v <= (1l << 24) && !(v & (v - 1))) o.dd_entries_opt = (uint32_t)v; }
     if (const char* e = getenv("TD_COLL_SHRINK")) o.coll_shrink = std::max(1, atoi(e));
+    if (const char* e = getenv("TD_WS_FILL")) { const int v = atoi(e); if (v >= 0 && v <= 255) o.ws_fill = v; }
     return o;
 }
 
@@ -62,6 +63,31 @@ int ensure(td_tokenizer* t, DevBuf& b, size_t bytes) {
     HIP_TRY(t, hipMalloc(&b.p, want));
     b.cap = want;
     t->ws_bytes += want;
+    if (t->opt.ws_fill >= 0) {  // (debugging, TD_OPT_WS_FILL: what nobody has written yet reads as this byte, not as what the allocator left)
+        int rc = own_streams(t);
+        if (rc) return rc;
+        HIP_TRY(t, hipMemsetAsync(b.p, t->opt.ws_fill, want, t->s_own));
+        HIP_TRY(t, hipStreamSynchronize(t->s_own));
+        t->ws_filled += (int64_t)want;
+    }
+    return TD_OK;
+}
+
+// TD_OPT_WS_FILL in front of a step: every buffer of the step workspace over its whole capacity, on the call's stream, but for the
+// control block's own bytes (the sticky error, the counters the host reads after a call); td_giant_pieces' scratch behind them is filled.
+static int fill_step_ws(td_tokenizer* t, hipStream_t stream) {
+    DevBuf* const ws[] = {&t->dd_table, &t->rest_mask, &t->coll_ctr, &t->tile_state, &t->slab, &t->docbits, &t->startbits, &t->slow_list,
+                          &t->tile_flag, &t->tile_carry, &t->stage, &t->stage2, &t->tile_count, &t->tile_extra, &t->miss_list,
+                          &t->flagged_list, &t->deferred_list, &t->gap_list, &t->gapbits, &t->gx_exit, &t->gx_state, &t->tile_base,
+                          &t->doc_slot, &t->long_list, &t->pool, &t->ctl, &t->tile_first_doc, &t->chunk_pref};
+    static_assert(sizeof ws / sizeof ws[0] == 28, "the step workspace (td_handle.h)");
+    for (DevBuf* b : ws) {
+        if (!b->p) continue;
+        const size_t skip = b == &t->ctl ? std::min(CTL_BYTES, b->cap) : 0;
+        if (b->cap == skip) continue;
+        HIP_TRY(t, hipMemsetAsync((char*)b->p + skip, t->opt.ws_fill, b->cap - skip, stream));
+        t->ws_filled += (int64_t)(b->cap - skip);
+    }
     return TD_OK;
 }
 
@@ -266,6 +292,7 @@ int td::encode_device_locked(td_tokenizer* t, const void* d_text, int64_t n, con
     }
     const bool dense = mode != TD_MODE_ENCODE && !t->H.merge_closed;
     if ((rc = reserve_ws(t, n, n_docs, dense))) return rc;
+    if (t->opt.ws_fill >= 0 && (rc = fill_step_ws(t, stream))) return rc;  // (in front of the plain launches and of a graph's replay alike)
     const int64_t n_tiles = (n + K_TILE - 1) / K_TILE;
     if (n_tiles > 0x7FFFFFF0ll) { t->err = "input too large"; return TD_E_INVALID; }
     EncodeArgs a;
@@ -295,7 +322,7 @@ int td::encode_device_locked(td_tokenizer* t, const void* d_text, int64_t n, con
     a.long_count = &ctl->long_count;
     a.giant_count = &ctl->giant_count;
     a.gp_ctl = ctl->gp_ctl;
-    a.gp_scratch = (uint32_t*)((char*)t->ctl.p + CTL_BYTES);  // (behind the control block; needs no reset)
+    a.gp_scratch = (uint32_t*)((char*)t->ctl.p + CTL_BYTES);  // (behind the control block; needs no reset: what is read was written in front of the grid barrier the read is behind)
     a.gp_coop_min = t->opt.gp_coop_min;
     a.tile_draw = &ctl->tile_draw;
     a.far_count = &ctl->far_tiles;
@@ -1107,6 +1134,7 @@ int64_t td_info(const td_tokenizer* t, int what) {
         case TD_INFO_LISTED_PIECES: return t->last_listed;
         case TD_INFO_CHAR_SEEDS: return (int64_t)t->H.n_char_seeds;
         case TD_INFO_SPARSE: return t->last_sparse ? 1 : 0;
+        case TD_INFO_WS_FILLED_BYTES: return t->ws_filled;
     }
     return -1;
 }
@@ -1136,6 +1164,7 @@ int td_set_option(td_tokenizer* t, int what, int64_t value) {
         case TD_OPT_PIPE_THREADS: if (value < 1 || value > 256) break; o.pipe_threads = (int)value; return TD_OK;
         case TD_OPT_COUNTS_FLUSH_TILES: if (value < 0 || value > CNT_FLUSH_TILES) break; o.counts_flush_tiles = (int)value; return TD_OK;
         case TD_OPT_NGRAM_TAG_BITS: if (value < 0 || value > 31) break; o.ngram_tag_bits = (int)value; return TD_OK;
+        case TD_OPT_WS_FILL: if (value < -1 || value > 255) break; o.ws_fill = (int)value; return TD_OK;
         case TD_OPT_COUNTS_SEATS: {  // a power of two from 2 to the production size, or 0 for it
             if (value == 0) { o.counts_seat_bits = 0; return TD_OK; }
             if (value < 2 || value > CNT_SEATS || (value & (value - 1))) break;

@@ -218,6 +218,7 @@ struct Options {
     int counts_flush_tiles = 0;   // TD_OPT_COUNTS_FLUSH_TILES: tiles of a workgroup between two flushes of that table, 0 = CNT_FLUSH_TILES (tests shrink it)
     int counts_seat_bits = 0;     // TD_OPT_COUNTS_SEATS: log2 of the seats of td_cnt_tiles' on-chip table, 0 = the production size (tests force conflicts with 2)
     int ngram_tag_bits = 0;       // TD_OPT_NGRAM_TAG_BITS: hash bits td_ng_tiles compares before the ids, 0 = all 32 (tests force id compares with 1 to 4)
+    int ws_fill = -1;             // TD_OPT_WS_FILL / TD_WS_FILL (debugging): -1 = off, 0..255 = the byte ensure() and every step fill the workspace with
     static Options from_env();
 };
 
@@ -317,6 +318,7 @@ struct td_tokenizer {
     const uint16_t* d_rx_s1 = nullptr;
     const uint8_t* d_rx_s2 = nullptr;
     size_t ws_bytes = 0;
+    int64_t ws_filled = 0;        // TD_INFO_WS_FILLED_BYTES: what ensure() and the steps have filled (Options::ws_fill)
     // One workspace per handle: work of this handle may be in flight on one stream at a time.  A call on another
     // stream first waits (on the device, not the host) for the previous call's last kernel.
     Event last_done;

@@ -200,7 +200,7 @@ __device__ __forceinline__ int64_t lower_bound_i64(const int64_t* a, int64_t n, 
 __global__ void td_mark_docs(const int64_t* doc_offsets, int64_t n_docs, int64_t n, uint32_t* docbits,
                              uint32_t* tile_first_doc) {
     // Document offsets are non-decreasing, so a document knows from its two neighbours whether it shares its word of the
-    // bitmap or is the first one of its tile: the common case (alone in its 32 bytes, the bitmap is zeroed by td_prepare) is
+    // bitmap or is the first one of its tile: the common case (alone in its 32 bytes; docbits is zeroed by td_prepare, the launch in front) is
     // a plain store, and the first document of a tile is exactly one thread's plain store.  (One atomicOr + one atomicMin per
     // document were 62 us per GiB of short paragraphs: 1.7 M atomics.)
     for (int64_t d = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; d < n_docs; d += (int64_t)gridDim.x * blockDim.x) {
