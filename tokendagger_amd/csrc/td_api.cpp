@@ -409,7 +409,8 @@ int td::encode_device_locked(td_tokenizer* t, const void* d_text, int64_t n, con
         a.sp.cand_pos = (int64_t*)t->sp_cpos.p;
         a.sp.cand_lit = (int32_t*)t->sp_clit.p;
         a.sp.cand_count = (uint32_t*)t->sp_ccount.p;
-        a.sp.cand_cap = (uint32_t)std::min<size_t>(t->sp_clit.cap / 4, 0x7FFFFFF0u);
+        // (entries BOTH lists hold: ensure() grows a buffer by an eighth and 256 BYTES, which is 64 entries of cand_lit and 32 of cand_pos)
+        a.sp.cand_cap = (uint32_t)std::min<size_t>(std::min(t->sp_clit.cap / 4, t->sp_cpos.cap / 8), 0x7FFFFFF0u);
         a.sp.accbits = (uint32_t*)t->sp_acc.p;
         a.sp.n = t->sp_n;
         a.sp.maxlen = t->sp_maxlen;

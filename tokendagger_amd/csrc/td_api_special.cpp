@@ -2,6 +2,7 @@
 #include "td_handle.h"
 #include "td_offsets.h"
 #include "td_regex.h"
+#include "td_special_table.h"
 
 namespace {
 
@@ -22,54 +23,35 @@ int build_special_table(td_tokenizer* t, const int32_t* allowed_ids, int64_t n_a
     }
     std::sort(lits.begin(), lits.end(), [](const auto& x, const auto& y) { return x.first < y.first; });  // (bytewise: std::string compares as unsigned char)
     lits.erase(std::unique(lits.begin(), lits.end(), [](const auto& x, const auto& y) { return x.first == y.first; }), lits.end());
-    const size_t n = lits.size();
-    std::vector<uint8_t> bytes;
-    std::vector<uint32_t> off(n + 1, 0), lens(n + 1, 0), first2(2048, 0);
-    std::vector<int32_t> ids(n), parent(n, -1);
-    uint32_t maxlen = 0;
-    for (size_t i = 0; i < n; ++i) {
-        const std::string& x = lits[i].first;
-        off[i] = (uint32_t)bytes.size();
-        lens[i] = (uint32_t)x.size();
-        bytes.insert(bytes.end(), x.begin(), x.end());
-        while (bytes.size() % 4) bytes.push_back(0);
-        if (x.size() > 48) {
+    for (const auto& lit : lits) {
+        const std::string& x = lit.first;
+        if (x.size() > SP_MAXLEN) {
             t->err = "td_encode_device_with_special: the allowed special token '" + x + "' is " + std::to_string(x.size()) +
                      " bytes long; the device search takes literals of at most 48 bytes (td_encode_batch_with_special searches on the host)";
             return TD_E_INVALID;
         }
-        ids[i] = lits[i].second;
-        maxlen = std::max<uint32_t>(maxlen, (uint32_t)x.size());
-        // longest proper prefix that is a literal: in sorted order a prefix stands in front of its extensions
-        for (size_t j = i; j-- > 0;) {
-            const std::string& y = lits[j].first;
-            if (y.size() < x.size() && x.compare(0, y.size(), y) == 0) { parent[i] = (int32_t)j; break; }
-            if (y.empty() || (uint8_t)y[0] != (uint8_t)x[0]) break;
-        }
-        const uint32_t b0 = (uint8_t)x[0];
-        if (x.size() == 1) for (uint32_t b1 = 0; b1 < 256; ++b1) first2[(b0 << 8 | b1) >> 5] |= 1u << ((b0 << 8 | b1) & 31);
-        else { const uint32_t kk = b0 << 8 | (uint8_t)x[1]; first2[kk >> 5] |= 1u << (kk & 31); }
     }
-    if (bytes.empty()) bytes.push_back(0);
+    const size_t n = lits.size();
+    const SpecialTableHost T = special_table_build(lits);
     int rc;
-    if ((rc = ensure(t, t->sp_bytes, bytes.size() + 16))) return rc;
+    if ((rc = ensure(t, t->sp_bytes, T.bytes.size() + 16))) return rc;
     if ((rc = ensure(t, t->sp_off, (n + 1) * 4))) return rc;
     if ((rc = ensure(t, t->sp_len, (n + 1) * 4))) return rc;
     if ((rc = ensure(t, t->sp_id, std::max<size_t>(n, 1) * 4))) return rc;
     if ((rc = ensure(t, t->sp_parent, std::max<size_t>(n, 1) * 4))) return rc;
-    if ((rc = ensure(t, t->sp_first2, 2048 * 4))) return rc;
+    if ((rc = ensure(t, t->sp_first2, SP_FIRST2_WORDS * 4))) return rc;
     if ((rc = own_streams(t))) return rc;
     // (the callers have waited for the kernels that read the previous table; the call that uses this one is ordered behind
     // these copies by the host: each is waited for)
-    if ((rc = copy_wait(t, t->sp_bytes.p, bytes.data(), bytes.size(), hipMemcpyHostToDevice, t->s_own))) return rc;
-    if ((rc = copy_wait(t, t->sp_off.p, off.data(), (n + 1) * 4, hipMemcpyHostToDevice, t->s_own))) return rc;
-    if ((rc = copy_wait(t, t->sp_len.p, lens.data(), (n + 1) * 4, hipMemcpyHostToDevice, t->s_own))) return rc;
-    if ((rc = copy_wait(t, t->sp_id.p, ids.data(), n * 4, hipMemcpyHostToDevice, t->s_own))) return rc;
-    if ((rc = copy_wait(t, t->sp_parent.p, parent.data(), n * 4, hipMemcpyHostToDevice, t->s_own))) return rc;
-    if ((rc = copy_wait(t, t->sp_first2.p, first2.data(), 2048 * 4, hipMemcpyHostToDevice, t->s_own))) return rc;
+    if ((rc = copy_wait(t, t->sp_bytes.p, T.bytes.data(), T.bytes.size(), hipMemcpyHostToDevice, t->s_own))) return rc;
+    if ((rc = copy_wait(t, t->sp_off.p, T.off.data(), (n + 1) * 4, hipMemcpyHostToDevice, t->s_own))) return rc;
+    if ((rc = copy_wait(t, t->sp_len.p, T.len.data(), (n + 1) * 4, hipMemcpyHostToDevice, t->s_own))) return rc;
+    if ((rc = copy_wait(t, t->sp_id.p, T.id.data(), n * 4, hipMemcpyHostToDevice, t->s_own))) return rc;
+    if ((rc = copy_wait(t, t->sp_parent.p, T.parent.data(), n * 4, hipMemcpyHostToDevice, t->s_own))) return rc;
+    if ((rc = copy_wait(t, t->sp_first2.p, T.first2.data(), SP_FIRST2_WORDS * 4, hipMemcpyHostToDevice, t->s_own))) return rc;
     t->sp_key = key;
     t->sp_n = (uint32_t)n;
-    t->sp_maxlen = maxlen;
+    t->sp_maxlen = T.maxlen;
     return TD_OK;
 }
 

@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include "td_common.h"
+#include "td_special_dev.h"  // SpecialTable: the allowed special literals of a call
 
 namespace td {
 
@@ -15,23 +16,6 @@ struct LongEntry {      // a piece longer than K_MAXSHORT bytes, merged by td_lo
     uint32_t len;       // bytes
     uint32_t ntok;      // out: number of tokens
     uint64_t pool_off;  // out: offset (in u32) of its tokens inside the pool
-};
-
-// The allowed special literals of a call, sorted bytewise (td_special.hip), and the two bitmaps of the cut search.
-struct SpecialTable {
-    const uint8_t* bytes;     // the literals, each dword-aligned and zero-padded to a multiple of 4 bytes
-    const uint32_t* off;      // [n] byte offset of literal i (a multiple of 4)
-    const uint32_t* len;      // [n] its length in bytes
-    const int32_t* id;        // [n]
-    const int32_t* parent;    // [n] the longest other literal that is a proper prefix of literal i, or -1
-    const uint32_t* first2;   // [2048] bit (b0 << 8 | b1): a literal starts with these two bytes
-    int64_t* cand_pos;        // [cand_cap] positions whose first two bytes start an allowed literal
-    int32_t* cand_lit;        // [cand_cap] the literal matched there, or -1
-    uint32_t* cand_count;
-    uint32_t cand_cap;
-    uint32_t* hitbits;        // [(n_text+31)/32] an allowed literal matches at this byte
-    uint32_t* accbits;        // ... and is cut out (not inside a literal cut out in front of it)
-    uint32_t n, maxlen;       // literals; bytes of the longest one.  n == 0: no cuts in this call
 };
 
 // Generic split patterns: text bytes per lane of td_generic_chunks.  A lane needs about 3 microseconds per byte (a

@@ -19,6 +19,9 @@
 //                      and walks its cluster -> ACCEPTED bitmap
 //   td_special_mark    document bits at both ends of every accepted literal (behind td_mark_docs)
 //   td_special_ids     behind the merge kernels: the literal's pieces -> markers (1 id, then 0 ids)
+//
+// The search's pure logic (the candidate test, the match, the document limit, the cluster walk) is td_special_dev.h, shared with the
+// CPU model tests/twin/special_model.cpp.
 #include <hip/hip_runtime.h>
 
 #include "td_kernels.h"
@@ -29,68 +32,6 @@ namespace {
 
 __device__ __forceinline__ void raise_s(const EncodeArgs& a, int code, int64_t pos) {
     if (atomicCAS(a.err, 0, code) == 0) *a.err_pos = pos;
-}
-
-// first document start in (p, p + span], or p + span
-__device__ __forceinline__ int64_t sp_doc_limit(const EncodeArgs& a, int64_t p, int64_t span) {
-    int64_t lim = p + span < a.n ? p + span : a.n;
-    for (int64_t q = p + 1; q < lim;) {
-        uint32_t m = a.docbits[q >> 5] >> (q & 31);
-        if (m) { const int64_t f = q + (__ffs(m) - 1); return f < lim ? f : lim; }
-        q = ((q >> 5) + 1) << 5;
-    }
-    return lim;
-}
-
-// index of the longest allowed literal that is a prefix of text[p, lim), or -1.  The text at p is taken into registers once
-// (12 dwords: literals are at most SP_MAXLEN bytes), the literals are stored dword-aligned and zero-padded, and a comparison
-// goes a dword at a time in byte order (a byte-by-byte walk through the 40-byte common prefix of a thousand reserved tokens
-// was ~440 dependent loads per match).
-constexpr uint32_t SP_QWORDS = 12;
-__device__ __forceinline__ int sp_match(const SpecialTable& S, const uint8_t* text, int64_t p, int64_t lim) {
-    const int64_t avail64 = lim - p;
-    const uint32_t avail = avail64 > (int64_t)(4 * SP_QWORDS) ? 4 * SP_QWORDS : (uint32_t)avail64;
-    uint32_t Q[SP_QWORDS];
-#pragma unroll
-    for (uint32_t k = 0; k < SP_QWORDS; ++k) {
-        uint32_t w = 0;
-#pragma unroll
-        for (uint32_t j = 0; j < 4; ++j)
-            if (4 * k + j < avail) w |= (uint32_t)text[p + 4 * k + j] << (24 - 8 * j);  // (byte order: a dword compare is a memcmp)
-        Q[k] = w;
-    }
-    // literal i <= Q ?  (prefix: the literal is a prefix of Q)
-    auto le = [&](int i, bool& prefix) {
-        const uint32_t o = S.off[i], len = S.len[i];
-        const uint32_t* lw = reinterpret_cast<const uint32_t*>(S.bytes + o);
-        prefix = false;
-        bool decided = false, res = false;
-#pragma unroll
-        for (uint32_t k = 0; k < SP_QWORDS; ++k) {
-            if (!decided && 4 * k < len) {
-                const uint32_t nb = len - 4 * k < 4u ? len - 4 * k : 4u;           // literal bytes in this dword
-                const uint32_t mask = nb == 4u ? 0xFFFFFFFFu : ~(0xFFFFFFFFu >> (8 * nb));
-                const uint32_t x = __builtin_bswap32(lw[k]) & mask, y = Q[k] & mask;
-                if (x != y) { decided = true; res = x < y; }
-                else if (4 * k + nb > avail) { decided = true; res = false; }      // Q ends inside the literal (its bytes read as 0): the literal is greater
-            }
-        }
-        if (!decided) { prefix = len <= avail; return prefix; }
-        // equal bytes up to a difference: when the difference lies behind the end of Q the literal is the greater one
-        return res;
-    };
-    int lo = -1, hi = (int)S.n;  // literal[lo] <= Q < literal[hi]
-    bool pre = false, lo_pre = false;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (le(mid, pre)) { lo = mid; lo_pre = pre; } else hi = mid;
-    }
-    int i = lo;
-    while (i >= 0 && !lo_pre) {  // up the chain of prefixes: everything in [longest prefix literal, Q] starts with it
-        i = S.parent[i];
-        if (i >= 0) (void)le(i, lo_pre);
-    }
-    return i;
 }
 
 }  // namespace
@@ -131,20 +72,9 @@ __global__ __launch_bounds__(256) void td_special_scan(const EncodeArgs a) {
                 tw[0] = v0.x; tw[1] = v0.y; tw[2] = v0.z; tw[3] = v0.w; tw[4] = v1.x; tw[5] = v1.y; tw[6] = v1.z; tw[7] = v1.w;
                 tw[8] = a.text[p0 + 32];
             } else {
-#pragma unroll
-                for (int k = 0; k < 9; ++k) {
-                    uint32_t x = 0;
-                    for (int j = 0; j < 4; ++j)
-                        if (p0 + 4 * k + j < a.n) x |= (uint32_t)a.text[p0 + 4 * k + j] << (8 * j);
-                    tw[k] = x;
-                }
+                sp_words_bytewise(a.text, a.n, p0, tw);
             }
-#pragma unroll
-            for (int k = 0; k < 32; ++k) {
-                const uint32_t b0 = (tw[k >> 2] >> (8 * (k & 3))) & 0xFFu, b1 = (tw[(k + 1) >> 2] >> (8 * ((k + 1) & 3))) & 0xFFu;
-                const uint32_t key = (b0 << 8) | b1;
-                if (p0 + k < a.n && ((s_first2[key >> 5] >> (key & 31)) & 1u)) cand |= 1u << k;
-            }
+            cand = sp_word_candidates(tw, s_first2, p0, a.n);
             a.sp.hitbits[w] = 0;
             a.sp.accbits[w] = 0;
         }
@@ -154,7 +84,7 @@ __global__ __launch_bounds__(256) void td_special_scan(const EncodeArgs a) {
         const uint32_t cnt = __popc(cand);
         uint32_t at = cnt ? atomicAdd(&s_nc, cnt) : 0u;
         for (uint32_t m = cand; m; m &= m - 1u) {
-            const int64_t cp = p0 + (__ffs(m) - 1);
+            const int64_t cp = p0 + sp_low_bit(m);
             if (at < (uint32_t)SP_LCAP) {
                 s_cpos[at] = cp;
             } else {  // (text that is mostly candidates: what the LDS list cannot take goes to the global list one by one)
@@ -177,7 +107,7 @@ __global__ __launch_bounds__(256) void td_special_match(const EncodeArgs a) {
     const uint32_t nc = *a.sp.cand_count < a.sp.cand_cap ? *a.sp.cand_count : a.sp.cand_cap;
     for (uint32_t j = blockIdx.x * blockDim.x + threadIdx.x; j < nc; j += gridDim.x * blockDim.x) {
         const int64_t p = a.sp.cand_pos[j];
-        const int i = sp_match(a.sp, a.text, p, sp_doc_limit(a, p, a.sp.maxlen));
+        const int i = sp_match(a.sp, a.text, p, sp_doc_limit(a.docbits, a.n, p, a.sp.maxlen));
         a.sp.cand_lit[j] = i;
         if (i >= 0) atomicOr(&a.sp.hitbits[p >> 5], 1u << (p & 31));
     }
@@ -187,39 +117,14 @@ __global__ __launch_bounds__(256) void td_special_match(const EncodeArgs a) {
 // so a hit without another one in the maxlen - 1 bytes in front of it is accepted for sure; its lane walks its cluster
 __global__ __launch_bounds__(256) void td_special_accept(const EncodeArgs a) {
     const uint32_t nc = *a.sp.cand_count < a.sp.cand_cap ? *a.sp.cand_count : a.sp.cand_cap;
-    const int64_t back = (int64_t)a.sp.maxlen - 1;  // a literal that starts further back ends in front of the hit
-    auto next_hit = [&](int64_t q, int64_t lim) {  // first hit in [q, lim), or lim
-        while (q < lim) {
-            const uint32_t m = a.sp.hitbits[q >> 5] >> (q & 31);
-            if (m) { const int64_t f = q + (__ffs(m) - 1); return f < lim ? f : lim; }
-            q = ((q >> 5) + 1) << 5;
-        }
-        return lim;
-    };
     for (uint32_t j = blockIdx.x * blockDim.x + threadIdx.x; j < nc; j += gridDim.x * blockDim.x) {
-        int i = a.sp.cand_lit[j];
+        const int i = a.sp.cand_lit[j];
         if (i < 0) continue;
         const int64_t p = a.sp.cand_pos[j];
-        const int64_t lo = p - back > 0 ? p - back : 0;
-        if (next_hit(lo, p) < p) continue;  // not the head of its cluster: the head's lane gets here
-        int64_t cur = p;
-        for (;;) {  // cur is accepted, i its literal
-            atomicOr(&a.sp.accbits[cur >> 5], 1u << (cur & 31));
-            const int64_t end = cur + (int64_t)a.sp.len[i];
-            // hits inside the literal are dropped; the next one at or behind its end is accepted if it belongs to this cluster
-            int64_t last = cur, q = cur + 1;
-            bool more = false;
-            for (;;) {
-                const int64_t lim = last + back + 1 < a.n ? last + back + 1 : a.n;
-                const int64_t f = next_hit(q, lim);
-                if (f >= lim) break;  // the cluster ends: the next hit is a head of its own
-                last = f;
-                if (f >= end) { cur = f; more = true; break; }
-                q = f + 1;
-            }
-            if (!more) break;
-            i = sp_match(a.sp, a.text, cur, sp_doc_limit(a, cur, a.sp.maxlen));
-        }
+        if (!sp_is_head(a.sp, p)) continue;  // not the head of its cluster: the head's lane gets here
+        sp_cluster_walk(
+            a.sp, a.n, p, i, [&](int64_t cur) { atomicOr(&a.sp.accbits[cur >> 5], 1u << (cur & 31)); },
+            [&](int64_t cur) { return sp_match(a.sp, a.text, cur, sp_doc_limit(a.docbits, a.n, cur, a.sp.maxlen)); });
     }
 }
 
