@@ -488,6 +488,112 @@ int td_encode_batch_select(td_tokenizer* t, const uint8_t* text, const int64_t* 
                            const int64_t* sel, int64_t n_sel, const td_select_spec* spec, int32_t* out_ids, int64_t ids_capacity,
                            int64_t* out_offsets, int64_t* out_docs, int64_t* counts);
 
+/* ---- field joins: one example from several encoded fields (td_join.hip) --------------------------------------------------------
+ * Fine-tuning data is several fields an example: prompt + completion, prompt + chosen / rejected, query + passage, chat turns.
+ * Each field is a DOCUMENT of the stream; this call puts the K fields of an example into one output document, with literal ids
+ * (the template: BOS, header markers, SEP, EOS) between them, per-field and per-example truncation, and a label and a type stream
+ * written in the same pass.  The output is again ids + tok_offsets (+ labels, + types): it feeds the labeled row calls, the
+ * selection, the counts and the n-gram matches unchanged.  Field text encoded with no special token allowed cannot spoof the
+ * template, because the template never passes through text.
+ *   Input.  K = spec.n_fields, 1 <= K <= TD_JOIN_MAX_FIELDS.  n_docs must be a multiple of K, n_ex = n_docs / K.  Field f of
+ *   example x is document x * K + f; under TD_JOIN_FIELD_MAJOR it is document f * n_ex + x (two separately held batches, their
+ *   buffers concatenated).  L_f = that document's length.
+ *   Per field (td_join_field): before[n_before], 0 .. TD_JOIN_MAX_LITERAL literal ids written in front of the field's body;
+ *   max_len, -1 or a cap >= 0 on the body; shrink_rank, 0 = never cut for the total, > 0 = may be cut; type_value, any int32;
+ *   flags: TD_JOIN_KEEP_TAIL (a cut body keeps its LAST ids), TD_JOIN_TRAIN (body slots are trained), TD_JOIN_TRAIN_BEFORE (the
+ *   field's literal slots are trained).
+ *   Per spec: tail[n_tail], 0 .. 16 literal ids behind the last field; tail_type; max_total, -1 or >= 0; shrink, TD_JOIN_SHRINK_ORDER
+ *   or TD_JOIN_SHRINK_LONGEST; ignore_index, any int32; flags: TD_JOIN_FIELD_MAJOR, TD_JOIN_TRAIN_TAIL.  Every literal id must be
+ *   an id of the vocabulary, ordinary or special (else TD_E_BAD_TOKEN): the rule of bos_id / eos_id.
+ *   Kept lengths c_f of one example, in this order:
+ *     1. c_f = L_f, or min(L_f, max_len_f) where a cap is set.
+ *     2. fixed = sum n_before_f + n_tail, need = fixed + sum c_f.  max_total < 0 or need <= max_total: the lengths are final.
+ *     3. over = need - max_total.
+ *        TD_JOIN_SHRINK_ORDER: the fields with shrink_rank > 0 by ascending rank, equal ranks by ascending field index; for each,
+ *          cut = min(c_f, over), c_f -= cut, over -= cut.
+ *        TD_JOIN_SHRINK_LONGEST: `over` times, one id is taken from the field with the largest c_f among those with shrink_rank > 0
+ *          and c_f > 0, a tie going to the HIGHEST field index (Hugging Face's longest_first, which pops from the second of a tied
+ *          pair); each step lowers `over` by one; it stops when no such field is left.  (Computed in closed form.)
+ *     4. over > 0 still: the example does not fit and is DROPPED.  Otherwise it is kept, and it is TRUNCATED if any c_f < L_f.
+ *   Output for the kept examples x_0 < ... < x_{E-1}:
+ *     out ids of an example = before_0 body_0 before_1 body_1 ... before_{K-1} body_{K-1} tail, body_f = the first c_f ids of the
+ *       field, or its last c_f under TD_JOIN_KEEP_TAIL                        int32, room for ids_capacity, T written
+ *     offsets[E + 1], offsets[0] = 0                                          int64, room for n_ex + 1
+ *     examples[E] = x_k                                                       int64, room for n_ex; may be NULL
+ *     labels: the slot's id where its part is trained, ignore_index elsewhere  int32, as ids; may be NULL
+ *     types: the field's type_value on its literals and body, tail_type on the tail   int32, as ids; may be NULL
+ *     field_len[E * K] = the kept c_f (saturating at 2^31 - 1)                int32, room for n_ex * K; may be NULL
+ *     counts[4] (int64) = {E, T = offsets[E], examples dropped, examples truncated}; [0] + [2] = n_ex.
+ *     An example whose every part is empty is kept as an empty output document.
+ *   Errors, by the rules of the selection and the row calls:
+ *     before any launch, TD_E_INVALID with a message: a bad spec (K out of range, literal counts out of range, max_len < -1,
+ *       max_total < -1, shrink_rank < 0, unknown shrink or flags, a value outside int32 where int32 is meant), n_docs % K != 0,
+ *       ids of the output overlapping the input ids;
+ *     offsets of a document that are not 0 <= lo <= hi <= n_tokens: TD_E_INVALID with position = the example.  No id outside
+ *       [0, n_tokens) is ever read;
+ *     T > ids_capacity: TD_E_CAPACITY with counts[1] = T.
+ *   On any error nothing is written to any output but counts. */
+#define TD_JOIN_MAX_FIELDS 8
+#define TD_JOIN_MAX_LITERAL 16
+#define TD_JOIN_KEEP_TAIL 1    /* td_join_field.flags */
+#define TD_JOIN_TRAIN 2
+#define TD_JOIN_TRAIN_BEFORE 4
+#define TD_JOIN_FIELD_MAJOR 1  /* td_join_spec.flags */
+#define TD_JOIN_TRAIN_TAIL 2
+#define TD_JOIN_SHRINK_ORDER 0 /* td_join_spec.shrink */
+#define TD_JOIN_SHRINK_LONGEST 1
+typedef struct td_join_field {
+    int64_t before[TD_JOIN_MAX_LITERAL];
+    int64_t n_before;
+    int64_t max_len;     /* -1: no cap */
+    int64_t shrink_rank; /* 0: never cut for max_total */
+    int64_t type_value;  /* int32 */
+    int64_t flags;
+} td_join_field;
+typedef struct td_join_spec {
+    int64_t n_fields;
+    td_join_field fields[TD_JOIN_MAX_FIELDS];
+    int64_t tail[TD_JOIN_MAX_LITERAL];
+    int64_t n_tail;
+    int64_t tail_type;    /* int32 */
+    int64_t max_total;    /* -1: no limit */
+    int64_t shrink;
+    int64_t ignore_index; /* int32 */
+    int64_t flags;
+} td_join_spec;
+/* Where a join writes: host pointers for td_join_fields / td_encode_batch_join, device pointers for td_join_fields_device. */
+typedef struct td_join_outputs {
+    void* ids;            /* int32[ids_capacity] */
+    void* labels;         /* int32[ids_capacity] or NULL */
+    void* types;          /* int32[ids_capacity] or NULL */
+    int64_t ids_capacity;
+    void* offsets;        /* int64[n_ex + 1] */
+    void* examples;       /* int64[n_ex] or NULL */
+    void* field_len;      /* int32[n_ex * K] or NULL */
+} td_join_outputs;
+
+/* The contract's executable statement, on the host, from tok_offsets and the spec alone (no handle, no device, so literal ids
+ * are not looked up): counts, and out_offsets [n_ex + 1], out_examples [n_ex] and out_field_len [n_ex * K] where not NULL.  It
+ * runs the truncation rule the kernels run.  Argument errors (NULL tok_offsets / spec / counts, a bad spec, n_docs % K != 0) are
+ * TD_E_INVALID with counts[0] = -1; offsets of an example's document that are negative, decrease or exceed 2^59 are TD_E_INVALID
+ * with counts[0] = the example.  Nothing else is written then. */
+int td_join_plan(const int64_t* tok_offsets, int64_t n_docs, const td_join_spec* spec, int64_t* counts, int64_t* out_offsets,
+                 int64_t* out_examples, int32_t* out_field_len);
+/* DEVICE buffers, asynchronously on hip_stream: no synchronisation and no read-back.  d_counts (4 int64) is device memory.
+ * Errors surface through td_device_status: TD_E_INVALID with err_pos = the example, TD_E_CAPACITY with err_pos = T (and
+ * counts[1] = T). */
+int td_join_fields_device(td_tokenizer* t, const void* d_ids, int64_t n_tokens, const void* d_tok_offsets, int64_t n_docs,
+                          const td_join_spec* spec, const td_join_outputs* d_out, void* d_counts, void* hip_stream);
+/* Host buffers, synchronously.  tok_offsets is checked like every host entry point's offsets.  The plan is known on the host:
+ * a capacity below T fails before any launch. */
+int td_join_fields(td_tokenizer* t, const int32_t* ids, int64_t n_tokens, const int64_t* tok_offsets, int64_t n_docs,
+                   const td_join_spec* spec, const td_join_outputs* out, int64_t* counts);
+/* td_encode_batch (TD_MODE_ENCODE / TD_MODE_ORDINARY, no allowed special tokens) and td_join_fields in one call: the ids stay
+ * in the workspace between the two.  Field text cannot spoof the template: a field that contains the literal string of a
+ * special token comes out as that string's ordinary ids, while the template's special arrives as its id.  Synchronous. */
+int td_encode_batch_join(td_tokenizer* t, const uint8_t* text, const int64_t* doc_offsets, int64_t n_docs, int mode,
+                         const td_join_spec* spec, const td_join_outputs* out, int64_t* counts);
+
 /* ---- loss labels: train only inside marked id spans (td_labels.hip) ----------------------------------------------------------
  * ids + per-document token offsets -> labels[i] = ids[i] where the loss applies, ignore_index everywhere else.  The rule knows
  * no chat template: a span is opened by an opener id SEQUENCE (e.g. the three ids of <|header_start|>assistant<|header_end|>)

@@ -72,6 +72,7 @@ EXPORTS = [
     "td_make_rows_labeled", "td_make_rows_labeled_device", "td_pack_rows_labeled", "td_pack_rows_labeled_device",
     "td_window_rows_labeled", "td_window_rows_labeled_device", "td_encode_batch_span_label_rows",
     "td_select_plan", "td_select_docs", "td_select_docs_device", "td_encode_batch_select",
+    "td_join_plan", "td_join_fields", "td_join_fields_device", "td_encode_batch_join",
     "td_range_plan", "td_range_labels", "td_range_labels_device", "td_encode_batch_range_labels", "td_encode_batch_range_label_rows",
     "td_token_counts_host", "td_token_counts", "td_token_counts_device", "td_encode_batch_token_counts",
     "td_decode_rows_check", "td_decode_rows", "td_decode_rows_device",
@@ -176,6 +177,14 @@ def load_library():
     lib.td_select_docs.argtypes = [vp, vp, vp, i64, vp, i64, vp, i64, vp, vp, vp, i64, vp, vp, vp]
     lib.td_encode_batch_select.restype = i32
     lib.td_encode_batch_select.argtypes = [vp, vp, vp, i64, i32, vp, i64, vp, vp, i64, vp, vp, vp]
+    lib.td_join_plan.restype = i32
+    lib.td_join_plan.argtypes = [vp, i64, vp, vp, vp, vp, vp]
+    lib.td_join_fields_device.restype = i32
+    lib.td_join_fields_device.argtypes = [vp, vp, i64, vp, i64, vp, vp, vp, vp]
+    lib.td_join_fields.restype = i32
+    lib.td_join_fields.argtypes = [vp, vp, i64, vp, i64, vp, vp, vp]
+    lib.td_encode_batch_join.restype = i32
+    lib.td_encode_batch_join.argtypes = [vp, vp, vp, i64, i32, vp, vp, vp]
     lib.td_range_plan.restype = i32
     lib.td_range_plan.argtypes = [vp, vp, i64, vp, vp, ctypes.POINTER(i64)]
     lib.td_range_labels_device.restype = i32
@@ -450,6 +459,94 @@ def select_plan(tok_offsets, sel=None, spec: SelectSpec | None = None, outputs: 
         raise ex
     k = int(counts[0])
     return (counts, offs[:k + 1], docs[:k]) if outputs else counts
+
+
+TD_JOIN_MAX_FIELDS, TD_JOIN_MAX_LITERAL = 8, 16
+TD_JOIN_KEEP_TAIL, TD_JOIN_TRAIN, TD_JOIN_TRAIN_BEFORE = 1, 2, 4  # td_join_field.flags
+TD_JOIN_FIELD_MAJOR, TD_JOIN_TRAIN_TAIL = 1, 2                    # td_join_spec.flags
+TD_JOIN_SHRINK_ORDER, TD_JOIN_SHRINK_LONGEST = 0, 1
+
+
+class JoinField(ctypes.Structure):
+    """td_join_field (include/tokendagger_hip.h)."""
+    _fields_ = [("before", ctypes.c_int64 * TD_JOIN_MAX_LITERAL), ("n_before", ctypes.c_int64), ("max_len", ctypes.c_int64),
+                ("shrink_rank", ctypes.c_int64), ("type_value", ctypes.c_int64), ("flags", ctypes.c_int64)]
+
+
+class JoinSpec(ctypes.Structure):
+    """td_join_spec (include/tokendagger_hip.h)."""
+    _fields_ = [("n_fields", ctypes.c_int64), ("fields", JoinField * TD_JOIN_MAX_FIELDS), ("tail", ctypes.c_int64 * TD_JOIN_MAX_LITERAL),
+                ("n_tail", ctypes.c_int64), ("tail_type", ctypes.c_int64), ("max_total", ctypes.c_int64), ("shrink", ctypes.c_int64),
+                ("ignore_index", ctypes.c_int64), ("flags", ctypes.c_int64)]
+
+
+class JoinOutputs(ctypes.Structure):
+    """td_join_outputs (include/tokendagger_hip.h): host or device addresses."""
+    _fields_ = [("ids", ctypes.c_void_p), ("labels", ctypes.c_void_p), ("types", ctypes.c_void_p), ("ids_capacity", ctypes.c_int64),
+                ("offsets", ctypes.c_void_p), ("examples", ctypes.c_void_p), ("field_len", ctypes.c_void_p)]
+
+
+def join_field(before=(), max_len: int | None = None, shrink_rank: int = 0, type_value: int = 0, keep_tail: bool = False,
+               train: bool = False, train_before: bool = False, flags: int | None = None) -> dict:
+    """One field of a join_spec: literal ids in front of the body, the body's cap, its rank in the cut for max_total (0: never
+    cut), its type value, and what is trained.  flags, where given, replaces the three booleans."""
+    fl = flags if flags is not None else (TD_JOIN_KEEP_TAIL * keep_tail | TD_JOIN_TRAIN * train | TD_JOIN_TRAIN_BEFORE * train_before)
+    return {"before": [int(x) for x in before], "max_len": -1 if max_len is None else int(max_len), "shrink_rank": int(shrink_rank),
+            "type_value": int(type_value), "flags": int(fl)}
+
+
+def join_spec(fields, tail=(), tail_type: int = 0, train_tail: bool = False, max_total: int | None = None,
+              shrink: int | str = TD_JOIN_SHRINK_ORDER, field_major: bool = False, ignore_index: int = -100, flags: int | None = None,
+              n_fields: int | None = None) -> JoinSpec:
+    """td_join_spec from join_field(...) dicts.  shrink: TD_JOIN_SHRINK_ORDER / "order" or TD_JOIN_SHRINK_LONGEST / "longest".
+    Counts that the structure cannot hold raise ValueError; everything else is left to the library's checks (flags and n_fields,
+    where given, are passed as they are)."""
+    fields = list(fields)
+    tail = [int(x) for x in tail]
+    if len(fields) > TD_JOIN_MAX_FIELDS or len(tail) > TD_JOIN_MAX_LITERAL or any(len(f["before"]) > TD_JOIN_MAX_LITERAL for f in fields):
+        raise ValueError("a join has at most 8 fields and 16 literal ids a place")
+    sp = JoinSpec()
+    sp.n_fields = len(fields) if n_fields is None else n_fields
+    for i, f in enumerate(fields):
+        for q, x in enumerate(f["before"]):
+            sp.fields[i].before[q] = x
+        sp.fields[i].n_before = f.get("n_before", len(f["before"]))
+        sp.fields[i].max_len, sp.fields[i].shrink_rank = f["max_len"], f["shrink_rank"]
+        sp.fields[i].type_value, sp.fields[i].flags = f["type_value"], f["flags"]
+    for q, x in enumerate(tail):
+        sp.tail[q] = x
+    sp.n_tail, sp.tail_type = len(tail), tail_type
+    sp.max_total = -1 if max_total is None else max_total
+    sp.shrink = {"order": TD_JOIN_SHRINK_ORDER, "longest": TD_JOIN_SHRINK_LONGEST}.get(shrink, shrink)
+    sp.ignore_index = ignore_index
+    sp.flags = flags if flags is not None else (TD_JOIN_FIELD_MAJOR * field_major | TD_JOIN_TRAIN_TAIL * train_tail)
+    return sp
+
+
+def join_plan(tok_offsets, spec: JoinSpec, outputs: bool = True):
+    """td_join_plan (host only, no device): counts int64[4] = kept examples E, kept slots T, examples dropped, examples truncated;
+    with outputs=True also out_offsets int64[E + 1], out_examples int64[E] and out_field_len int32[E, K].  An error carries
+    .counts ([0]: the example with bad offsets, -1 for an argument error)."""
+    lib = load_library()
+    o = np.ascontiguousarray(tok_offsets, dtype=np.int64)
+    n_docs = len(o) - 1
+    if n_docs < 0:
+        raise ValueError("tok_offsets must have n_docs + 1 entries")
+    K = max(int(spec.n_fields), 1)
+    n_ex = n_docs // K
+    counts = np.zeros(4, dtype=np.int64)
+    offs = np.empty(n_ex + 1, dtype=np.int64) if outputs else None
+    exs = np.empty(max(n_ex, 1), dtype=np.int64) if outputs else None
+    flen = np.empty(max(n_ex, 1) * K, dtype=np.int32) if outputs else None
+    rc = lib.td_join_plan(o.ctypes.data, n_docs, ctypes.byref(spec), counts.ctypes.data, offs.ctypes.data if outputs else None,
+                          exs.ctypes.data if outputs else None, flen.ctypes.data if outputs else None)
+    if rc != TD_OK:
+        ex = TokenDaggerHipError(rc, "td_join_plan: invalid spec or arguments" if counts[0] < 0 else
+                                 f"td_join_plan: example {int(counts[0])} has a document without valid offsets")
+        ex.counts = counts
+        raise ex
+    e = int(counts[0])
+    return (counts, offs[:e + 1], exs[:e], flen[:e * K].reshape(e, K)) if outputs else counts
 
 
 TD_DECODE_KEEP_STOP, TD_DECODE_SKIP_NEGATIVE, TD_DECODE_SKIP_SPECIAL = 1, 2, 4
@@ -1457,6 +1554,70 @@ class HipTokenizer:
         self._check_counts(rc, counts)
         k, n = int(counts[0]), int(counts[1])
         return out[:n], o_out[:k + 1], (dcs[:k] if docs else None), counts
+
+    # ---- field joins (td_join_spec) ---------------------------------------------------------------------------
+    @staticmethod
+    def _join_buffers(cap: int, n_ex: int, K: int, labels: bool, types: bool, examples: bool, field_len: bool):
+        b = {"ids": np.empty(max(cap, 1), dtype=np.int32),
+             "labels": np.empty(max(cap, 1), dtype=np.int32) if labels else None,
+             "types": np.empty(max(cap, 1), dtype=np.int32) if types else None,
+             "offsets": np.empty(n_ex + 1, dtype=np.int64),
+             "examples": np.empty(max(n_ex, 1), dtype=np.int64) if examples else None,
+             "field_len": np.empty(max(n_ex, 1) * K, dtype=np.int32) if field_len else None}
+        p = lambda a: a.ctypes.data if a is not None else None
+        return b, JoinOutputs(p(b["ids"]), p(b["labels"]), p(b["types"]), cap, p(b["offsets"]), p(b["examples"]), p(b["field_len"]))
+
+    @staticmethod
+    def _join_result(b, counts, K: int):
+        e, n = int(counts[0]), int(counts[1])
+        cut = lambda a, k: a[:k] if a is not None else None
+        fl = b["field_len"]
+        return (b["ids"][:n], cut(b["labels"], n), cut(b["types"], n), b["offsets"][:e + 1], cut(b["examples"], e),
+                fl[:e * K].reshape(e, K) if fl is not None else None, counts)
+
+    def join_fields(self, ids, tok_offsets, spec: JoinSpec, labels: bool = True, types: bool = False, examples: bool = True,
+                    field_len: bool = False, ids_capacity: int | None = None):
+        """td_join_fields -> (ids int32[T], labels int32[T] | None, types int32[T] | None, offsets int64[E + 1], examples int64[E] |
+        None, field_len int32[E, K] | None, counts int64[4]).  The default capacity is the exact T (td_join_plan).  An error carries
+        .counts (TD_E_CAPACITY: counts[1] = the ids needed)."""
+        t = np.ascontiguousarray(ids, dtype=np.int32)
+        o = np.ascontiguousarray(tok_offsets, dtype=np.int64)
+        n_docs = len(o) - 1
+        K = max(int(spec.n_fields), 1)
+        cap = ids_capacity if ids_capacity is not None else int(join_plan(o, spec, outputs=False)[1])
+        b, outs = self._join_buffers(cap, n_docs // K, K, labels, types, examples, field_len)
+        counts = np.zeros(4, dtype=np.int64)
+        rc = self._lib.td_join_fields(self._h, t.ctypes.data if len(t) else None, len(t), o.ctypes.data, n_docs, ctypes.byref(spec),
+                                      ctypes.byref(outs), counts.ctypes.data)
+        self._check_counts(rc, counts)
+        return self._join_result(b, counts, K)
+
+    def join_fields_device(self, d_ids: int, n_tokens: int, d_tok_offsets: int, n_docs: int, spec: JoinSpec, d_out_ids: int,
+                           ids_capacity: int, d_out_offsets: int, d_counts: int, d_out_labels: int = 0, d_out_types: int = 0,
+                           d_out_examples: int = 0, d_out_field_len: int = 0, stream: int = 0):
+        """td_join_fields_device: raw device pointers, asynchronous on `stream`; check with device_status(stream)."""
+        outs = JoinOutputs(d_out_ids or None, d_out_labels or None, d_out_types or None, ids_capacity, d_out_offsets or None,
+                           d_out_examples or None, d_out_field_len or None)
+        self._check(self._lib.td_join_fields_device(self._h, d_ids or None, n_tokens, d_tok_offsets, n_docs, ctypes.byref(spec),
+                                                    ctypes.byref(outs), d_counts or None, stream or None))
+
+    def encode_batch_join(self, text, doc_offsets, spec: JoinSpec, mode: int = TD_MODE_ENCODE, labels: bool = True, types: bool = False,
+                          examples: bool = True, field_len: bool = False, ids_capacity: int | None = None):
+        """td_encode_batch_join: encode (no special token allowed) + td_join_fields in one call; the result of join_fields.  The
+        default capacity is the most slots the examples can have (one id per byte, and every literal)."""
+        buf = _as_u8(text)
+        offs = np.ascontiguousarray(doc_offsets, dtype=np.int64)
+        n_docs = len(offs) - 1
+        K = max(int(spec.n_fields), 1)
+        n_ex = n_docs // K
+        fixed = int(spec.n_tail) + sum(int(spec.fields[f].n_before) for f in range(min(K, TD_JOIN_MAX_FIELDS)))
+        cap = ids_capacity if ids_capacity is not None else (int(offs[-1]) if len(offs) else 0) + max(fixed, 0) * n_ex
+        b, outs = self._join_buffers(cap, n_ex, K, labels, types, examples, field_len)
+        counts = np.zeros(4, dtype=np.int64)
+        rc = self._lib.td_encode_batch_join(self._h, buf.ctypes.data if len(buf) else None, offs.ctypes.data, n_docs, mode,
+                                            ctypes.byref(spec), ctypes.byref(outs), counts.ctypes.data)
+        self._check_counts(rc, counts)
+        return self._join_result(b, counts, K)
 
     # ---- token counts (td_counts_spec) ------------------------------------------------------------------------
     def token_counts(self, ids, tok_offsets=None, groups=None, spec: CountsSpec | None = None, counts=None, n_tokens: int | None = None):

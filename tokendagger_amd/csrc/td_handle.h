@@ -253,6 +253,9 @@ struct td_tokenizer {
     DevBuf win_scan, win_first, win_len, win_docs, win_starts;
     // document selection (td_select.hip): the scan words and src_base, the host entry points' list, offsets and documents on the device
     DevBuf sel_scan, sel_base, sel_in, sel_off, sel_docs;
+    // field joins (td_join.hip): the scan words and the plan records, the host entry points' offsets, examples, field lengths and
+    // types on the device (their ids and labels: rows_out, rows_lab)
+    DevBuf join_scan, join_plan, join_off, join_ex, join_flen, join_types;
     bool rows_last = false;  // the last call launched the rows kernels (the unit of a TD_E_CAPACITY position)
     // loss labels (td_labels.hip): the counts and flags, the document-start bitmap, the tiles' events / states, their trained ids
     // and the lanes' (trained_offsets only); the host entry points' outputs on the device

@@ -112,6 +112,18 @@ class DecodedRows(NamedTuple):
     n_stopped: int       # segments a stop id ended
 
 
+class JoinedFields(NamedTuple):
+    """Examples built from several encoded fields (Tokenizer.join_fields / encode_fields; the contract: include/tokendagger_hip.h,
+    td_join_spec).  ids + offsets (+ labels) feed ids_to_labeled_rows, select_docs and the rest unchanged."""
+    ids: np.ndarray               # int32 [T]: per kept example, before_0 body_0 ... before_{K-1} body_{K-1} tail
+    labels: np.ndarray | None     # int32 [T]: the id where its part is trained, ignore_index elsewhere
+    types: np.ndarray | None      # int32 [T]: the field's type value, the tail's on the tail
+    offsets: np.ndarray           # int64 [E + 1]: example k is ids[offsets[k]:offsets[k + 1]]
+    examples: np.ndarray          # int64 [E]: the input example that output example k is
+    field_len: np.ndarray         # int32 [E, K]: the ids kept of every field
+    counts: np.ndarray            # int64 [4]: kept examples E, kept slots T, examples dropped, examples truncated
+
+
 class TokenDaggerError(Exception):
     """Base exception for TokenDagger errors (reference: wrapper.py:23-25)."""
 
@@ -492,6 +504,77 @@ class Tokenizer:
         except _capi.TokenDaggerHipError as ex:
             raise TokenDaggerError(f"Encoding failed: {ex}")
         return i, o, d
+
+    # ------------------------------------------------------------------ field joins ------------
+    # One example from several encoded fields (prompt + completion, prompt + chosen / rejected, query + passage, chat turns): the
+    # K fields of an example are K documents of the stream, example x's at x * K .. x * K + K - 1 (field_major: field f's at
+    # f * n_ex + x).  `fields` has one dict a field, with the keys (all optional)
+    #   before        literal ids or special-token strings written in front of the body (the template: never passes through text)
+    #   max_len       a cap on the body          shrink_rank   0: never cut for max_total; > 0: cut in ascending rank
+    #   keep_tail     a cut body keeps its END   train         the body is trained       train_before   the literals are trained
+    #   type          the value of the type stream on the field
+    # tail: literals behind the last field.  shrink: "order" (by shrink_rank) or "longest" (Hugging Face's longest_first).  An
+    # example that cannot be cut to max_total is dropped.
+    def _join_literals(self, items) -> list[int]:
+        out = []
+        for x in items:
+            if isinstance(x, str):
+                if x not in self._special_tokens:
+                    raise TokenDaggerError(f"{x!r} is not a special token of this vocabulary")
+                x = self._special_tokens[x]
+            out.append(int(x))
+        return out
+
+    def _join_spec(self, fields, tail, tail_type, train_tail, max_total, shrink, field_major, ignore_index):
+        known = {"before", "max_len", "shrink_rank", "keep_tail", "train", "train_before", "type"}
+        fs = []
+        for f in fields:
+            if set(f) - known:
+                raise TokenDaggerError(f"unknown field keys: {sorted(set(f) - known)}")
+            fs.append(_capi.join_field(self._join_literals(f.get("before", ())), f.get("max_len"), f.get("shrink_rank", 0), f.get("type", 0),
+                                       bool(f.get("keep_tail", False)), bool(f.get("train", False)), bool(f.get("train_before", False))))
+        if shrink not in ("order", "longest"):
+            raise TokenDaggerError('shrink must be "order" or "longest"')
+        try:
+            return _capi.join_spec(fs, self._join_literals(tail), tail_type, train_tail, max_total, shrink, field_major, ignore_index)
+        except ValueError as ex:
+            raise TokenDaggerError(str(ex))
+
+    def join_fields(self, ids: np.ndarray, tok_offsets: np.ndarray, fields, *, tail=(), max_total: int | None = None, shrink: str = "order",
+                    field_major: bool = False, ignore_index: int = -100, labels: bool = True, types: bool = False, tail_type: int = 0,
+                    train_tail: bool = False) -> JoinedFields:
+        """Examples from fields already encoded (int32 ids + int64 per-document token offsets, len(fields) documents an example)."""
+        spec = self._join_spec(fields, tail, tail_type, train_tail, max_total, shrink, field_major, ignore_index)
+        hip = _capi.HipTokenizer.borrow(self._core_bpe.handle())
+        try:
+            return JoinedFields(*hip.join_fields(ids, tok_offsets, spec, labels=labels, types=types, field_len=True))
+        except _capi.TokenDaggerHipError as ex:
+            raise TokenDaggerError(f"Joining fields failed: {ex}")
+
+    def encode_fields(self, texts_per_field, fields, *, offsets=None, tail=(), max_total: int | None = None, shrink: str = "order",
+                      ignore_index: int = -100, labels: bool = True, types: bool = False, tail_type: int = 0, train_tail: bool = False,
+                      ordinary: bool = False) -> JoinedFields:
+        """Encode and join in one call (the ids never leave the device in between).  texts_per_field: len(fields) equally long
+        lists of str / bytes, list f holding field f of every example; or, with offsets=, one bytes / uint8 buffer and its int64
+        document offsets, field-major (field f of example x is document f * n_ex + x).  The text is encoded with no special
+        token allowed: a field that contains the string of a special token gets that string's ordinary ids."""
+        spec = self._join_spec(fields, tail, tail_type, train_tail, max_total, shrink, True, ignore_index)
+        if offsets is None:
+            lists = [list(col) for col in texts_per_field]
+            if len(lists) != len(fields) or len({len(col) for col in lists}) > 1:
+                raise TokenDaggerError("texts_per_field needs one list a field, all equally long")
+            docs = [s.encode("utf-8") if isinstance(s, str) else bytes(s) for col in lists for s in col]
+            buf = np.frombuffer(b"".join(docs), dtype=np.uint8)
+            offs = np.concatenate([[0], np.cumsum([len(d) for d in docs], dtype=np.int64)]).astype(np.int64)
+        else:
+            buf = np.frombuffer(texts_per_field, dtype=np.uint8) if isinstance(texts_per_field, (bytes, bytearray)) else texts_per_field
+            offs = np.asarray(offsets, dtype=np.int64)
+        hip = _capi.HipTokenizer.borrow(self._core_bpe.handle())
+        try:
+            return JoinedFields(*hip.encode_batch_join(buf, offs, spec, mode=MODE_ORDINARY if ordinary else MODE_ENCODE, labels=labels,
+                                                       types=types, field_len=True))
+        except _capi.TokenDaggerHipError as ex:
+            raise TokenDaggerError(f"Encoding failed: {ex}")
 
     # ------------------------------------------------------------------ token counts -----------
     # What is in the ids: counts[g, v] = how often id v occurs in the documents of group g (a source, a language, a split), on the
