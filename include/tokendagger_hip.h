@@ -837,7 +837,7 @@ int td_encode_batch_token_counts(td_tokenizer* t, const uint8_t* text, const int
  * the inputs alone (not of the hash, the table size, TD_OPT_NGRAM_TAG_BITS or the launch shape), and all sums are integer sums:
  * bitwise reproducible.
  * Out of scope: a list of match positions (its order would depend on scheduling), patterns with wildcards, near-duplicate
- * detection, sets that span several devices. */
+ * detection (its signatures: td_minhash* below), sets that span several devices. */
 #define TD_NGRAM_MAX_LEN 64
 #define TD_NGRAM_MAX_LENGTHS 8
 #define TD_NGRAM_ACCUMULATE 1
@@ -886,6 +886,64 @@ int td_ngram_matches(td_tokenizer* t, const td_ngram_set* set, const int32_t* id
 int td_encode_batch_ngram_matches(td_tokenizer* t, const uint8_t* text, const int64_t* doc_offsets, int64_t n_docs, int mode,
                                   const td_ngram_set* set, const td_ngram_spec* spec, int64_t* doc_stats, int64_t* pattern_counts,
                                   int64_t* counts, int64_t* n_tokens_out);
+
+/* ---- MinHash signatures and LSH band keys per document (td_minhash.hip) ----------------------------------------------------------------
+ * What near-duplicate detection needs from the tokenizer's side, without copying the ids to the host: a signature per document over
+ * its id shingles, and optionally the band keys that bucket documents into candidate groups.  Both are a pure function of ONE
+ * document, so they compose across batches, calls and ranks; the clustering, which is global and a matter of policy, is the caller's.
+ * Inputs: ids (int32), tok_offsets[n_docs + 1] (int64: from 0, non-decreasing, ending at or below n_tokens, as for td_ngram_matches*)
+ * and a spec {k, num_perm, seed, bands, rows, flags}.  Per document [a, z) = [tok_offsets[d], tok_offsets[d + 1]), L = z - a:
+ *   SHINGLES     L >= k: the L - k + 1 windows of k consecutive ids; none reaches across a document boundary.  1 <= L < k: ONE
+ *                shingle, the whole document, hashed with its own length L.  L = 0: none.
+ *   SHINGLE HASH 32 bits, x = finish(poly(window), len) with len = k or L: the n-gram matches' window hash, the library's only one.
+ *                poly: h = 0, then h = h * 0x9E3779B1 + id over the window's ids as uint32 bit patterns, modulo 2^32.  finish:
+ *                x = h + len * 0x7FEB352D; x ^= x >> 16; x *= 0x85EBCA6B; x ^= x >> 13; x *= 0xC2B2AE35; x ^= x >> 16.
+ *                The ids are not checked against a vocabulary: label streams (-100 and all) may be sketched.
+ *   PERMUTATIONS mix64(z), the splitmix64 finaliser: z ^= z >> 30; z *= 0xBF58476D1CE4E5B9; z ^= z >> 27; z *= 0x94D049BB133111EB;
+ *                z ^= z >> 31.  With G = 0x9E3779B97F4A7C15 and j in 0 .. num_perm: a_j = mix64(seed + (2j + 1) G) | 1,
+ *                b_j = mix64(seed + (2j + 2) G), h_j(x) = (uint32)((a_j * (uint64)x + b_j) >> 32), arithmetic modulo 2^64:
+ *                multiply-add-shift, strongly universal for 32-bit keys (the strength class of (a x + b) mod p).
+ *                td_minhash_params gives a_j and b_j, so another system can reproduce the family.
+ *   SIGNATURE    sig[d][j] (uint32, [n_docs][num_perm]) = the minimum over d's shingles of h_j(x); 0xFFFFFFFF for a document with no id.
+ *   BAND KEYS    optional (bands >= 1, rows >= 1, bands * rows <= num_perm): key[d][b] (uint64, [n_docs][bands]) = h after
+ *                h = mix64(b + 1), then h = mix64(h ^ sig[d][j]) for j = b * rows .. (b + 1) * rows.  Equal keys in the same band
+ *                mean "candidate pair".  Documents with no id all share their keys: drop them by counts or by their lengths.
+ *   counts[4] (int64) = {shingles hashed, documents with no id, documents of 1 .. k - 1 ids (one short shingle each), 0}
+ * Limits: k in 1 .. TD_NGRAM_MAX_LEN, num_perm in 1 .. TD_MINHASH_MAX_PERM, bands >= 0 (0: no keys; rows is then ignored), flags == 0,
+ * band_keys not NULL when bands >= 1; anything else is TD_E_INVALID with a message, before any launch.
+ * The result is a function of the inputs alone: a minimum does not depend on the order of its operands, so it is bitwise
+ * reproducible whatever the launch shape or the scheduling is.
+ * Out of scope: clustering and keep lists, signatures merged across calls (np.minimum of two does it), weighted or b-bit MinHash,
+ * anything that makes the device decide which duplicate survives. */
+#define TD_MINHASH_MAX_PERM 1024
+typedef struct td_minhash_spec {
+    int64_t k;        /* ids a shingle */
+    int64_t num_perm; /* permutations: the signature's length */
+    uint64_t seed;    /* of the family */
+    int64_t bands;    /* 0: no band keys */
+    int64_t rows;     /* signature entries a band */
+    int64_t flags;    /* 0 */
+} td_minhash_spec;
+/* a[j], b[j] for j in 0 .. num_perm (no handle, no device).  TD_E_INVALID: num_perm outside 1 .. TD_MINHASH_MAX_PERM, a NULL array. */
+int td_minhash_params(uint64_t seed, int64_t num_perm, uint64_t* a, uint64_t* b);
+/* The contract's executable statement, on the host (no handle, no device).  Argument errors (bad offsets, a bad spec, NULL counts,
+ * NULL sig with documents, NULL ids with ids to visit) are TD_E_INVALID and nothing is written. */
+int td_minhash_host(const int32_t* ids, int64_t n_tokens, const int64_t* tok_offsets, int64_t n_docs, const td_minhash_spec* spec,
+                    uint32_t* sig, uint64_t* band_keys, int64_t* counts);
+/* DEVICE buffers, asynchronously on hip_stream: no synchronisation and no read-back; filling d_sig and zeroing d_counts is part of
+ * the launches.  hip_stream is a stream of the caller's, never the null stream (TD_E_INVALID).  d_band_keys and d_counts are 8-byte
+ * aligned, d_sig 4-byte.  Offsets that do not start at 0, decrease, are negative or end above n_tokens raise TD_E_INVALID through
+ * td_device_status with err_pos = the lowest such document, and then NOTHING is written to any output.  The handle keeps the table of
+ * (a_j, b_j) for the last (seed, num_perm): a call with another pair rebuilds it first, by a small kernel on hip_stream. */
+int td_minhash_device(td_tokenizer* t, const void* d_ids, int64_t n_tokens, const void* d_tok_offsets, int64_t n_docs,
+                      const td_minhash_spec* spec, void* d_sig, void* d_band_keys, void* d_counts, void* hip_stream);
+/* Host buffers, synchronously; the offsets are checked like every host entry point's, before any launch. */
+int td_minhash(td_tokenizer* t, const int32_t* ids, int64_t n_tokens, const int64_t* tok_offsets, int64_t n_docs, const td_minhash_spec* spec,
+               uint32_t* sig, uint64_t* band_keys, int64_t* counts);
+/* td_encode_batch (TD_MODE_ENCODE / TD_MODE_ORDINARY, no allowed special tokens) and the signatures in one call: the ids never leave
+ * the device, only sig, band_keys (NULL with bands == 0), counts and *n_tokens_out (the ids made; may be NULL) come back.  Synchronous. */
+int td_encode_batch_minhash(td_tokenizer* t, const uint8_t* text, const int64_t* doc_offsets, int64_t n_docs, int mode,
+                            const td_minhash_spec* spec, uint32_t* sig, uint64_t* band_keys, int64_t* counts, int64_t* n_tokens_out);
 
 /* Options. */
 #define TD_OPT_LONG_POOL_BYTES 1 /* scratch for pieces longer than 64 bytes (default max(64 MiB, 2 x input)) */

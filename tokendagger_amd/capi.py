@@ -46,6 +46,7 @@ TD_COUNTS_ACCUMULATE = 1
 TD_OPT_NGRAM_TAG_BITS = 17
 TD_NGRAM_ACCUMULATE = 1
 TD_NGRAM_MAX_LEN, TD_NGRAM_MAX_LENGTHS = 64, 8
+TD_MINHASH_MAX_PERM = 1024
 TD_NGRAM_INFO = {"patterns": 1, "distinct": 2, "lengths": 3, "max_len": 4, "slots": 5, "max_probe": 6, "device_bytes": 7}
 TD_INFO_DEFERRED_TILES, TD_INFO_FLAGGED_TILES = 9, 10
 TD_INFO_DIRECT_TILES = 11
@@ -78,6 +79,7 @@ EXPORTS = [
     "td_decode_rows_check", "td_decode_rows", "td_decode_rows_device",
     "td_ngram_set_create", "td_ngram_set_destroy", "td_ngram_set_info", "td_ngram_matches_host", "td_ngram_matches_device",
     "td_ngram_matches", "td_encode_batch_ngram_matches",
+    "td_minhash_params", "td_minhash_host", "td_minhash_device", "td_minhash", "td_encode_batch_minhash",
 ]
 
 
@@ -221,6 +223,16 @@ def load_library():
     lib.td_ngram_matches.argtypes = [vp, vp, vp, i64, vp, i64, vp, vp, vp, vp, vp, vp]
     lib.td_encode_batch_ngram_matches.restype = i32
     lib.td_encode_batch_ngram_matches.argtypes = [vp, vp, vp, i64, i32, vp, vp, vp, vp, vp, ctypes.POINTER(i64)]
+    lib.td_minhash_params.restype = i32
+    lib.td_minhash_params.argtypes = [ctypes.c_uint64, i64, vp, vp]
+    lib.td_minhash_host.restype = i32
+    lib.td_minhash_host.argtypes = [vp, i64, vp, i64, vp, vp, vp, vp]
+    lib.td_minhash_device.restype = i32
+    lib.td_minhash_device.argtypes = [vp, vp, i64, vp, i64, vp, vp, vp, vp, vp]
+    lib.td_minhash.restype = i32
+    lib.td_minhash.argtypes = [vp, vp, i64, vp, i64, vp, vp, vp, vp]
+    lib.td_encode_batch_minhash.restype = i32
+    lib.td_encode_batch_minhash.argtypes = [vp, vp, vp, i64, i32, vp, vp, vp, vp, ctypes.POINTER(i64)]
     lib.td_encode_batch_token_counts.restype = i32
     lib.td_encode_batch_token_counts.argtypes = [vp, vp, vp, i64, i32, vp, vp, vp, vp, ctypes.POINTER(i64)]
     lib.td_comm_unique_id.restype = i32
@@ -723,6 +735,58 @@ def ngram_matches_host(sequences, ids, tok_offsets, spec: NgramSpec | None = Non
     if rc != TD_OK:
         raise TokenDaggerHipError(rc, "td_ngram_matches_host: invalid patterns, offsets, spec or arguments")
     return _ngram_result(total, n_docs, cv, lb, ds, pc, counts)
+
+
+class MinhashSpec(ctypes.Structure):
+    """td_minhash_spec (include/tokendagger_hip.h)."""
+    _fields_ = [("k", ctypes.c_int64), ("num_perm", ctypes.c_int64), ("seed", ctypes.c_uint64), ("bands", ctypes.c_int64),
+                ("rows", ctypes.c_int64), ("flags", ctypes.c_int64)]
+
+
+def minhash_spec(k: int = 5, num_perm: int = 128, seed: int = 1, bands: int = 0, rows: int | None = None, flags: int = 0) -> MinhashSpec:
+    """k ids a shingle, num_perm permutations of the family `seed`; bands > 0 asks for band keys of `rows` signature entries each
+    (None: num_perm // bands)."""
+    if rows is None:
+        rows = num_perm // bands if bands > 0 else 0
+    return MinhashSpec(k, num_perm, seed, bands, rows, flags)
+
+
+def minhash_params(seed: int, num_perm: int):
+    """td_minhash_params -> (a uint64[num_perm], b uint64[num_perm]): h_j(x) = (a[j] * x + b[j] mod 2^64) >> 32."""
+    lib = load_library()
+    a, b = np.zeros(max(num_perm, 1), dtype=np.uint64), np.zeros(max(num_perm, 1), dtype=np.uint64)
+    rc = lib.td_minhash_params(seed, num_perm, a.ctypes.data, b.ctypes.data)
+    if rc != TD_OK:
+        raise TokenDaggerHipError(rc, "td_minhash_params: num_perm must be in 1 .. 1024")
+    return a[:num_perm], b[:num_perm]
+
+
+def _minhash_args(ids, tok_offsets, spec: MinhashSpec):
+    """-> (ids int32, offsets int64, n_docs, sig uint32[n_docs, num_perm], keys uint64[n_docs, bands] | None, counts int64[4])"""
+    t = np.ascontiguousarray(ids, dtype=np.int32).reshape(-1)
+    o = np.ascontiguousarray(tok_offsets, dtype=np.int64)
+    n_docs = len(o) - 1
+    return t, o, n_docs, _minhash_outputs(n_docs, spec)
+
+
+def _minhash_outputs(n_docs: int, spec: MinhashSpec):
+    np_, nb = max(int(spec.num_perm), 1), max(int(spec.bands), 0)
+    sig = np.zeros((max(n_docs, 1), np_), dtype=np.uint32)
+    keys = np.zeros((max(n_docs, 1), nb), dtype=np.uint64) if nb > 0 else None
+    return sig, keys, np.zeros(4, dtype=np.int64)
+
+
+def minhash_host(ids, tok_offsets, spec: MinhashSpec | None = None, n_tokens: int | None = None):
+    """td_minhash_host (host only, no device) -> (sig uint32[n_docs, num_perm], band_keys uint64[n_docs, bands] | None, counts int64[4]
+    = shingles hashed, documents with no id, documents of 1 .. k - 1 ids, 0)."""
+    lib = load_library()
+    spec = spec if spec is not None else minhash_spec()
+    t, o, n_docs, (sig, keys, counts) = _minhash_args(ids, tok_offsets, spec)
+    rc = lib.td_minhash_host(t.ctypes.data if len(t) else None, len(t) if n_tokens is None else n_tokens, o.ctypes.data, n_docs,
+                             ctypes.byref(spec), sig.ctypes.data, _ptr(keys), counts.ctypes.data)
+    if rc != TD_OK:
+        raise TokenDaggerHipError(rc, "td_minhash_host: invalid offsets, spec or arguments")
+    return sig[:n_docs], (keys[:n_docs] if keys is not None else None), counts
 
 
 class NgramSet:
@@ -1693,6 +1757,35 @@ class HipTokenizer:
                                                             nset._h, ctypes.byref(spec), _ptr(ds), _ptr(pc), counts.ctypes.data,
                                                             ctypes.byref(total)))
         return (ds[:n_docs] if ds is not None else None), pc, counts, int(total.value)
+
+    # ---- MinHash signatures (td_minhash_spec) -----------------------------------------------------------------------
+    def minhash(self, ids, tok_offsets, spec: MinhashSpec | None = None, n_tokens: int | None = None):
+        """td_minhash -> (sig uint32[n_docs, num_perm], band_keys uint64[n_docs, bands] | None, counts int64[4])."""
+        spec = spec if spec is not None else minhash_spec()
+        t, o, n_docs, (sig, keys, counts) = _minhash_args(ids, tok_offsets, spec)
+        self._check(self._lib.td_minhash(self._h, t.ctypes.data if len(t) else None, len(t) if n_tokens is None else n_tokens, o.ctypes.data,
+                                         n_docs, ctypes.byref(spec), sig.ctypes.data, _ptr(keys), counts.ctypes.data))
+        return sig[:n_docs], (keys[:n_docs] if keys is not None else None), counts
+
+    def minhash_device(self, d_ids: int, n_tokens: int, d_tok_offsets: int, n_docs: int, spec: MinhashSpec, d_sig: int, d_band_keys: int,
+                       d_counts: int, stream: int):
+        """td_minhash_device: raw device pointers (d_band_keys 0 with bands == 0), asynchronous on `stream`, which must not be the
+        null stream; check with device_status(stream)."""
+        self._check(self._lib.td_minhash_device(self._h, d_ids or None, n_tokens, d_tok_offsets or None, n_docs, ctypes.byref(spec),
+                                                d_sig or None, d_band_keys or None, d_counts or None, stream or None))
+
+    def encode_batch_minhash(self, text, doc_offsets, spec: MinhashSpec | None = None, mode: int = TD_MODE_ENCODE):
+        """td_encode_batch_minhash: encode + signatures in one call, the ids stay on the device -> (sig, band_keys | None, counts,
+        n_tokens)."""
+        spec = spec if spec is not None else minhash_spec()
+        buf = _as_u8(text)
+        offs = np.ascontiguousarray(doc_offsets, dtype=np.int64)
+        n_docs = len(offs) - 1
+        sig, keys, counts = _minhash_outputs(n_docs, spec)
+        total = ctypes.c_int64(0)
+        self._check(self._lib.td_encode_batch_minhash(self._h, buf.ctypes.data if len(buf) else None, offs.ctypes.data, n_docs, mode,
+                                                      ctypes.byref(spec), sig.ctypes.data, _ptr(keys), counts.ctypes.data, ctypes.byref(total)))
+        return sig[:n_docs], (keys[:n_docs] if keys is not None else None), counts, int(total.value)
 
     # ---- decode rows (td_decode_spec) ---------------------------------------------------------------------------
     def decode_rows(self, ids, spec: DecodeSpec, tok_offsets=None, lengths=None, n_segs: int | None = None, capacity: int | None = None):

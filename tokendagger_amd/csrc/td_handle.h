@@ -272,6 +272,11 @@ struct td_tokenizer {
     // n-gram matches (td_ngrams.hip): the bad-offsets word, doc_stats where the caller has none; the host entry points' cover, labels,
     // doc_stats, pattern counts and counts on the device
     DevBuf ng_head, ng_stats, ng_cover, ng_labels, ng_doc_stats, ng_pats, ng_counts;
+    // MinHash signatures (td_minhash.hip): the bad-offsets word and the document counts, the permutation table and what it was built
+    // for; the host entry points' signatures, band keys and counts on the device
+    DevBuf mh_head, mh_table, mh_sig, mh_keys, mh_counts;
+    int64_t mh_table_perm = 0;     // 0: no table yet
+    uint64_t mh_table_seed = 0;
     std::vector<int64_t> dcr_key;  // flags, then the distinct listed ids with their bits (sorted); empty: no table yet
     // best-fit packing (td_pack.hip): the items, the sort's and the scan's scratch, the header + runs read back, the plan uploaded,
     // the segments; the host entry points' row lengths and segment documents on the device

@@ -102,6 +102,19 @@ class NgramMatches(NamedTuple):
     counts: np.ndarray                 # int64 [4]: occurrences, covered ids, documents with an occurrence, 0
 
 
+class MinHashes(NamedTuple):
+    """MinHash signatures and LSH band keys per document (Tokenizer.ids_to_minhash / encode_batch_to_minhash; the contract:
+    include/tokendagger_hip.h, td_minhash_spec)."""
+    signatures: np.ndarray        # uint32 [n_docs, num_perm]; all 0xFFFFFFFF for a document with no id
+    band_keys: np.ndarray | None  # uint64 [n_docs, bands]: equal keys in the same band mean "candidate pair"
+    counts: np.ndarray            # int64 [4]: shingles hashed, documents with no id, documents of 1 .. ngram - 1 ids, 0
+
+    def similarity(self, i: int, j: int) -> float:
+        """The fraction of equal signature entries of documents i and j: an unbiased estimate of the Jaccard similarity of their
+        shingle sets, with standard deviation sqrt(J (1 - J) / num_perm)."""
+        return float(np.mean(self.signatures[i] == self.signatures[j]))
+
+
 class DecodedRows(NamedTuple):
     """Tokenizer.decode_rows_to_numpy (the contract: include/tokendagger_hip.h, td_decode_spec)."""
     data: np.ndarray     # uint8: the segments' bytes, concatenated
@@ -691,6 +704,35 @@ class Tokenizer:
         except _capi.TokenDaggerHipError as ex:
             raise TokenDaggerError(f"Encoding failed: {ex}")
         return NgramMatches(None, None, ds, pc, counts), total
+
+    # ------------------------------------------------------------------ MinHash signatures -----
+    # Near-duplicate detection's device half: a signature per document over its shingles of `ngram` ids, and with bands > 0 the LSH
+    # band keys.  Both are a function of one document, so results of different batches, calls and ranks go side by side; grouping the
+    # candidates and choosing the survivors is the caller's (band keys -> np.unique per band -> similarity ->
+    # select_docs).  bands b and rows r make two documents of Jaccard similarity s candidates with probability 1 - (1 - s^r)^b;
+    # the curve's threshold is about (1 / b)^(1 / r).
+    def ids_to_minhash(self, ids: np.ndarray, tok_offsets: np.ndarray, *, ngram: int = 5, num_perm: int = 128, seed: int = 1,
+                       bands: int = 0, rows: int | None = None) -> MinHashes:
+        """MinHash signatures (and band keys) of encoded documents.  rows=None: num_perm // bands.  ids are not checked against the
+        vocabulary: a label stream may be sketched as well."""
+        hip = _capi.HipTokenizer.borrow(self._core_bpe.handle())
+        try:
+            return MinHashes(*hip.minhash(ids, tok_offsets, _capi.minhash_spec(ngram, num_perm, seed, bands, rows)))
+        except _capi.TokenDaggerHipError as ex:
+            raise TokenDaggerError(f"MinHash failed: {ex}")
+
+    def encode_batch_to_minhash(self, text: np.ndarray | bytes, offsets: np.ndarray, *, ngram: int = 5, num_perm: int = 128, seed: int = 1,
+                                bands: int = 0, rows: int | None = None, ordinary: bool = False):
+        """encode_batch_to_numpy and ids_to_minhash in one call: the ids never leave the device -> (MinHashes, the ids made)."""
+        hip = _capi.HipTokenizer.borrow(self._core_bpe.handle())
+        buf = np.frombuffer(text, dtype=np.uint8) if isinstance(text, (bytes, bytearray)) else text
+        try:
+            sig, keys, counts, total = hip.encode_batch_minhash(buf, np.asarray(offsets, dtype=np.int64),
+                                                                _capi.minhash_spec(ngram, num_perm, seed, bands, rows),
+                                                                mode=MODE_ORDINARY if ordinary else MODE_ENCODE)
+        except _capi.TokenDaggerHipError as ex:
+            raise TokenDaggerError(f"Encoding failed: {ex}")
+        return MinHashes(sig, keys, counts), total
 
     # ------------------------------------------------------------------ loss labels ------------
     # labels[i] = ids[i] inside a span, ignore_index elsewhere.  A span starts behind an opener (a string, encoded once with every
