@@ -172,6 +172,10 @@ int td_encode_batch_with_special_strs(td_tokenizer* t, const uint8_t* text, cons
 #define TD_INFO_CHAR_SEEDS 15    /* characters of 2..3 bytes this vocabulary allows to enter the merge of a long piece as one part (td_common.h) */
 #define TD_INFO_SPARSE 16        /* 1: the last td_encode_device call of the handle took the sparse launch sequence (TD_OPT_SPARSE), 0: the dense one */
 #define TD_INFO_WS_FILLED_BYTES 17 /* bytes this handle has filled since it was made (TD_OPT_WS_FILL): at allocation and in front of steps */
+#define TD_INFO_SMALL_ENCODES 18          /* host calls of at most 4 KiB and 1024 documents the one-launch kernel (td_small_encode / td_small_resident) answered itself, an error it reported included, since the handle was made (a td_clone handle starts at 0) */
+#define TD_INFO_SMALL_ENCODE_HANDBACKS 19 /* ... and calls it handed back to the general path (a piece above 1024 bytes, a full list) */
+#define TD_INFO_SMALL_DECODES 20          /* td_decode_bytes calls of at most 1024 ids td_small_decode answered itself, since the handle was made */
+#define TD_INFO_SMALL_DECODE_HANDBACKS 21 /* ... and calls it handed back (more than 16 384 bytes) */
 #define TD_INFO_DIRECT_TILES 11 /* pre-tokenizer tiles (8 KiB) whose ids the fused tile loop wrote straight to the output (TD_OPT_DIRECT), last call */
 int64_t td_info(const td_tokenizer* t, int what);
 

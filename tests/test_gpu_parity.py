@@ -445,7 +445,8 @@ def test_pipelined_host_batches_equal_the_plain_path():
 def test_one_launch_path_for_small_inputs(golden):
     """Inputs of at most 4 KiB take td_small_encode (one launch, pinned host buffers).  Every golden document that fits,
     alone and in small batches with empty documents, against the compiled reference's ids; the same calls with the path
-    switched off give the same answer; pieces above 64 bytes fall back to the general path."""
+    switched off give the same answer; pieces of 65..1024 bytes are merged by the kernel itself, a wavefront each, and only a piece above
+    1024 bytes makes it hand the call back to the general path (tests/test_gpu_small_encode.py asserts which path answered)."""
     from tokendagger_amd import capi
     pat, mr, special = H.llama4()
     tok = capi.HipTokenizer(pat, mr, special, device=0)
@@ -478,7 +479,7 @@ def test_one_launch_path_for_small_inputs(golden):
         assert np.array_equal(tok.encode(doc), gold[go[d]:go[d + 1]])
     tok.set_option(capi.TD_OPT_SMALL_PATH, 1)
     for doc in (b"x" + b" " * 300 + b"y", ("=" * 100 + "\n").encode(), ("的" * 200).encode("utf-8"), b"a" * 4096):
-        assert np.array_equal(tok.encode(doc), O.encode(doc))     # long pieces: handed back to the general path
+        assert np.array_equal(tok.encode(doc), O.encode(doc))     # long pieces: three inside the kernel, the last (4096 bytes) handed back
     toy = capi.HipTokenizer(pat, {b"a": 0, b"b": 1, b"ab": 2}, {}, device=0)
     assert toy.encode(b"abba").tolist() == [2, 1, 0]
     with pytest.raises(capi.TokenDaggerHipError):

@@ -55,6 +55,8 @@ TD_INFO_REPEATS, TD_INFO_LISTED_PIECES, TD_INFO_CHAR_SEEDS = 13, 14, 15
 TD_INFO_SPARSE = 16
 TD_OPT_WS_FILL = 18  # debugging: -1 off, 0..255 the byte every workspace buffer is filled with at allocation and before every step
 TD_INFO_WS_FILLED_BYTES = 17
+# which path answered the handle's small host calls since it was made: the one-launch kernels themselves, or the general path they handed to
+TD_INFO_SMALL_ENCODES, TD_INFO_SMALL_ENCODE_HANDBACKS, TD_INFO_SMALL_DECODES, TD_INFO_SMALL_DECODE_HANDBACKS = 18, 19, 20, 21
 
 EXPORTS = [
     "td_create", "td_clone", "td_destroy", "td_last_error", "td_encode_batch", "td_encode_device", "td_reserve",

@@ -754,7 +754,7 @@ constexpr int64_t SMALL_MAX_BYTES = 4096, SMALL_MAX_DOCS = 1024;
 static_assert(SMALL_MAX_DOCS == SM_MAXDOCS, "td_small_encode keeps the document offsets in LDS");
 constexpr size_t SMALL_IN_BYTES = 64 + (SMALL_MAX_DOCS + 2) * 8 + SMALL_MAX_BYTES + 256;  // (64: td_small_resident's request header)
 constexpr size_t SMALL_OUT_BYTES = 64 + (SMALL_MAX_DOCS + 2) * 8 + SMALL_MAX_BYTES * 4 + 256;
-// returns TD_OK, a TD_E_* code, or -1: the kernel handed the call back (a piece above 64 bytes)
+// returns TD_OK, a TD_E_* code, or -1: the kernel handed the call back (a piece above 1024 bytes); TD_INFO_SMALL_ENCODES / _HANDBACKS count which
 int encode_batch_small(td_tokenizer* t, const uint8_t* text, const int64_t* doc_offsets, int64_t n_docs, int mode,
                        int32_t* out_tokens, int64_t out_capacity, int64_t* out_offsets, int64_t* n_tokens) {
     const int64_t n = doc_offsets[n_docs];
@@ -823,7 +823,8 @@ int encode_batch_small(td_tokenizer* t, const uint8_t* text, const int64_t* doc_
     if ((rc = wait_for_seq(t, seqp, a.seq, s, 0xFFFu, 5, "td_small_encode did not complete"))) return rc;
     }
     const SmallStatus st = *a.status;
-    if (st.fallback) return -1;
+    if (st.fallback) { ++t->small_encode_handbacks; return -1; }
+    ++t->small_encodes;  // (an error the kernel reported is its answer too)
     if (st.err) {
         t->err = st.err == TD_E_UNKNOWN_BYTE ? device_error_text(st.err, st.err_pos, false) : "device error " + std::to_string(st.err);
         return st.err;
@@ -1136,6 +1137,10 @@ int64_t td_info(const td_tokenizer* t, int what) {
         case TD_INFO_CHAR_SEEDS: return (int64_t)t->H.n_char_seeds;
         case TD_INFO_SPARSE: return t->last_sparse ? 1 : 0;
         case TD_INFO_WS_FILLED_BYTES: return t->ws_filled;
+        case TD_INFO_SMALL_ENCODES: return t->small_encodes;
+        case TD_INFO_SMALL_ENCODE_HANDBACKS: return t->small_encode_handbacks;
+        case TD_INFO_SMALL_DECODES: return t->small_decodes;
+        case TD_INFO_SMALL_DECODE_HANDBACKS: return t->small_decode_handbacks;
     }
     return -1;
 }

@@ -52,13 +52,14 @@ int decode_bytes_small(td_tokenizer* t, const int32_t* tokens, int64_t n_tokens,
     HIP_TRY(t, launch_small_decode(a, s));
     if ((rc = wait_for_seq(t, &a.status->seq, a.seq, s, 0xFFFu, 5, "td_small_decode did not complete"))) return rc;
     const SmallStatus st = *a.status;
+    if (!st.err && st.fallback) { ++t->small_decode_handbacks; return -1; }
+    ++t->small_decodes;  // (an error the kernel reported is its answer too)
     if (st.err == TD_E_BAD_TOKEN) {
         const long long ep = st.err_pos;
         t->err = "Invalid token for decoding: " + std::to_string(ep >= 0 && ep < n_tokens ? tokens[ep] : -1);  // reference: tiktoken.cpp:249
         return TD_E_BAD_TOKEN;
     }
     if (st.err) { t->err = "device error " + std::to_string(st.err); return st.err; }
-    if (st.fallback) return -1;
     if (n_bytes) *n_bytes = st.n_tokens;
     if ((int64_t)st.n_tokens > out_capacity) { t->err = "decode capacity too small"; return TD_E_CAPACITY; }
     if (st.n_tokens > 0 && !out) { t->err = "null out"; return TD_E_INVALID; }

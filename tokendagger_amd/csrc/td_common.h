@@ -479,6 +479,16 @@ TD_HD typename A::pos_t scan_piece_gpt2(const A& a, typename A::pos_t pos) {
         const uint32_t c1 = v1 & CLS_MASK;
         if (!(v1 & F_DOC) && (in_set(M_U | M_W, c1) || c1 == C_NUM || in_set(M_X, c1))) { st = pos + 1; cls = c1; }
     }
+#if defined(__HIP_DEVICE_COMPILE__)
+    // (the device compiler kept `cls` only on the apostrophe and blank branches above: for a lane that took neither, run_set was made from a
+    // register nobody had written, and a run that starts at `pos` ended after its first character — td_small_encode, the one kernel that
+    // walks this scanner from every document start, gave "H" + "ello" for "Hello".  Pinning the value in a register here restores it;
+    // tests/test_gpu_small_encode.py holds every family's scanner to the reference through that kernel.
+    // Seen with AMD clang 22.0.0git (roc-7.2.0, HIP 7.2.26015), -O3, gfx950.  The evidence is the ISA of td_small_encode: without this line the
+    // register that holds `cls` is written on the class <= 2 and blank paths only and read on all of them; with it, a move of c0 into it
+    // appears on the remaining path.  Re-check on a toolchain change: if the move is there without the line, the line can go.)
+    asm volatile("" : "+v"(cls));
+#endif
     const uint32_t run_set = in_set(M_U | M_W, cls) ? (M_U | M_W) : (cls == C_NUM) ? (1u << C_NUM) : in_set(M_X, cls) ? M_X : 0u;
     if (run_set) {
         P e = st;

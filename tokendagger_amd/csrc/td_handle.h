@@ -349,6 +349,9 @@ struct td_tokenizer {
     PinnedBuf small_in, small_out;
     PinnedBuf small_dec_in, small_dec_out;  // td_small_decode: ids in, status + bytes out
     unsigned long long small_seq = 0;
+    // which path answered, since the handle was made (TD_INFO_SMALL_*; td_clone's handle starts at 0): calls the one-launch kernels
+    // answered themselves (an error they reported included) and calls they handed back to the general path
+    int64_t small_encodes = 0, small_encode_handbacks = 0, small_decodes = 0, small_decode_handbacks = 0;
     // the resident form of the one-launch kernel (td_small_resident): its own stream, the generation of the last launch
     Stream s_res;
     unsigned long long res_gen = 0;
