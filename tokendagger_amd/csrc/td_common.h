@@ -952,6 +952,90 @@ struct ArrMaskP {
     }
 };
 
+// ---- compact storage of the class masks (the fused tile loop's: nine arrays instead of twelve) ----
+// Three of the twelve masks are functions of stored ones, and one is stored elsewhere already:
+//   MK_N = NRAW & ~X & ~S,  MK_A = NRAW & X,  MK_SP = NRAW & S   (NRAW: feature bit FB_N, set for C_NUM, C_APOS and C_SP)
+//   MK_D = the document bits of the window
+// The nine others are stored MASK-MAJOR: dword j (window bytes 32 j .. 32 j + 31) of stored mask s at arr[s * stride + j], so
+// lanes that take consecutive 32-byte strides read consecutive dwords of one array (word-major, a lane's dwords lie
+// MK_COUNT * 2 apart and four lanes of a wavefront meet in every bank).  The views derive the rest where they are loaded.
+enum : int { CM_U = 0, CM_W, CM_X, CM_S, CM_NRAW, CM_CR, CM_TR, CM_C, CM_SYNC, CM_COUNT };
+// the twelve views (a BitWin or a BitWin32) from the nine stored values s[CM_*] and the document bits d
+template <class V, class W>
+TD_HD void cm_expand(V& v, const W* s, W d) {
+    v.m[MK_U] = s[CM_U]; v.m[MK_W] = s[CM_W]; v.m[MK_X] = s[CM_X]; v.m[MK_S] = s[CM_S];
+    v.m[MK_N] = s[CM_NRAW] & ~(s[CM_X] | s[CM_S]);
+    v.m[MK_CR] = s[CM_CR]; v.m[MK_TR] = s[CM_TR]; v.m[MK_C] = s[CM_C];
+    v.m[MK_D] = d;
+    v.m[MK_A] = s[CM_NRAW] & s[CM_X];
+    v.m[MK_SP] = s[CM_NRAW] & s[CM_S];
+    v.m[MK_SYNC] = s[CM_SYNC];
+}
+// Provider over the compact storage: ArrMaskP's questions, answered from 64-bit words put together from two dwords.  `doc`:
+// the document bits as dwords; both arrays must be readable (and zero) up to the last word the scanner may ask for.
+struct CompactMaskP {
+    const uint32_t* arr;
+    const uint32_t* doc;
+    int stride;  // dwords per stored mask
+    int o, lim;
+    TD_HD CompactMaskP(const uint32_t* a, int stride_, const uint32_t* d, int o_, int lim_) : arr(a), doc(d), stride(stride_), o(o_), lim(lim_) {}
+    TD_HD uint64_t stored(int s, int wi) const { return ((uint64_t)arr[s * stride + 2 * wi + 1] << 32) | arr[s * stride + 2 * wi]; }
+    TD_HD uint64_t dword64(int wi) const { return ((uint64_t)doc[2 * wi + 1] << 32) | doc[2 * wi]; }
+    TD_HD uint64_t word(int k, int wi) const {
+        switch (k) {
+            case MK_U: return stored(CM_U, wi);
+            case MK_W: return stored(CM_W, wi);
+            case MK_X: return stored(CM_X, wi);
+            case MK_S: return stored(CM_S, wi);
+            case MK_N: return stored(CM_NRAW, wi) & ~(stored(CM_X, wi) | stored(CM_S, wi));
+            case MK_CR: return stored(CM_CR, wi);
+            case MK_TR: return stored(CM_TR, wi);
+            case MK_C: return stored(CM_C, wi);
+            case MK_D: return dword64(wi);
+            case MK_A: return stored(CM_NRAW, wi) & stored(CM_X, wi);
+            case MK_SP: return stored(CM_NRAW, wi) & stored(CM_S, wi);
+            default: return stored(CM_SYNC, wi);
+        }
+    }
+    TD_HD uint64_t eword(int wi) const {  // end-of-subject bits after o
+        const int wo = o >> 6;
+        if (wi < wo) return 0;
+        const uint64_t d = dword64(wi);
+        return wi == wo ? d & ~td_bits_below((o & 63) + 1) : d;
+    }
+    TD_HD bool bit(int k, int i) const { return (word(k, i >> 6) >> (i & 63)) & 1ull; }
+    TD_HD bool ebit(int i) const { return i > o && bit(MK_D, i); }
+    template <class F>
+    TD_HD int run_where(const F& f, int from) const {  // first i >= from whose bit in f(word index) & ~end-of-subject is clear
+        int i = from;
+        while (i < lim) {
+            const int wi = i >> 6, sh = i & 63;
+            const uint64_t m = (f(wi) & ~eword(wi)) >> sh;
+            const int t = td_ctz64(~m);
+            if (t < 64 - sh) return i + t;
+            i += 64 - sh;
+        }
+        return i;
+    }
+    TD_HD int run_end(int k, int from) const { return run_where([&](int wi) { return word(k, wi); }, from); }
+    TD_HD int run_end2(int k1, int k2, int from) const { return run_where([&](int wi) { return word(k1, wi) | word(k2, wi); }, from); }
+    template <class F>
+    TD_HD int last_where(const F& f, int lo, int hi) const {  // highest i in [lo,hi) whose bit in f(word index) is set
+        if (hi <= lo) return -1;
+        for (int wi = (hi - 1) >> 6; wi >= (lo >> 6); --wi) {
+            uint64_t m = f(wi);
+            const int base = wi << 6;
+            if (hi - base < 64) m &= td_bits_below(hi - base);
+            if (lo > base) m &= ~td_bits_below(lo - base);
+            if (m) return base + td_top64(m) - 1;
+        }
+        return -1;
+    }
+    TD_HD int last_and(int k1, int k2, int lo, int hi) const { return last_where([&](int wi) { return word(k1, wi) & word(k2, wi); }, lo, hi); }
+    TD_HD int last_set(int k, int lo, int hi) const { return last_where([&](int wi) { return word(k, wi); }, lo, hi); }
+    TD_HD int last_clear(int k, int lo, int hi) const { return last_where([&](int wi) { return ~word(k, wi); }, lo, hi); }
+};
+
 // (?i:'s|'t|'re|'ve|'m|'ll|'d)? on masks; `bytes(i)` returns the raw byte at position i.
 template <class P, class B>
 TD_HD int scan_contraction_p(const P& p, const B& bytes, int e, bool leading = false) {

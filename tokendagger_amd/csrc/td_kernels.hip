@@ -344,9 +344,10 @@ __device__ __forceinline__ uint64_t bits64(const uint32_t* arr, int pos) {
 
 // pieces / look-ahead longer than a 64-byte register window: the same matcher on the mask words in LDS (cold path,
 // kept out of line so that the hot loop stays small)
+constexpr int CM_STRIDE = (K_MWORDS + 1) * 2;  // dwords per stored class mask: the window's words and a zero word behind them
 template <uint32_t PV>
-__device__ __noinline__ int scan_piece_lds(const uint64_t* s_mask, const uint8_t* s_txt, int p) {
-    const ArrMaskP mp(s_mask, p, K_LIM);
+__device__ __noinline__ int scan_piece_lds(const uint32_t* s_cm, const uint32_t* s_doc, const uint8_t* s_txt, int p) {
+    const CompactMaskP mp(s_cm, CM_STRIDE, s_doc, p, K_LIM);
     return scan_piece_p(mp, [s_txt](int q) { return (uint32_t)s_txt[q]; }, PV);
 }
 
@@ -707,7 +708,7 @@ __device__ __forceinline__ void fz_stage_with_misses(const uint32_t* slab, uint3
 #endif
 // PV = the pattern's scanner flags as a compile-time constant: one instantiation per member of the pattern family, so
 // the hot scan loop of the Llama-4 pattern carries no trace of the others (as run-time flags they cost 5 % of it).
-constexpr int KS_HCAP = 768;   // heads the list holds per tile (what does not fit is matched by the lane that found it)
+constexpr int KS_HCAP = 576;   // heads the list holds per tile (what does not fit is matched by the lane that found it; most seen: 448)
 constexpr int KS_CCAP = 128;
 
 // ---- the fused form (FUSED = true) ---------------------------------------------------------------------------------
@@ -727,22 +728,21 @@ constexpr int KS_CCAP = 128;
 // window: the td_split_far_* cases) or hold (more than FZ_NPC pieces) is DEFERRED: its token tiles go on a list, and
 // td_probe_tiles — which otherwise finds nothing to do — looks their pieces up after the far kernels have completed the
 // START bits.  Results are the same slots either way.
-constexpr int FZ_NPC = 5120;         // pieces per tile the LDS list holds (a tile with more: deferred)
+constexpr int FZ_NPC = 4736;         // pieces per tile the LDS list holds (a tile with more: deferred; most seen: 4612)
 #ifndef TD_FZ_PB
 #define TD_FZ_PB 1
 #endif
 constexpr int FZ_PB = TD_FZ_PB;      // lookups a lane has in flight
-constexpr int FZ_R_MASK = (K_MWORDS + 1) * MK_COUNT * 8;  // bytes of the class masks
+constexpr int FZ_R_MASK = CM_STRIDE * CM_COUNT * 4;       // bytes of the stored class masks (nine, mask-major: td_common.h, compact storage)
 constexpr int FZ_R_HEADS = FZ_R_MASK;                     // s_heads behind them
 constexpr int FZ_R_COLD = FZ_R_HEADS + (KS_HCAP + 2) * 2;
 constexpr int FZ_R_SPLIT_END = FZ_R_COLD + KS_CCAP * 2;
 // the same bytes during the token phases
 constexpr int FZ_R_PLIST = 0;                                 // u16[FZ_NPC + 8] piece starts (window positions) + end delimiter
-constexpr int FZ_CCAP = 768;                                  // pieces a tile can put aside for the long route (more: deferred)
+constexpr int FZ_CCAP = 512;                                  // pieces a tile can put aside for the long route (more: deferred; most seen above 12 bytes: 205)
 constexpr int FZ_R_COLDK = ((FZ_NPC + 8) * 2 + 15) & ~15;     // u16[FZ_CCAP] pieces put aside for the long route
 constexpr int FZ_R_PB = FZ_R_COLDK + FZ_CCAP * 2;             // u16[K_THREADS] pieces before each lane's 32 bytes
-constexpr int FZ_R_SM = FZ_R_PB + K_THREADS * 2;              // u32[K_THREADS] START bits of each lane's 32 bytes
-constexpr int FZ_R_TOK_END = FZ_R_SM + K_THREADS * 4;
+constexpr int FZ_R_TOK_END = FZ_R_PB + K_THREADS * 2;         // (the START bits of each lane's 32 bytes stay where they are: s_start)
 static_assert(SLAB_MIDS >= FZ_NPC + 8, "a slab holds the slots of the fullest tile the fused loop takes");
 constexpr int FZ_R_BYTES = ((FZ_R_SPLIT_END > FZ_R_TOK_END ? FZ_R_SPLIT_END : FZ_R_TOK_END) + 15) & ~15;
 // s_pd[ring slot]: a tile whose placement is pending (written by the token phases of iteration i, read by the placement in
@@ -761,18 +761,23 @@ static_assert(SLAB_MAX_MISSES == 2 * K_MISS_LISTED_MAX, "slab layout");
 #define TD_LB_MAX_ROUNDS 4      // ... and rounds of 256 predecessors that all had a count but none a prefix
 #endif
 #ifndef TD_FUSED_MIN_WAVES
-#define TD_FUSED_MIN_WAVES 6  // (256 MiB: English 0.66 ms at 5 and at 6, 0.71 at 4; source code 0.98 / 0.96 / 1.09; mixed-script 1.63 / 1.56 / 1.87)
+#define TD_FUSED_MIN_WAVES 7  // (256 MiB: English 0.66 ms at 5 and at 6, 0.71 at 4; source code 0.98 / 0.96 / 1.09; mixed-script 1.63 / 1.56 / 1.87;
+                              // seven against six on 1024 MiB: DESIGN.md 5.2)
 #endif
 
 // DIRECT (only with FUSED): the loop also places the ids of the tiles whose output base it learns in time (TD_OPT_DIRECT,
 // see "placement" below).  An instantiation of its own: the code it adds (20 KB) and the registers it takes cost the loop
 // 5-7 % even on the tiles that do not use it.
+#ifndef TD_DIRECT_MIN_WAVES
+#define TD_DIRECT_MIN_WAVES 6  // (its own bound: the opt-in direct placement has the ring's LDS and more registers to hold)
+#endif
+static_assert(TD_FUSED_MIN_WAVES < 7 || FZ_R_BYTES <= 11072, "seven workgroups per CU: 22 752 B of LDS each, of which s_R may have 11 072");
 template <uint32_t PV, bool FUSED, bool DIRECT>
-__global__ __launch_bounds__(K_THREADS, FUSED ? TD_FUSED_MIN_WAVES : TD_SPLIT_MIN_WAVES) void td_split_tiles(const EncodeArgs a_kern) {
+__global__ __launch_bounds__(K_THREADS, !FUSED ? TD_SPLIT_MIN_WAVES : DIRECT ? TD_DIRECT_MIN_WAVES : TD_FUSED_MIN_WAVES) void td_split_tiles(const EncodeArgs a_kern) {
     static_assert(FUSED || !DIRECT, "direct placement is part of the fused tile loop");
     __shared__ __attribute__((aligned(16))) uint8_t s_txt[K_WIN];
     __shared__ __attribute__((aligned(16))) uint8_t s_R[FZ_R_BYTES];  // class masks | heads | cold list; FUSED: then piece list | slots
-    uint64_t* const s_mask = reinterpret_cast<uint64_t*>(s_R);       // [(K_MWORDS + 1) * MK_COUNT] class masks, word-major
+    uint32_t* const s_cm = reinterpret_cast<uint32_t*>(s_R);         // [CM_COUNT][CM_STRIDE] stored class masks, mask-major; N, A, SP and D are derived
     uint16_t* const s_heads = reinterpret_cast<uint16_t*>(s_R + FZ_R_HEADS);  // [KS_HCAP + 2] unresolved heads (window positions)
     uint16_t* const s_cold = reinterpret_cast<uint16_t*>(s_R + FZ_R_COLD);    // [KS_CCAP] piece starts the branch-free matcher left open
     __shared__ uint32_t s_start[K_WIN / 32 + 3];  // bit i: a piece starts at window byte i
@@ -808,6 +813,8 @@ __global__ __launch_bounds__(K_THREADS, FUSED ? TD_FUSED_MIN_WAVES : TD_SPLIT_MI
     for (int q = tid; q < 128; q += K_THREADS) s_lut[q] = (uint8_t)feature_of_class(T->ascii_cls[q]);
     if (tid < 16) s_fcls[tid] = (uint8_t)feature_of_class((uint32_t)tid);
     if (tid == 0) s_nonascii = 0;
+    if (tid < 2) s_doc[K_WIN / 32 + tid] = 0;  // the word behind the window's document bits: read as the zero word of MK_D, never written again
+    static_assert(K_WIN / 32 + 2 == CM_STRIDE, "the document bits cover the words the stored masks have");
     // FUSED: state of the token phases (declared unconditionally; the plain instantiation never touches it and the
     // compiler drops it)
     __shared__ __attribute__((aligned(16))) uint32_t s_kmask[FUSED ? (P12_MAXLEN + 1) * 4 : 4];  // row len: byte masks of a len-byte key
@@ -1187,28 +1194,30 @@ __global__ __launch_bounds__(K_THREADS, FUSED ? TD_FUSED_MIN_WAVES : TD_SPLIT_MI
         // ---- phase 1: class masks.  Every lane takes 8 text bytes: feature byte per byte (ASCII: 128-B LUT in LDS;
         //      otherwise UTF-8 decode + 2-stage Unicode table in L2), an 8x8 bit transpose turns the 8 feature bytes
         //      into the 8-bit slices of the class masks, the SYNC slice follows from them and the neighbour's last
-        //      byte; 12 byte stores put the slices into the word-major mask array ------------------------------------
+        //      byte; 9 byte stores put the slices into the mask-major arrays (N, A, SP and D are derived by the views) ------
         LdsSrc src;
         src.txt = s_txt;
         src.docw = s_doc;
         src.lo = (wg0 < 0) ? -wg0 : 0;
         src.hi = (a->n - wg0 < K_WIN) ? (a->n - wg0) : K_WIN;
-        if (tid < MK_COUNT) s_mask[K_MWORDS * MK_COUNT + tid] = 0;  // zero word behind the last one
+        if (tid < 2 * CM_COUNT) s_cm[(tid >> 1) * CM_STRIDE + 2 * K_MWORDS + (tid & 1)] = 0;  // zero word behind the last one of every stored mask
         // masks of one item from its eight feature bytes and the feature byte in front of them
         auto emit_masks = [&](int it, uint32_t flo, uint32_t fhi, uint32_t pf) {
             const uint64_t P = transpose8x8(((uint64_t)fhi << 32) | flo);  // byte k = bit plane of feature bit k
             const uint32_t plo = (uint32_t)P, phi = (uint32_t)(P >> 32);
             const uint32_t mU = plo & 0xFF, mW = (plo >> 8) & 0xFF, mX = (plo >> 16) & 0xFF, mS = plo >> 24;
             const uint32_t nraw = phi & 0xFF, mCR = (phi >> 8) & 0xFF, mSL = (phi >> 16) & 0xFF, mC = phi >> 24;
-            const uint32_t mN = nraw & ~mX & ~mS, mA = nraw & mX, mSP = nraw & mS;
+            const uint32_t mN = nraw & ~mX & ~mS, mA = nraw & mX;
             const uint32_t mD = reinterpret_cast<const uint8_t*>(s_doc)[it];
             const uint32_t mSY = sync_byte(mU, mW, mX, mS, mN, mCR, mSL, mC, mD, mA, pf, PV);
-            static_assert(MK_U == 0 && MK_W == 1 && MK_X == 2 && MK_S == 3 && MK_N == 4 && MK_CR == 5 && MK_TR == 6 &&
-                          MK_C == 7 && MK_D == 8 && MK_A == 9 && MK_SP == 10 && MK_SYNC == 11, "mask order");
-            uint8_t* o = reinterpret_cast<uint8_t*>(s_mask + (it >> 3) * MK_COUNT) + (it & 7);
-            o[0 * 8] = (uint8_t)mU; o[1 * 8] = (uint8_t)mW; o[2 * 8] = (uint8_t)mX; o[3 * 8] = (uint8_t)mS;
-            o[4 * 8] = (uint8_t)mN; o[5 * 8] = (uint8_t)mCR; o[6 * 8] = (uint8_t)(mCR | mSL); o[7 * 8] = (uint8_t)mC;
-            o[8 * 8] = (uint8_t)mD; o[9 * 8] = (uint8_t)mA; o[10 * 8] = (uint8_t)mSP; o[11 * 8] = (uint8_t)mSY;
+            // (stored: nine; the views derive N, A and SP from NRAW, X and S and take D from s_doc — cm_expand, CompactMaskP)
+            static_assert(CM_U == 0 && CM_W == 1 && CM_X == 2 && CM_S == 3 && CM_NRAW == 4 && CM_CR == 5 && CM_TR == 6 &&
+                          CM_C == 7 && CM_SYNC == 8, "stored mask order");
+            uint8_t* o = reinterpret_cast<uint8_t*>(s_cm) + it;
+            constexpr int MB = CM_STRIDE * 4;  // bytes per stored mask
+            o[0 * MB] = (uint8_t)mU; o[1 * MB] = (uint8_t)mW; o[2 * MB] = (uint8_t)mX; o[3 * MB] = (uint8_t)mS;
+            o[4 * MB] = (uint8_t)nraw; o[5 * MB] = (uint8_t)mCR; o[6 * MB] = (uint8_t)(mCR | mSL); o[7 * MB] = (uint8_t)mC;
+            o[8 * MB] = (uint8_t)mSY;
         };
         constexpr int P1_ITEMS = K_WIN / 8;
         if (tile_ascii) {
@@ -1397,8 +1406,20 @@ __global__ __launch_bounds__(K_THREADS, FUSED ? TD_FUSED_MIN_WAVES : TD_SPLIT_MI
         //      ("first piece start unknown": it lies inside a piece longer than the halo) and gets it through tile_carry.
         {
             constexpr bool FAST = !(PV & (PV_GPT2 | PV_LEADING_CONTRACTION | PV_PLAIN_LETTERS | PV_WS_EOS_FIRST));
-            const uint32_t* s_mask32 = reinterpret_cast<const uint32_t*>(s_mask);
-            auto dword_at = [](int j) { return (j >> 1) * (MK_COUNT * 2) + (j & 1); };  // mask 0 of dword j; mask k: + 2 k
+            // dwords j and j + 1 of the nine stored masks and of the document bits, as 64-bit words (sh == 0) or cut to the 32 bits
+            // from bit sh of dword j on, expanded to the twelve views
+            auto load_view64 = [&](BitWin& v, int j) {
+                uint64_t s[CM_COUNT];
+#pragma unroll
+                for (int k = 0; k < CM_COUNT; ++k) s[k] = ((uint64_t)s_cm[k * CM_STRIDE + j + 1] << 32) | s_cm[k * CM_STRIDE + j];
+                cm_expand(v, s, ((uint64_t)s_doc[j + 1] << 32) | s_doc[j]);
+            };
+            auto load_view32 = [&](BitWin32& v, int j, uint32_t sh) {
+                uint32_t s[CM_COUNT];
+#pragma unroll
+                for (int k = 0; k < CM_COUNT; ++k) s[k] = __funnelshift_r(s_cm[k * CM_STRIDE + j], s_cm[k * CM_STRIDE + j + 1], sh);
+                cm_expand(v, s, __funnelshift_r(s_doc[j], s_doc[j + 1], sh));
+            };
             auto defer = [&](int64_t g) {
                 if (FUSED) s_defer = 1;
                 const uint32_t q = atomicAdd(a->slow_count, 1u);
@@ -1406,7 +1427,7 @@ __global__ __launch_bounds__(K_THREADS, FUSED ? TD_FUSED_MIN_WAVES : TD_SPLIT_MI
                 else raise(a, TD_E_SCRATCH, g);
             };
             auto mark = [&](int q) { atomicOr(&s_start[q >> 5], 1u << (q & 31)); };
-            auto sync_at = [&](int q) { return (s_mask32[dword_at(q >> 5) + 2 * MK_SYNC] >> (q & 31)) & 1u; };
+            auto sync_at = [&](int q) { return (s_cm[CM_SYNC * CM_STRIDE + (q >> 5)] >> (q & 31)) & 1u; };
             auto crossed = [&](int e) {  // first piece start of the next tile
                 if (FUSED) s_cross = e;
                 if (tile + 1 < a->n_stiles) a->tile_carry[tile + 1] = wg0 + e;
@@ -1414,7 +1435,7 @@ __global__ __launch_bounds__(K_THREADS, FUSED ? TD_FUSED_MIN_WAVES : TD_SPLIT_MI
             // general matcher from the piece start p (marked) to the end of its chain
             auto walk = [&](int p) {
                 for (;;) {
-                    const int e = scan_piece_lds<PV>(s_mask, s_txt, p);
+                    const int e = scan_piece_lds<PV>(s_cm, s_doc, s_txt, p);
                     if (e < 0) { if (p >= K_HL) defer(wg0 + p); return; }
                     if (e >= tile_hi) { crossed(e); return; }
                     if (sync_at(e)) return;
@@ -1427,11 +1448,8 @@ __global__ __launch_bounds__(K_THREADS, FUSED ? TD_FUSED_MIN_WAVES : TD_SPLIT_MI
             uint32_t mine = 0;  // unresolved heads of my stride that found no room on the list
             uint32_t extra_hi = 0;
             {
-                const uint32_t* lo = s_mask32 + dword_at(b0 >> 5);
-                const uint32_t* hi = s_mask32 + dword_at((b0 >> 5) + 1);
                 BitWin wv;
-#pragma unroll
-                for (int k = 0; k < MK_COUNT; ++k) wv.m[k] = ((uint64_t)hi[2 * k] << 32) | lo[2 * k];
+                load_view64(wv, b0 >> 5);
                 uint32_t sy = (uint32_t)wv.m[MK_SYNC];
                 const int room = tile_hi - b0;
                 if (room < 32) sy = room <= 0 ? 0u : sy & ((1u << room) - 1u);
@@ -1474,10 +1492,11 @@ __global__ __launch_bounds__(K_THREADS, FUSED ? TD_FUSED_MIN_WAVES : TD_SPLIT_MI
                 // lane 1 with the tile's last head
                 if (tid == 0) {
                     static_assert(K_HL % 64 == 0 && K_HL >= 64, "left halo = whole mask words");
-                    if (!(s_mask[(K_HL / 64) * MK_COUNT + MK_SYNC] & 1ull)) {
+                    const uint32_t* const sync32 = s_cm + CM_SYNC * CM_STRIDE;
+                    if (!(sync32[K_HL / 32] & 1u)) {
                         int sp = -1;
                         for (int w = K_HL / 64 - 1; w >= 0 && sp < 0; --w) {
-                            uint64_t m = s_mask[w * MK_COUNT + MK_SYNC];
+                            uint64_t m = ((uint64_t)sync32[2 * w + 1] << 32) | sync32[2 * w];
                             if (w == 0) m &= ~0xFull;
                             if (m) sp = w * 64 + td_top64(m) - 1;
                         }
@@ -1501,12 +1520,8 @@ __global__ __launch_bounds__(K_THREADS, FUSED ? TD_FUSED_MIN_WAVES : TD_SPLIT_MI
                     }
                     if (!__ballot(p >= 0)) break;
                     if (p >= 0) {
-                        const int sh = p & 31;
-                        const uint32_t* lo = s_mask32 + dword_at(p >> 5);
-                        const uint32_t* hi = s_mask32 + dword_at((p >> 5) + 1);
                         BitWin32 v;  // 32-bit view of every mask with bit 0 = the piece start
-#pragma unroll
-                        for (int k = 0; k < MK_COUNT; ++k) v.m[k] = __funnelshift_r(lo[2 * k], hi[2 * k], (uint32_t)sh);
+                        load_view32(v, p >> 5, (uint32_t)(p & 31));
                         const int avail = (K_LIM - p < 32) ? (K_LIM - p) : 32;
                         auto bytes = [&](int q) { return (uint32_t)s_txt[p + q]; };
                         const int r = FAST ? scan_piece_fast32(v, avail, bytes, PV) : scan_piece_p(WinP32(v, avail), bytes, PV);
@@ -1573,7 +1588,6 @@ __global__ __launch_bounds__(K_THREADS, FUSED ? TD_FUSED_MIN_WAVES : TD_SPLIT_MI
             uint16_t* const s_plist = reinterpret_cast<uint16_t*>(s_R + FZ_R_PLIST);
             uint16_t* const s_coldk = reinterpret_cast<uint16_t*>(s_R + FZ_R_COLDK);
             uint16_t* const s_pb = reinterpret_cast<uint16_t*>(s_R + FZ_R_PB);
-            uint32_t* const s_sm = reinterpret_cast<uint32_t*>(s_R + FZ_R_SM);
             const int wv = tid >> 6;
             const int tile4 = tile * NT4;            // first token tile of the pair
             const bool two = K_HL + K_TILE < tile_hi;  // the second one exists
@@ -1614,7 +1628,6 @@ __global__ __launch_bounds__(K_THREADS, FUSED ? TD_FUSED_MIN_WAVES : TD_SPLIT_MI
                     }
                 }
                 s_pb[tid] = (uint16_t)pbase;
-                s_sm[tid] = smask0;
                 if (tid == 0) s_plist[np] = (uint16_t)cross;  // end of the tile's last piece: where the boundary scan crossed the tile end
                 const uint64_t fdd = fd0 != 0xFFFFFFFFu ? fd0 : fd1;
                 // (parked now: what is kept in a register to the end of the tile is spilled, and a reload from scratch memory behind the
@@ -1742,7 +1755,7 @@ __global__ __launch_bounds__(K_THREADS, FUSED ? TD_FUSED_MIN_WAVES : TD_SPLIT_MI
                         const int64_t tile_end_g = wg0 + tile_hi;
                         auto slot_of = [&](int64_t p) {
                             const int lp = (int)(p - tile_g0);
-                            const uint32_t k = (uint32_t)s_pb[lp >> 5] + __popc(s_sm[lp >> 5] & ((1u << (lp & 31)) - 1u));
+                            const uint32_t k = (uint32_t)s_pb[lp >> 5] + __popc(s_start[K_HL / 32 + (lp >> 5)] & ((1u << (lp & 31)) - 1u));
                             return k >= n0 ? k - n0 : k;
                         };
                         if (dpos < tile_end_g) {
@@ -1806,7 +1819,7 @@ __global__ __launch_bounds__(K_THREADS, FUSED ? TD_FUSED_MIN_WAVES : TD_SPLIT_MI
                     const int64_t tile_end_g = wg0 + tile_hi;
                     auto slot_of = [&](int64_t p) {
                         const int lp = (int)(p - tile_g0);
-                        const uint32_t k = (uint32_t)s_pb[lp >> 5] + __popc(s_sm[lp >> 5] & ((1u << (lp & 31)) - 1u));
+                        const uint32_t k = (uint32_t)s_pb[lp >> 5] + __popc(s_start[K_HL / 32 + (lp >> 5)] & ((1u << (lp & 31)) - 1u));
                         return k >= n0 ? k - n0 : k;
                     };
                     if (dpos < tile_end_g) {
