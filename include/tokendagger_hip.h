@@ -949,6 +949,67 @@ int td_minhash(td_tokenizer* t, const int32_t* ids, int64_t n_tokens, const int6
 int td_encode_batch_minhash(td_tokenizer* t, const uint8_t* text, const int64_t* doc_offsets, int64_t n_docs, int mode,
                             const td_minhash_spec* spec, uint32_t* sig, uint64_t* band_keys, int64_t* counts, int64_t* n_tokens_out);
 
+/* ---- Unicode NFC normalisation (td_nfc.hip) ---------------------------------------------------------------------------------------------
+ * The Qwen2 / Qwen2.5 / Qwen3 tokenizers normalise to NFC in front of their split pattern; the other supported families do not
+ * normalise.  Text + doc_offsets[n_docs + 1] (int64: from 0, non-decreasing, ending at or below n_bytes) -> flags[d] (uint8: 0 = the
+ * document is PROVEN to be its own NFC, 1 = not proven), and the normalised text + out_doc_offsets[n_docs + 1], which every
+ * td_encode_* entry point takes as it stands.  The tables are generated from one Unicode version, which td_nfc_info reports; host and
+ * device compile the same statement of the rule (td_nfc_args.h), so they cannot disagree.
+ *   UNITS      At byte p of a document, a well-formed UTF-8 sequence (Unicode Table 3-7: no overlong form, no surrogate, nothing above
+ *              U+10FFFF) that starts there and ends inside the document is a code point.  Otherwise byte p alone is an OPAQUE unit: it is
+ *              copied unchanged, composes with nothing, and nothing is reordered across it.  No sequence reaches across a document
+ *              boundary.
+ *   BOUNDARY   A unit that is opaque, the first of its document, or a code point with ccc == 0 and NFC_Quick_Check == Yes.  A SEGMENT
+ *              runs from a boundary to the next; documents and segments normalise independently.  Every code point that is no boundary
+ *              is >= U+0300, so every unit led by a byte below 0xCC is a boundary.
+ *   SEGMENT    UAX #15: canonical decomposition (at most 4 code points, Hangul by arithmetic), non-starters ordered stably by ccc, then
+ *              composition: a mark composes with the current starter iff the pair is a primary composite and no kept unit with
+ *              ccc == 0 or ccc >= its own lies between (Hangul LV, LVT by arithmetic; composition exclusions are no primary composites).
+ *              Any length is handled.
+ *   PROVEN     A stretch is proven NFC when every code point in it is Quick_Check Yes and ccc never decreases inside a run of
+ *              non-starters.  A proven segment is copied; flags[d] == 1 iff document d holds a code point that is not Quick_Check Yes or
+ *              a non-starter whose ccc is below that of the code point right in front of it.  Not proven does not mean changed (a Maybe
+ *              with nothing to compose with).
+ *   counts[8]  (int64) {output bytes needed, documents not proven, documents changed, segments rewritten (the segments not proven),
+ *              code points in them, opaque bytes, the longest segment in code points, 0}.  [5] and [6] are over the whole text, proven
+ *              or not (ASCII alone: 0 and 1).  td_nfc_check_device counts [1] alone, the rest is 0: the proof decodes nothing below
+ *              0xCC.  So does td_encode_batch_nfc when no document is flagged: {n_bytes, 0, 0, 0, 0, 0, 0, 0}, [5] and [6] NOT counted.
+ *   COST       A segment is normalised by one lane, in time linear in its length times the distinct ccc values in it: a document that is
+ *              one run of millions of combining marks is rewritten correctly, by a single lane, and holds its call up accordingly.
+ *   SIZES      The output is at most 3 x the input in bytes (U+1D1C0 reaches it): a capacity of 3 * n_bytes always fits.  An
+ *              output that does not fit is TD_E_CAPACITY (position: the bytes needed, also in counts[0]); no byte of `out` is written.
+ *              Bytes behind the last document are not copied.  changed[d] (uint8) = 1 iff the document's bytes differ.
+ * Argument errors are TD_E_INVALID before any launch: offsets on the host that do not start at 0 or decrease, a NULL stream, an
+ * output that overlaps the text.  Out of scope: NFD, NFKC, NFKD (the property word has five spare bits), a map from normalised bytes
+ * back to source bytes, Unicode versions other than the tables'. */
+#define TD_NFC_INFO_UNICODE_VERSION 0 /* major * 10000 + minor * 100 + patch */
+#define TD_NFC_INFO_TABLE_BYTES 1
+int64_t td_nfc_info(int what); /* -1: no such value */
+/* The contract's executable statement, on the host (no handle, no device).  out may be NULL with out_capacity == 0: out_doc_offsets,
+ * flags, changed (each may be NULL) and counts alone.  Argument errors write nothing. */
+int td_nfc_host(const uint8_t* text, const int64_t* doc_offsets, int64_t n_docs, uint8_t* out, int64_t out_capacity,
+                int64_t* out_doc_offsets, uint8_t* flags, uint8_t* changed, int64_t* counts);
+/* DEVICE buffers, asynchronously on hip_stream (never the null stream): no synchronisation and no read-back.  d_doc_offsets, d_counts
+ * and d_out_doc_offsets are 8-byte aligned; d_text needs no alignment.  Offsets that do not start at 0, decrease, are negative or end
+ * above n_bytes raise TD_E_INVALID through td_device_status with err_pos = the lowest such document, and then NOTHING is written. */
+int td_nfc_check_device(td_tokenizer* t, const void* d_text, int64_t n_bytes, const void* d_doc_offsets, int64_t n_docs,
+                        void* d_flags, void* d_counts, void* hip_stream);
+/* d_changed may be NULL.  TD_E_CAPACITY surfaces through td_device_status; d_counts is complete then, d_out and d_out_doc_offsets are
+ * not written. */
+int td_nfc_device(td_tokenizer* t, const void* d_text, int64_t n_bytes, const void* d_doc_offsets, int64_t n_docs,
+                  void* d_out, int64_t out_capacity, void* d_out_doc_offsets, void* d_changed, void* d_counts, void* hip_stream);
+/* Host buffers, synchronously; td_nfc_host's arguments behind the handle. */
+int td_nfc(td_tokenizer* t, const uint8_t* text, const int64_t* doc_offsets, int64_t n_docs, uint8_t* out, int64_t out_capacity,
+           int64_t* out_doc_offsets, uint8_t* flags, uint8_t* changed, int64_t* counts);
+/* Upload, check, and td_encode_batch (TD_MODE_ENCODE / TD_MODE_ORDINARY) of the ORIGINAL device buffer when no document is flagged;
+ * otherwise the text is normalised into the handle's workspace and that is encoded.  out_tok_offsets[n_docs + 1], and everything later
+ * computed from byte positions, refer to the NORMALISED text, which comes back on request: norm_text (may be NULL with norm_capacity
+ * 0), norm_doc_offsets and changed (may be NULL).  When nothing changed the normalised text is the input.  counts: as td_nfc gives
+ * them when a document is flagged, the check's otherwise (counts[8] above).  Synchronous. */
+int td_encode_batch_nfc(td_tokenizer* t, const uint8_t* text, const int64_t* doc_offsets, int64_t n_docs, int mode,
+                        int32_t* out_ids, int64_t ids_capacity, int64_t* out_tok_offsets,
+                        uint8_t* norm_text, int64_t norm_capacity, int64_t* norm_doc_offsets, uint8_t* changed, int64_t* counts);
+
 /* Options. */
 #define TD_OPT_LONG_POOL_BYTES 1 /* scratch for pieces longer than 64 bytes (default max(64 MiB, 2 x input)) */
 #define TD_OPT_PROFILE 2         /* 1: bracket the kernels of every td_encode_device call with HIP events on the

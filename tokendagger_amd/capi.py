@@ -82,6 +82,7 @@ EXPORTS = [
     "td_ngram_set_create", "td_ngram_set_destroy", "td_ngram_set_info", "td_ngram_matches_host", "td_ngram_matches_device",
     "td_ngram_matches", "td_encode_batch_ngram_matches",
     "td_minhash_params", "td_minhash_host", "td_minhash_device", "td_minhash", "td_encode_batch_minhash",
+    "td_nfc_info", "td_nfc_host", "td_nfc_check_device", "td_nfc_device", "td_nfc", "td_encode_batch_nfc",
 ]
 
 
@@ -235,6 +236,18 @@ def load_library():
     lib.td_minhash.argtypes = [vp, vp, i64, vp, i64, vp, vp, vp, vp]
     lib.td_encode_batch_minhash.restype = i32
     lib.td_encode_batch_minhash.argtypes = [vp, vp, vp, i64, i32, vp, vp, vp, vp, ctypes.POINTER(i64)]
+    lib.td_nfc_info.restype = i64
+    lib.td_nfc_info.argtypes = [i32]
+    lib.td_nfc_host.restype = i32
+    lib.td_nfc_host.argtypes = [vp, vp, i64, vp, i64, vp, vp, vp, vp]
+    lib.td_nfc_check_device.restype = i32
+    lib.td_nfc_check_device.argtypes = [vp, vp, i64, vp, i64, vp, vp, vp]
+    lib.td_nfc_device.restype = i32
+    lib.td_nfc_device.argtypes = [vp, vp, i64, vp, i64, vp, i64, vp, vp, vp, vp]
+    lib.td_nfc.restype = i32
+    lib.td_nfc.argtypes = [vp, vp, vp, i64, vp, i64, vp, vp, vp, vp]
+    lib.td_encode_batch_nfc.restype = i32
+    lib.td_encode_batch_nfc.argtypes = [vp, vp, vp, i64, i32, vp, i64, vp, vp, i64, vp, vp, vp]
     lib.td_encode_batch_token_counts.restype = i32
     lib.td_encode_batch_token_counts.argtypes = [vp, vp, vp, i64, i32, vp, vp, vp, vp, ctypes.POINTER(i64)]
     lib.td_comm_unique_id.restype = i32
@@ -789,6 +802,47 @@ def minhash_host(ids, tok_offsets, spec: MinhashSpec | None = None, n_tokens: in
     if rc != TD_OK:
         raise TokenDaggerHipError(rc, "td_minhash_host: invalid offsets, spec or arguments")
     return sig[:n_docs], (keys[:n_docs] if keys is not None else None), counts
+
+
+TD_NFC_INFO_UNICODE_VERSION, TD_NFC_INFO_TABLE_BYTES = 0, 1
+
+
+def nfc_info(what: int) -> int:
+    """td_nfc_info: TD_NFC_INFO_UNICODE_VERSION (major * 10000 + minor * 100 + patch) or TD_NFC_INFO_TABLE_BYTES; -1: no such value."""
+    return int(load_library().td_nfc_info(what))
+
+
+def _nfc_args(text, doc_offsets):
+    """-> (text uint8, offsets int64, n_docs, out_doc_offsets int64[n_docs + 1], flags uint8[n_docs], changed uint8[n_docs], counts int64[8])"""
+    buf = _as_u8(text)
+    o = np.ascontiguousarray(doc_offsets, dtype=np.int64)
+    n_docs = len(o) - 1
+    return (buf, o, n_docs, np.zeros(n_docs + 1, dtype=np.int64), np.zeros(max(n_docs, 1), dtype=np.uint8),
+            np.zeros(max(n_docs, 1), dtype=np.uint8), np.zeros(8, dtype=np.int64))
+
+
+def _nfc_capacity(buf, o, capacity):
+    """The bytes a normalised text can need (three times the documents' bytes) where the caller names none."""
+    return 3 * int(o[-1]) if capacity is None and len(o) and 0 <= int(o[-1]) <= len(buf) else int(capacity or 0)
+
+
+def nfc_host(text, doc_offsets, capacity: int | None = None, want_text: bool = True):
+    """td_nfc_host (host only, no device) -> (text uint8[counts[0]] | None, out_doc_offsets int64[n_docs + 1], flags uint8[n_docs]
+    (0: proven NFC), changed uint8[n_docs], counts int64[8] = output bytes, documents not proven, documents changed, segments rewritten,
+    code points in them, opaque bytes, longest segment, 0).  want_text=False: the sizing call.  capacity None: three times the input."""
+    lib = load_library()
+    buf, o, n_docs, ooff, flags, changed, counts = _nfc_args(text, doc_offsets)
+    if n_docs >= 0 and len(o) and int(o[-1]) > len(buf):
+        raise TokenDaggerHipError(TD_E_INVALID, "td_nfc_host: doc_offsets end behind the text")
+    cap = _nfc_capacity(buf, o, capacity) if want_text else 0
+    out = np.empty(max(cap, 1), dtype=np.uint8)
+    rc = lib.td_nfc_host(buf.ctypes.data if len(buf) else None, o.ctypes.data if len(o) else None, n_docs, out.ctypes.data if want_text else None,
+                         cap, ooff.ctypes.data, flags.ctypes.data, changed.ctypes.data, counts.ctypes.data)
+    if rc != TD_OK:
+        ex = TokenDaggerHipError(rc, "td_nfc_host: output capacity too small" if rc == TD_E_CAPACITY else "td_nfc_host: invalid offsets or arguments")
+        ex.counts = counts
+        raise ex
+    return (out[:int(counts[0])] if want_text else None), ooff, flags[:n_docs], changed[:n_docs], counts
 
 
 class NgramSet:
@@ -1788,6 +1842,50 @@ class HipTokenizer:
         self._check(self._lib.td_encode_batch_minhash(self._h, buf.ctypes.data if len(buf) else None, offs.ctypes.data, n_docs, mode,
                                                       ctypes.byref(spec), sig.ctypes.data, _ptr(keys), counts.ctypes.data, ctypes.byref(total)))
         return sig[:n_docs], (keys[:n_docs] if keys is not None else None), counts, int(total.value)
+
+    # ---- Unicode NFC normalisation ------------------------------------------------------------------------------
+    def nfc_check(self, d_text: int, n_bytes: int, d_doc_offsets: int, n_docs: int, d_flags: int, d_counts: int, stream: int):
+        """td_nfc_check_device: raw device pointers, asynchronous on `stream`, which must not be the null stream; d_flags uint8[n_docs]
+        (0: proven NFC), d_counts int64[8]; check with device_status(stream)."""
+        self._check(self._lib.td_nfc_check_device(self._h, d_text or None, n_bytes, d_doc_offsets or None, n_docs, d_flags or None,
+                                                  d_counts or None, stream or None))
+
+    def nfc_device(self, d_text: int, n_bytes: int, d_doc_offsets: int, n_docs: int, d_out: int, out_capacity: int, d_out_doc_offsets: int,
+                   d_changed: int, d_counts: int, stream: int):
+        """td_nfc_device: raw device pointers (d_changed may be 0), asynchronous on `stream`; check with device_status(stream)."""
+        self._check(self._lib.td_nfc_device(self._h, d_text or None, n_bytes, d_doc_offsets or None, n_docs, d_out or None, out_capacity,
+                                            d_out_doc_offsets or None, d_changed or None, d_counts or None, stream or None))
+
+    def nfc(self, text, doc_offsets, capacity: int | None = None, want_text: bool = True):
+        """td_nfc: nfc_host's arguments and results, computed on the device."""
+        buf, o, n_docs, ooff, flags, changed, counts = _nfc_args(text, doc_offsets)
+        cap = _nfc_capacity(buf, o, capacity) if want_text else 0
+        out = np.empty(max(cap, 1), dtype=np.uint8)
+        rc = self._lib.td_nfc(self._h, buf.ctypes.data if len(buf) else None, o.ctypes.data, n_docs, out.ctypes.data if want_text else None, cap,
+                              ooff.ctypes.data, flags.ctypes.data, changed.ctypes.data, counts.ctypes.data)
+        if rc != TD_OK:
+            ex = TokenDaggerHipError(rc, self._lib.td_last_error(self._h).decode("utf-8", "replace"))
+            ex.counts = counts
+            raise ex
+        return (out[:int(counts[0])] if want_text else None), ooff, flags[:n_docs], changed[:n_docs], counts
+
+    def encode_batch_nfc(self, text, doc_offsets, mode: int = TD_MODE_ENCODE, return_text: bool = False):
+        """td_encode_batch_nfc: check, normalise where a document is flagged, encode -> (ids int32, tok_offsets int64[n_docs + 1],
+        norm_text uint8 | None, norm_doc_offsets int64[n_docs + 1], changed uint8[n_docs], counts int64[8]).  Offsets refer to the
+        normalised text."""
+        buf, o, n_docs, noff, _, changed, counts = _nfc_args(text, doc_offsets)
+        n = int(o[-1]) if len(o) and 0 <= int(o[-1]) <= len(buf) else 0
+        toff = np.zeros(n_docs + 1, dtype=np.int64)
+        for cap in (n + 64, 3 * n + 64):  # (NFC rarely grows a text: room for three times its bytes only when the first call asks for it)
+            ids = np.empty(cap, dtype=np.int32)
+            norm = np.empty(cap, dtype=np.uint8) if return_text else None
+            rc = self._lib.td_encode_batch_nfc(self._h, buf.ctypes.data if len(buf) else None, o.ctypes.data, n_docs, mode, ids.ctypes.data,
+                                               cap, toff.ctypes.data, _ptr(norm), cap if return_text else 0, noff.ctypes.data,
+                                               changed.ctypes.data, counts.ctypes.data)
+            if rc != TD_E_CAPACITY:
+                break
+        self._check(rc)
+        return ids[:int(toff[-1])], toff, (norm[:int(counts[0])] if return_text else None), noff, changed[:n_docs], counts
 
     # ---- decode rows (td_decode_spec) ---------------------------------------------------------------------------
     def decode_rows(self, ids, spec: DecodeSpec, tok_offsets=None, lengths=None, n_segs: int | None = None, capacity: int | None = None):

@@ -275,6 +275,9 @@ struct td_tokenizer {
     // MinHash signatures (td_minhash.hip): the bad-offsets word and the document counts, the permutation table and what it was built
     // for; the host entry points' signatures, band keys and counts on the device
     DevBuf mh_head, mh_table, mh_sig, mh_keys, mh_counts;
+    // NFC normalisation (td_nfc.hip): the bad-offsets / full words, the tiles' output bytes and bases, flags and changed where the
+    // caller has none; the host entry points' counts, normalised text and its document offsets on the device
+    DevBuf nfc_head, nfc_tiles, nfc_flags, nfc_changed, nfc_counts, nfc_out, nfc_out_off;
     int64_t mh_table_perm = 0;     // 0: no table yet
     uint64_t mh_table_seed = 0;
     std::vector<int64_t> dcr_key;  // flags, then the distinct listed ids with their bits (sorted); empty: no table yet

@@ -42,6 +42,9 @@ CL100K_PAT_STR_POSSESSIVE = (
 QWEN2_PAT_STR = (
     r"(?i:'s|'t|'re|'ve|'m|'ll|'d)|[^\r\n\p{L}\p{N}]?\p{L}+|\p{N}| ?[^\s\p{L}\p{N}]+[\r\n]*|\s*[\r\n]+|\s+(?!\S)|\s+"
 )
+# ... behind the normalizer of the same tokenizer.json ({"type": "NFC"}): Tokenizer(..., normalizer=QWEN2_NORMALIZER) for strings,
+# Tokenizer.normalize_batch / encode_batch_to_numpy_normalized for bulk text.  The other families here have no normalizer.
+QWEN2_NORMALIZER = "NFC"
 # cl100k_base as current tiktoken releases spell it (tiktoken_ext/openai_public.py): the same language again
 CL100K_PAT_STR_CURRENT = (
     r"'(?i:[sdmt]|ll|ve|re)|[^\r\n\p{L}\p{N}]?+\p{L}++|\p{N}{1,3}+| ?[^\s\p{L}\p{N}]++[\r\n]*+|\s++$|\s*[\r\n]|\s+(?!\S)|\s"

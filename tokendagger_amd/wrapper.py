@@ -115,6 +115,25 @@ class MinHashes(NamedTuple):
         return float(np.mean(self.signatures[i] == self.signatures[j]))
 
 
+class NormalizedText(NamedTuple):
+    """Tokenizer.normalize_batch (the contract: include/tokendagger_hip.h, td_nfc*): text + offsets go to every bulk method as they stand."""
+    text: np.ndarray     # uint8: the documents' NFC, concatenated
+    offsets: np.ndarray  # int64 [n_docs + 1]
+    flags: np.ndarray | None  # uint8 [n_docs]: 0 = the document was proven to be NFC already, 1 = not proven
+    changed: np.ndarray  # uint8 [n_docs]: 1 = the document's bytes differ
+    counts: np.ndarray   # int64 [8]: output bytes, documents not proven, documents changed, segments rewritten, code points in them,
+                         # opaque bytes, the longest segment in code points, 0
+
+
+_NORMALIZERS = (None, "NFC")
+
+
+def _check_normalizer(normalizer):
+    if normalizer not in _NORMALIZERS:
+        raise ValueError(f"normalizer must be None or 'NFC', not {normalizer!r}")
+    return normalizer
+
+
 class DecodedRows(NamedTuple):
     """Tokenizer.decode_rows_to_numpy (the contract: include/tokendagger_hip.h, td_decode_spec)."""
     data: np.ndarray     # uint8: the segments' bytes, concatenated
@@ -176,8 +195,10 @@ class Tokenizer:
         vocab_file: str | Path | None = None,
         special_tokens_file: str | Path | None = None,
         device: int = -1,
+        normalizer: str | None = None,
     ):
         self.name = name
+        self.normalizer = _check_normalizer(normalizer)
         self.pattern = pat_str if pat_str is not None else pattern
         if mergeable_ranks is not None:
             vocab = mergeable_ranks
@@ -208,7 +229,7 @@ class Tokenizer:
     def from_files(cls, name: str, *, pat_str: str | None = None, tiktoken_model: str | Path | None = None,
                    hf_config: str | Path | None = None, specials_mergeable: bool = False,
                    tekken: str | Path | None = None, vocab_file: str | Path | None = None,
-                   special_tokens_file: str | Path | None = None, device: int = -1) -> "Tokenizer":
+                   special_tokens_file: str | Path | None = None, device: int = -1, normalizer: str | None = None) -> "Tokenizer":
         """Build a tokenizer straight from vocabulary files with the C++ loaders (no per-token Python objects):
         a tiktoken ``.model`` (+ optional Hugging Face ``tokenizer_config.json`` for the special tokens, which
         ``specials_mergeable`` also enters as ordinary tokens the way the reference's benchmarks do), a Mistral
@@ -219,6 +240,7 @@ class Tokenizer:
         s = lambda p: "" if p is None else str(p)
         self = cls.__new__(cls)
         self.name = name
+        self.normalizer = _check_normalizer(normalizer)
         try:
             self._core_bpe = _core.CoreBPE.from_files(pat_str or "", s(tiktoken_model), s(hf_config), specials_mergeable,
                                                       s(tekken), s(vocab_file), s(special_tokens_file), device)
@@ -255,7 +277,19 @@ class Tokenizer:
                 raise ValueError(f"Encountered disallowed special token {token!r}. "
                                  f"Pass it to allowed_special to encode it as a special token.")
 
+    def _norm(self, text):
+        """A string (or bytes) through the tokenizer's normalizer: td_nfc_host, the tables the device uses."""
+        if self.normalizer is None:
+            return text
+        data = text.encode("utf-8", "surrogatepass") if isinstance(text, str) else bytes(text)
+        out = _capi.nfc_host(data, [0, len(data)])[0].tobytes()
+        return out.decode("utf-8", "surrogatepass") if isinstance(text, str) else out
+
+    def _norm_all(self, texts):
+        return texts if self.normalizer is None else [self._norm(t) for t in texts]
+
     def encode_ordinary(self, text: str) -> list[int]:
+        text = self._norm(text)
         try:
             return self._core_bpe.encode_ordinary(text)
         except Exception as e:
@@ -269,6 +303,7 @@ class Tokenizer:
         disallowed_special: Literal["all"] | Collection[str] = set(),
     ) -> list[int]:
         allowed, disallowed = self._special_sets(allowed_special, disallowed_special)
+        text = self._norm(text)
         self._check_disallowed(text, disallowed)
         try:
             tokens, _ = self._core_bpe.encode(text, allowed)
@@ -277,6 +312,7 @@ class Tokenizer:
             raise TokenDaggerError(f"Encoding failed: {e}")
 
     def encode_with_special_tokens(self, text: str) -> list[int]:
+        text = self._norm(text)
         try:
             return self._core_bpe.encode_with_special_tokens(text)
         except Exception as e:
@@ -292,6 +328,7 @@ class Tokenizer:
     ) -> list[list[int]]:
         allowed, disallowed = self._special_sets(allowed_special, disallowed_special)
         texts = text if isinstance(text, (list, tuple)) else list(text)  # (the binding takes a private tuple of the items itself)
+        texts = self._norm_all(texts)
         if disallowed:  # (nothing to look for otherwise: the loop alone was 0.2 us per document)
             for t in texts:
                 self._check_disallowed(t, disallowed)
@@ -304,13 +341,13 @@ class Tokenizer:
 
     def encode_ordinary_batch(self, text: Sequence[str], *, num_threads: int = 8) -> list[list[int]]:
         try:
-            return self._core_bpe.encode_batch(list(text), MODE_ORDINARY)
+            return self._core_bpe.encode_batch(self._norm_all(list(text)), MODE_ORDINARY)
         except Exception as e:
             raise TokenDaggerError(f"Encoding failed: {e}")
 
     def encode_to_numpy(self, text: str | bytes) -> np.ndarray:
         """tiktoken's array-returning encode: int32 ids without a Python int per token."""
-        data = text.encode("utf-8") if isinstance(text, str) else bytes(text)
+        data = self._norm(text.encode("utf-8") if isinstance(text, str) else bytes(text))
         buf = np.frombuffer(data, dtype=np.uint8)
         try:
             toks, _ = self._core_bpe.encode_batch_numpy(buf, np.asarray([0, len(buf)], dtype=np.int64), MODE_ENCODE)
@@ -326,6 +363,33 @@ class Tokenizer:
                                                      MODE_ORDINARY if ordinary else MODE_ENCODE)
         except Exception as e:
             raise TokenDaggerError(f"Encoding failed: {e}")
+
+    # ------------------------------------------------------------------ normalisation ----------
+    # The Qwen2 / Qwen2.5 / Qwen3 tokenizers normalise to NFC in front of their split pattern (vocab_io.QWEN2_NORMALIZER).  On the
+    # device: a check that proves a document NFC at read speed, and a rewrite of the places where it is not.  Token offsets and
+    # everything else computed from byte positions refer to the NORMALISED text; give it to the other bulk methods as it stands.
+    def normalize_batch(self, text: np.ndarray | bytes, offsets: np.ndarray, form: str = "NFC") -> NormalizedText:
+        """Concatenated UTF-8 bytes + int64 document offsets -> their NFC with its offsets, on the GPU."""
+        if form != "NFC":
+            raise ValueError(f"form must be 'NFC', not {form!r}")
+        hip = _capi.HipTokenizer.borrow(self._core_bpe.handle())
+        buf = np.frombuffer(text, dtype=np.uint8) if isinstance(text, (bytes, bytearray)) else text
+        try:
+            return NormalizedText(*hip.nfc(buf, np.asarray(offsets, dtype=np.int64)))
+        except _capi.TokenDaggerHipError as ex:
+            raise TokenDaggerError(f"Normalisation failed: {ex}")
+
+    def encode_batch_to_numpy_normalized(self, text: np.ndarray | bytes, offsets: np.ndarray, *, ordinary: bool = False, return_text: bool = False):
+        """encode_batch_to_numpy behind the NFC check: text that is proven NFC is encoded as it lies on the device, anything else is
+        normalised there first -> (int32 ids, int64 token offsets), with return_text also a NormalizedText (its flags: None)."""
+        hip = _capi.HipTokenizer.borrow(self._core_bpe.handle())
+        buf = np.frombuffer(text, dtype=np.uint8) if isinstance(text, (bytes, bytearray)) else text
+        try:
+            ids, toff, norm, noff, changed, counts = hip.encode_batch_nfc(buf, np.asarray(offsets, dtype=np.int64),
+                                                                          MODE_ORDINARY if ordinary else MODE_ENCODE, return_text=return_text)
+        except _capi.TokenDaggerHipError as ex:
+            raise TokenDaggerError(f"Encoding failed: {ex}")
+        return (ids, toff, NormalizedText(norm, noff, None, changed, counts)) if return_text else (ids, toff)
 
     # ------------------------------------------------------------------ offsets ----------------
     # The start of a token is where its text begins in its document: in "bytes", the offset of its first UTF-8 byte; in "chars",
@@ -1057,9 +1121,9 @@ def create_tokenizer(name: str, pattern: str, vocab: list[dict], special_tokens:
 
 
 def Encoding(name: str, *, pat_str: str, mergeable_ranks: dict[bytes, int],
-             special_tokens: dict[str, int] | None = None) -> Tokenizer:
+             special_tokens: dict[str, int] | None = None, normalizer: str | None = None) -> Tokenizer:
     """tiktoken-compatible factory (reference: wrapper.py:382-395)."""
-    return Tokenizer(name=name, pat_str=pat_str, mergeable_ranks=mergeable_ranks, special_tokens=special_tokens or {})
+    return Tokenizer(name=name, pat_str=pat_str, mergeable_ranks=mergeable_ranks, special_tokens=special_tokens or {}, normalizer=normalizer)
 
 
 def llama4_scout(device: int = -1) -> Tokenizer:
