@@ -1010,6 +1010,66 @@ int td_encode_batch_nfc(td_tokenizer* t, const uint8_t* text, const int64_t* doc
                         int32_t* out_ids, int64_t ids_capacity, int64_t* out_tok_offsets,
                         uint8_t* norm_text, int64_t norm_capacity, int64_t* norm_doc_offsets, uint8_t* changed, int64_t* counts);
 
+/* ---- UTF-8 validation and repair (td_utf8.hip) --------------------------------------------------------------------------------------------
+ * The reference encodes `str`, which is always well-formed UTF-8; the bulk entry points take raw bytes, and what the encoder does with
+ * ill-formed bytes is its own (td_common.h).  Text + doc_offsets[n_docs + 1] (int64: from 0, non-decreasing, ending at or below n_bytes)
+ * -> flags[d] (uint8: 0 = document d is well-formed), first_bad[d], n_bad[d], and the repaired text + out_doc_offsets[n_docs + 1], which
+ * every td_encode_* entry point takes as it stands.  Per document this is exactly CPython's
+ * bytes.decode("utf-8", "replace" | "ignore").encode("utf-8").  Host and device compile the same statement of the rule (td_utf8_args.h).
+ *   DOCUMENTS  are independent: nothing reaches across a document boundary.  Inside document d, walk from its first byte; at position p:
+ *   WELL-FORMED  A well-formed sequence (Unicode Table 3-7: no overlong form, no surrogate, nothing above U+10FFFF) that starts at p and
+ *              ends inside the document is one unit.  It is copied.
+ *   SUBPART    Otherwise the unit is the maximal subpart (Unicode 3.9, "U+FFFD substitution of maximal subparts", the WHATWG decoder):
+ *              the lead byte (C2 .. F4) plus as many following bytes as still form a prefix of some well-formed sequence, the second
+ *              byte held to the lead's own range (E0: A0 .. BF, ED: 80 .. 9F, F0: 90 .. BF, F4: 80 .. 8F, else 80 .. BF); a byte that can
+ *              start nothing (80 .. BF, C0, C1, F5 .. FF) is a subpart of length one.  TD_UTF8_REPLACE writes EF BF BD for the subpart,
+ *              TD_UTF8_IGNORE writes nothing.
+ *   CONTEXT    Whether p starts a unit is decided by at most three bytes in front of it: a byte that is no continuation byte always
+ *              does; a continuation byte is consumed iff the nearest non-continuation byte q in p - 3 .. p - 1, inside the document, is a
+ *              lead that needs more than p - q bytes and text[q + 1] is in that lead's second-byte range.
+ *   PER DOCUMENT  flags[d] (uint8), first_bad[d] (int64: the offset inside the document of its first ill-formed subpart, or -1),
+ *              n_bad[d] (int64: its ill-formed subparts), out_doc_offsets[n_docs + 1].
+ *   counts[8]  (int64) {output bytes needed, documents ill-formed, subparts, bytes in subparts, documents that begin with a
+ *              continuation byte, documents whose last unit is a subpart led by a lead byte, 0, 0}.  [4] and [5] say that a chunker cuts
+ *              characters.  td_utf8_check_device fills flags, first_bad and counts[1] ALONE, the rest of counts is 0; so does
+ *              td_encode_batch_utf8 when no document is flagged: {n_bytes, 0, 0, 0, 0, 0, 0, 0}.
+ *   SIZES      TD_UTF8_REPLACE needs at most 3 x the input (a text of stray 80s reaches it), TD_UTF8_IGNORE at most 1 x.  An output that
+ *              does not fit is TD_E_CAPACITY (position: the bytes needed, also in counts[0]); nothing is written to `out` or the
+ *              offsets.  Bytes behind the last document are not read.
+ * Argument errors are TD_E_INVALID before any launch: offsets on the host that do not start at 0 or decrease, a NULL stream, a policy
+ * other than the two, an output that overlaps the text.  Results are bitwise reproducible (minima, ors and integer sums only).  Out of
+ * scope: other encodings, one U+FFFD per byte, a map from repaired bytes back to source bytes, a NUL or control-character policy,
+ * dropping documents (td_select_docs with flags does it). */
+#define TD_UTF8_REPLACE 0
+#define TD_UTF8_IGNORE 1
+/* The contract's executable statement, on the host (no handle, no device).  out may be NULL with out_capacity == 0: out_doc_offsets,
+ * flags, first_bad, n_bad (each may be NULL) and counts alone.  Argument errors write nothing. */
+int td_utf8_host(const uint8_t* text, const int64_t* doc_offsets, int64_t n_docs, int policy, uint8_t* out, int64_t out_capacity,
+                 int64_t* out_doc_offsets, uint8_t* flags, int64_t* first_bad, int64_t* n_bad, int64_t* counts);
+/* DEVICE buffers, asynchronously on hip_stream (never the null stream): no synchronisation and no read-back.  d_doc_offsets, d_counts,
+ * d_first_bad, d_n_bad and d_out_doc_offsets are 8-byte aligned; d_text needs no alignment.  Offsets that do not start at 0, decrease,
+ * are negative or end above n_bytes raise TD_E_INVALID through td_device_status with err_pos = the lowest such document, and then
+ * NOTHING is written.  d_first_bad may be NULL.  counts: [1] alone. */
+int td_utf8_check_device(td_tokenizer* t, const void* d_text, int64_t n_bytes, const void* d_doc_offsets, int64_t n_docs,
+                         void* d_flags, void* d_first_bad, void* d_counts, void* hip_stream);
+/* d_flags, d_first_bad and d_n_bad may be NULL.  TD_E_CAPACITY surfaces through td_device_status; d_counts[0] holds the bytes needed
+ * then, d_out and d_out_doc_offsets are not written. */
+int td_utf8_device(td_tokenizer* t, const void* d_text, int64_t n_bytes, const void* d_doc_offsets, int64_t n_docs, int policy,
+                   void* d_out, int64_t out_capacity, void* d_out_doc_offsets, void* d_flags, void* d_first_bad, void* d_n_bad,
+                   void* d_counts, void* hip_stream);
+/* Host buffers, synchronously; td_utf8_host's arguments behind the handle.  With out, out_doc_offsets and n_bad all NULL the call is
+ * the CHECK (one pass at read speed): flags, first_bad and counts[1] alone, the rest of counts 0. */
+int td_utf8(td_tokenizer* t, const uint8_t* text, const int64_t* doc_offsets, int64_t n_docs, int policy, uint8_t* out,
+            int64_t out_capacity, int64_t* out_doc_offsets, uint8_t* flags, int64_t* first_bad, int64_t* n_bad, int64_t* counts);
+/* Upload, check, and td_encode_batch (TD_MODE_ENCODE / TD_MODE_ORDINARY only) of the ORIGINAL device buffer when no document is
+ * flagged; otherwise the text is repaired into the handle's workspace and that is encoded.  out_tok_offsets[n_docs + 1], and everything
+ * later computed from byte positions, refer to the REPAIRED text, which comes back on request: fixed_text (may be NULL with
+ * fixed_capacity 0), fixed_doc_offsets, flags, first_bad and n_bad (each may be NULL).  counts: as td_utf8 gives them when a document
+ * is flagged, the check's otherwise (counts[8] above).  Synchronous. */
+int td_encode_batch_utf8(td_tokenizer* t, const uint8_t* text, const int64_t* doc_offsets, int64_t n_docs, int mode, int policy,
+                         int32_t* out_ids, int64_t ids_capacity, int64_t* out_tok_offsets, uint8_t* fixed_text, int64_t fixed_capacity,
+                         int64_t* fixed_doc_offsets, uint8_t* flags, int64_t* first_bad, int64_t* n_bad, int64_t* counts);
+
 /* Options. */
 #define TD_OPT_LONG_POOL_BYTES 1 /* scratch for pieces longer than 64 bytes (default max(64 MiB, 2 x input)) */
 #define TD_OPT_PROFILE 2         /* 1: bracket the kernels of every td_encode_device call with HIP events on the

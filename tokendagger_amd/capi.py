@@ -248,6 +248,16 @@ def load_library():
     lib.td_nfc.argtypes = [vp, vp, vp, i64, vp, i64, vp, vp, vp, vp]
     lib.td_encode_batch_nfc.restype = i32
     lib.td_encode_batch_nfc.argtypes = [vp, vp, vp, i64, i32, vp, i64, vp, vp, i64, vp, vp, vp]
+    lib.td_utf8_host.restype = i32
+    lib.td_utf8_host.argtypes = [vp, vp, i64, i32, vp, i64, vp, vp, vp, vp, vp]
+    lib.td_utf8_check_device.restype = i32
+    lib.td_utf8_check_device.argtypes = [vp, vp, i64, vp, i64, vp, vp, vp, vp]
+    lib.td_utf8_device.restype = i32
+    lib.td_utf8_device.argtypes = [vp, vp, i64, vp, i64, i32, vp, i64, vp, vp, vp, vp, vp, vp]
+    lib.td_utf8.restype = i32
+    lib.td_utf8.argtypes = [vp, vp, vp, i64, i32, vp, i64, vp, vp, vp, vp, vp]
+    lib.td_encode_batch_utf8.restype = i32
+    lib.td_encode_batch_utf8.argtypes = [vp, vp, vp, i64, i32, i32, vp, i64, vp, vp, i64, vp, vp, vp, vp, vp]
     lib.td_encode_batch_token_counts.restype = i32
     lib.td_encode_batch_token_counts.argtypes = [vp, vp, vp, i64, i32, vp, vp, vp, vp, ctypes.POINTER(i64)]
     lib.td_comm_unique_id.restype = i32
@@ -843,6 +853,50 @@ def nfc_host(text, doc_offsets, capacity: int | None = None, want_text: bool = T
         ex.counts = counts
         raise ex
     return (out[:int(counts[0])] if want_text else None), ooff, flags[:n_docs], changed[:n_docs], counts
+
+
+TD_UTF8_REPLACE, TD_UTF8_IGNORE = 0, 1
+# (the UTF-8 entry points of include/tokendagger_hip.h)
+EXPORTS_UTF8 = ["td_utf8_host", "td_utf8_check_device", "td_utf8_device", "td_utf8", "td_encode_batch_utf8"]
+
+
+def _utf8_args(text, doc_offsets):
+    """-> (text uint8, offsets int64, n_docs, out_doc_offsets int64[n_docs + 1], flags uint8[n_docs], first_bad int64[n_docs], n_bad
+    int64[n_docs], counts int64[8])"""
+    buf = _as_u8(text)
+    o = np.ascontiguousarray(doc_offsets, dtype=np.int64)
+    n_docs = len(o) - 1
+    return (buf, o, n_docs, np.zeros(n_docs + 1, dtype=np.int64), np.zeros(max(n_docs, 1), dtype=np.uint8),
+            np.zeros(max(n_docs, 1), dtype=np.int64), np.zeros(max(n_docs, 1), dtype=np.int64), np.zeros(8, dtype=np.int64))
+
+
+def _utf8_capacity(buf, o, policy, capacity):
+    """The bytes a repaired text can need (three times the documents' bytes under REPLACE, their bytes under IGNORE) where the caller
+    names none."""
+    if capacity is None and len(o) and 0 <= int(o[-1]) <= len(buf):
+        return (1 if policy == TD_UTF8_IGNORE else 3) * int(o[-1])
+    return int(capacity or 0)
+
+
+def utf8_host(text, doc_offsets, policy: int = TD_UTF8_REPLACE, capacity: int | None = None, want_text: bool = True):
+    """td_utf8_host (host only, no device) -> (text uint8[counts[0]] | None, out_doc_offsets int64[n_docs + 1], flags uint8[n_docs]
+    (0: well-formed), first_bad int64[n_docs] (-1: none), n_bad int64[n_docs], counts int64[8] = output bytes, documents ill-formed,
+    subparts, bytes in subparts, documents that begin with a continuation byte, documents that end in a cut character, 0, 0).
+    want_text=False: the sizing call.  capacity None: what the policy can need."""
+    lib = load_library()
+    buf, o, n_docs, ooff, flags, first, nbad, counts = _utf8_args(text, doc_offsets)
+    if n_docs >= 0 and len(o) and int(o[-1]) > len(buf):
+        raise TokenDaggerHipError(TD_E_INVALID, "td_utf8_host: doc_offsets end behind the text")
+    cap = _utf8_capacity(buf, o, policy, capacity) if want_text else 0
+    out = np.empty(max(cap, 1), dtype=np.uint8)
+    rc = lib.td_utf8_host(buf.ctypes.data if len(buf) else None, o.ctypes.data if len(o) else None, n_docs, policy,
+                          out.ctypes.data if want_text else None, cap, ooff.ctypes.data, flags.ctypes.data, first.ctypes.data, nbad.ctypes.data,
+                          counts.ctypes.data)
+    if rc != TD_OK:
+        ex = TokenDaggerHipError(rc, "td_utf8_host: output capacity too small" if rc == TD_E_CAPACITY else "td_utf8_host: invalid offsets or arguments")
+        ex.counts = counts
+        raise ex
+    return (out[:int(counts[0])] if want_text else None), ooff, flags[:n_docs], first[:n_docs], nbad[:n_docs], counts
 
 
 class NgramSet:
@@ -1886,6 +1940,59 @@ class HipTokenizer:
                 break
         self._check(rc)
         return ids[:int(toff[-1])], toff, (norm[:int(counts[0])] if return_text else None), noff, changed[:n_docs], counts
+
+    # ---- UTF-8 validation and repair ----------------------------------------------------------------------------
+    def utf8_check(self, d_text: int, n_bytes: int, d_doc_offsets: int, n_docs: int, d_flags: int, d_first_bad: int, d_counts: int, stream: int):
+        """td_utf8_check_device: raw device pointers (d_first_bad may be 0), asynchronous on `stream`, which must not be the null stream;
+        d_flags uint8[n_docs] (0: well-formed), d_first_bad int64[n_docs], d_counts int64[8]; check with device_status(stream)."""
+        self._check(self._lib.td_utf8_check_device(self._h, d_text or None, n_bytes, d_doc_offsets or None, n_docs, d_flags or None,
+                                                   d_first_bad or None, d_counts or None, stream or None))
+
+    def utf8_device(self, d_text: int, n_bytes: int, d_doc_offsets: int, n_docs: int, policy: int, d_out: int, out_capacity: int,
+                    d_out_doc_offsets: int, d_flags: int, d_first_bad: int, d_n_bad: int, d_counts: int, stream: int):
+        """td_utf8_device: raw device pointers (d_flags, d_first_bad, d_n_bad may be 0), asynchronous on `stream`; check with
+        device_status(stream)."""
+        self._check(self._lib.td_utf8_device(self._h, d_text or None, n_bytes, d_doc_offsets or None, n_docs, policy, d_out or None, out_capacity,
+                                             d_out_doc_offsets or None, d_flags or None, d_first_bad or None, d_n_bad or None, d_counts or None,
+                                             stream or None))
+
+    def utf8(self, text, doc_offsets, policy: int = TD_UTF8_REPLACE, capacity: int | None = None, want_text: bool = True,
+             check_only: bool = False):
+        """td_utf8: utf8_host's arguments and results, computed on the device.  check_only: no output, no offsets and no n_bad are asked
+        for, which makes the call the check (one pass at read speed) -> (None, None, flags, first_bad, None, counts with [1] alone)."""
+        buf, o, n_docs, ooff, flags, first, nbad, counts = _utf8_args(text, doc_offsets)
+        want_text = want_text and not check_only
+        cap = _utf8_capacity(buf, o, policy, capacity) if want_text else 0
+        out = np.empty(max(cap, 1), dtype=np.uint8)
+        rc = self._lib.td_utf8(self._h, buf.ctypes.data if len(buf) else None, o.ctypes.data, n_docs, policy, out.ctypes.data if want_text else None,
+                               cap, None if check_only else ooff.ctypes.data, flags.ctypes.data, first.ctypes.data,
+                               None if check_only else nbad.ctypes.data, counts.ctypes.data)
+        if rc != TD_OK:
+            ex = TokenDaggerHipError(rc, self._lib.td_last_error(self._h).decode("utf-8", "replace"))
+            ex.counts = counts
+            raise ex
+        if check_only:
+            return None, None, flags[:n_docs], first[:n_docs], None, counts
+        return (out[:int(counts[0])] if want_text else None), ooff, flags[:n_docs], first[:n_docs], nbad[:n_docs], counts
+
+    def encode_batch_utf8(self, text, doc_offsets, mode: int = TD_MODE_ENCODE, policy: int = TD_UTF8_REPLACE, return_text: bool = False):
+        """td_encode_batch_utf8: check, repair where a document is flagged, encode -> (ids int32, tok_offsets int64[n_docs + 1],
+        fixed_text uint8 | None, fixed_doc_offsets int64[n_docs + 1], flags uint8[n_docs], first_bad int64[n_docs], n_bad int64[n_docs],
+        counts int64[8]).  Offsets refer to the repaired text."""
+        buf, o, n_docs, foff, flags, first, nbad, counts = _utf8_args(text, doc_offsets)
+        n = int(o[-1]) if len(o) and 0 <= int(o[-1]) <= len(buf) else 0
+        toff = np.zeros(n_docs + 1, dtype=np.int64)
+        for cap in (n + 64, 3 * n + 64):  # (room for three times the bytes only when the first call asks for it)
+            ids = np.empty(cap, dtype=np.int32)
+            fixed = np.empty(cap, dtype=np.uint8) if return_text else None
+            rc = self._lib.td_encode_batch_utf8(self._h, buf.ctypes.data if len(buf) else None, o.ctypes.data, n_docs, mode, policy, ids.ctypes.data,
+                                                cap, toff.ctypes.data, _ptr(fixed), cap if return_text else 0, foff.ctypes.data,
+                                                flags.ctypes.data, first.ctypes.data, nbad.ctypes.data, counts.ctypes.data)
+            if rc != TD_E_CAPACITY:
+                break
+        self._check(rc)
+        return (ids[:int(toff[-1])], toff, (fixed[:int(counts[0])] if return_text else None), foff, flags[:n_docs], first[:n_docs],
+                nbad[:n_docs], counts)
 
     # ---- decode rows (td_decode_spec) ---------------------------------------------------------------------------
     def decode_rows(self, ids, spec: DecodeSpec, tok_offsets=None, lengths=None, n_segs: int | None = None, capacity: int | None = None):

@@ -278,6 +278,9 @@ struct td_tokenizer {
     // NFC normalisation (td_nfc.hip): the bad-offsets / full words, the tiles' output bytes and bases, flags and changed where the
     // caller has none; the host entry points' counts, normalised text and its document offsets on the device
     DevBuf nfc_head, nfc_tiles, nfc_flags, nfc_changed, nfc_counts, nfc_out, nfc_out_off;
+    // UTF-8 validation and repair (td_utf8.hip): the bad-offsets / full words, the tiles' output bytes and bases, a byte a window for the
+    // documents' edges, flags where the caller has none; the host entry points' first_bad, n_bad, counts, repaired text and its offsets
+    DevBuf utf8_head, utf8_tiles, utf8_dirty, utf8_flags, utf8_first, utf8_nbad, utf8_counts, utf8_out, utf8_out_off;
     int64_t mh_table_perm = 0;     // 0: no table yet
     uint64_t mh_table_seed = 0;
     std::vector<int64_t> dcr_key;  // flags, then the distinct listed ids with their bits (sorted); empty: no table yet

@@ -125,6 +125,33 @@ class NormalizedText(NamedTuple):
                          # opaque bytes, the longest segment in code points, 0
 
 
+class ValidatedText(NamedTuple):
+    """Tokenizer.validate_batch (the contract: include/tokendagger_hip.h, td_utf8*)."""
+    flags: np.ndarray      # uint8 [n_docs]: 0 = the document is well-formed UTF-8
+    first_bad: np.ndarray  # int64 [n_docs]: the offset inside the document of its first ill-formed subpart, or -1
+    counts: np.ndarray     # int64 [8]: counts[1] = documents ill-formed; the rest is 0 (the check counts nothing else)
+
+
+class RepairedText(NamedTuple):
+    """Tokenizer.repair_batch: text + offsets go to every bulk method as they stand."""
+    text: np.ndarray       # uint8: the documents' bytes.decode("utf-8", errors).encode("utf-8"), concatenated
+    offsets: np.ndarray    # int64 [n_docs + 1]
+    flags: np.ndarray      # uint8 [n_docs]: 0 = the document was well-formed
+    first_bad: np.ndarray  # int64 [n_docs]
+    n_bad: np.ndarray      # int64 [n_docs]: the document's ill-formed subparts
+    counts: np.ndarray     # int64 [8]: output bytes, documents ill-formed, subparts, bytes in subparts, documents that begin with a
+                           # continuation byte, documents whose last unit is a subpart led by a lead byte, 0, 0
+
+
+_UTF8_ERRORS = {"replace": _capi.TD_UTF8_REPLACE, "ignore": _capi.TD_UTF8_IGNORE}
+
+
+def _utf8_policy(errors):
+    if errors not in _UTF8_ERRORS:
+        raise ValueError(f"errors must be 'replace' or 'ignore', not {errors!r}")
+    return _UTF8_ERRORS[errors]
+
+
 _NORMALIZERS = (None, "NFC")
 
 
@@ -390,6 +417,45 @@ class Tokenizer:
         except _capi.TokenDaggerHipError as ex:
             raise TokenDaggerError(f"Encoding failed: {ex}")
         return (ids, toff, NormalizedText(norm, noff, None, changed, counts)) if return_text else (ids, toff)
+
+    # ------------------------------------------------------------------ UTF-8 repair -----------
+    # The bulk methods take raw bytes; the reference only ever sees str.  On the device: a check at read speed, and
+    # bytes.decode("utf-8", errors).encode("utf-8") per document.  Repair comes before normalize_batch when both are wanted.
+    def validate_batch(self, text: np.ndarray | bytes, offsets: np.ndarray) -> ValidatedText:
+        """Concatenated bytes + int64 document offsets -> which documents are well-formed UTF-8, on the GPU: an upload and the check
+        (td_utf8_check_device's kernels, one pass over the text); counts[1] alone is counted."""
+        hip = _capi.HipTokenizer.borrow(self._core_bpe.handle())
+        buf = np.frombuffer(text, dtype=np.uint8) if isinstance(text, (bytes, bytearray)) else text
+        try:
+            _, _, flags, first, _, counts = hip.utf8(buf, np.asarray(offsets, dtype=np.int64), check_only=True)
+        except _capi.TokenDaggerHipError as ex:
+            raise TokenDaggerError(f"Validation failed: {ex}")
+        return ValidatedText(flags, first, counts)
+
+    def repair_batch(self, text: np.ndarray | bytes, offsets: np.ndarray, errors: str = "replace") -> RepairedText:
+        """Concatenated bytes + int64 document offsets -> well-formed UTF-8 with its offsets, on the GPU."""
+        policy = _utf8_policy(errors)
+        hip = _capi.HipTokenizer.borrow(self._core_bpe.handle())
+        buf = np.frombuffer(text, dtype=np.uint8) if isinstance(text, (bytes, bytearray)) else text
+        try:
+            return RepairedText(*hip.utf8(buf, np.asarray(offsets, dtype=np.int64), policy))
+        except _capi.TokenDaggerHipError as ex:
+            raise TokenDaggerError(f"Repair failed: {ex}")
+
+    def encode_batch_to_numpy_repaired(self, text: np.ndarray | bytes, offsets: np.ndarray, *, errors: str = "replace", ordinary: bool = False,
+                                       return_text: bool = False):
+        """encode_batch_to_numpy behind the UTF-8 check: well-formed text is encoded as it lies on the device, anything else is repaired
+        there first -> (int32 ids, int64 token offsets), with return_text also a RepairedText."""
+        policy = _utf8_policy(errors)
+        hip = _capi.HipTokenizer.borrow(self._core_bpe.handle())
+        buf = np.frombuffer(text, dtype=np.uint8) if isinstance(text, (bytes, bytearray)) else text
+        try:
+            ids, toff, fixed, foff, flags, first, nbad, counts = hip.encode_batch_utf8(buf, np.asarray(offsets, dtype=np.int64),
+                                                                                        MODE_ORDINARY if ordinary else MODE_ENCODE, policy,
+                                                                                        return_text=return_text)
+        except _capi.TokenDaggerHipError as ex:
+            raise TokenDaggerError(f"Encoding failed: {ex}")
+        return (ids, toff, RepairedText(fixed, foff, flags, first, nbad, counts)) if return_text else (ids, toff)
 
     # ------------------------------------------------------------------ offsets ----------------
     # The start of a token is where its text begins in its document: in "bytes", the offset of its first UTF-8 byte; in "chars",
