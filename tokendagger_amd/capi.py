@@ -822,18 +822,44 @@ def nfc_info(what: int) -> int:
     return int(load_library().td_nfc_info(what))
 
 
-def _nfc_args(text, doc_offsets):
-    """-> (text uint8, offsets int64, n_docs, out_doc_offsets int64[n_docs + 1], flags uint8[n_docs], changed uint8[n_docs], counts int64[8])"""
+_NFC_PER_DOC = (np.uint8, np.uint8)            # flags, changed
+_UTF8_PER_DOC = (np.uint8, np.int64, np.int64)  # flags, first_bad, n_bad
+
+
+def _rewrite_args(text, doc_offsets, per_doc):
+    """The arrays of a text rewrite (NFC, UTF-8) -> (text uint8, offsets int64, n_docs, out_doc_offsets int64[n_docs + 1], an array
+    [n_docs] of each dtype in per_doc, counts int64[8])"""
     buf = _as_u8(text)
     o = np.ascontiguousarray(doc_offsets, dtype=np.int64)
     n_docs = len(o) - 1
-    return (buf, o, n_docs, np.zeros(n_docs + 1, dtype=np.int64), np.zeros(max(n_docs, 1), dtype=np.uint8),
-            np.zeros(max(n_docs, 1), dtype=np.uint8), np.zeros(8, dtype=np.int64))
+    return (buf, o, n_docs, np.zeros(n_docs + 1, dtype=np.int64), *(np.zeros(max(n_docs, 1), dtype=d) for d in per_doc),
+            np.zeros(8, dtype=np.int64))
 
 
-def _nfc_capacity(buf, o, capacity):
-    """The bytes a normalised text can need (three times the documents' bytes) where the caller names none."""
-    return 3 * int(o[-1]) if capacity is None and len(o) and 0 <= int(o[-1]) <= len(buf) else int(capacity or 0)
+def _rewrite_capacity(buf, o, capacity, growth=3):
+    """The bytes a rewritten text can need where the caller names none: `growth` times the documents' bytes (three for NFC and for
+    UTF-8 under REPLACE, one under IGNORE)."""
+    return growth * int(o[-1]) if capacity is None and len(o) and 0 <= int(o[-1]) <= len(buf) else int(capacity or 0)
+
+
+def _raise_with_counts(rc, message, counts):
+    ex = TokenDaggerHipError(rc, message)
+    ex.counts = counts
+    raise ex
+
+
+def _encode_rewritten(buf, o, n_docs, return_text, call):
+    """td_encode_batch_nfc / _utf8: call(ids, cap, tok_offsets, text | None, text_cap) -> rc, with room for the text's own bytes and,
+    only when that call asks for it, for three times as many (a rewrite rarely grows a text) -> (rc, ids, tok_offsets, text | None)"""
+    n = int(o[-1]) if len(o) and 0 <= int(o[-1]) <= len(buf) else 0
+    toff = np.zeros(n_docs + 1, dtype=np.int64)
+    for cap in (n + 64, 3 * n + 64):
+        ids = np.empty(cap, dtype=np.int32)
+        out = np.empty(cap, dtype=np.uint8) if return_text else None
+        rc = call(ids.ctypes.data, cap, toff.ctypes.data, _ptr(out), cap if return_text else 0)
+        if rc != TD_E_CAPACITY:
+            break
+    return rc, ids, toff, out
 
 
 def nfc_host(text, doc_offsets, capacity: int | None = None, want_text: bool = True):
@@ -841,17 +867,15 @@ def nfc_host(text, doc_offsets, capacity: int | None = None, want_text: bool = T
     (0: proven NFC), changed uint8[n_docs], counts int64[8] = output bytes, documents not proven, documents changed, segments rewritten,
     code points in them, opaque bytes, longest segment, 0).  want_text=False: the sizing call.  capacity None: three times the input."""
     lib = load_library()
-    buf, o, n_docs, ooff, flags, changed, counts = _nfc_args(text, doc_offsets)
+    buf, o, n_docs, ooff, flags, changed, counts = _rewrite_args(text, doc_offsets, _NFC_PER_DOC)
     if n_docs >= 0 and len(o) and int(o[-1]) > len(buf):
         raise TokenDaggerHipError(TD_E_INVALID, "td_nfc_host: doc_offsets end behind the text")
-    cap = _nfc_capacity(buf, o, capacity) if want_text else 0
+    cap = _rewrite_capacity(buf, o, capacity) if want_text else 0
     out = np.empty(max(cap, 1), dtype=np.uint8)
     rc = lib.td_nfc_host(buf.ctypes.data if len(buf) else None, o.ctypes.data if len(o) else None, n_docs, out.ctypes.data if want_text else None,
                          cap, ooff.ctypes.data, flags.ctypes.data, changed.ctypes.data, counts.ctypes.data)
     if rc != TD_OK:
-        ex = TokenDaggerHipError(rc, "td_nfc_host: output capacity too small" if rc == TD_E_CAPACITY else "td_nfc_host: invalid offsets or arguments")
-        ex.counts = counts
-        raise ex
+        _raise_with_counts(rc, "td_nfc_host: output capacity too small" if rc == TD_E_CAPACITY else "td_nfc_host: invalid offsets or arguments", counts)
     return (out[:int(counts[0])] if want_text else None), ooff, flags[:n_docs], changed[:n_docs], counts
 
 
@@ -860,42 +884,22 @@ TD_UTF8_REPLACE, TD_UTF8_IGNORE = 0, 1
 EXPORTS_UTF8 = ["td_utf8_host", "td_utf8_check_device", "td_utf8_device", "td_utf8", "td_encode_batch_utf8"]
 
 
-def _utf8_args(text, doc_offsets):
-    """-> (text uint8, offsets int64, n_docs, out_doc_offsets int64[n_docs + 1], flags uint8[n_docs], first_bad int64[n_docs], n_bad
-    int64[n_docs], counts int64[8])"""
-    buf = _as_u8(text)
-    o = np.ascontiguousarray(doc_offsets, dtype=np.int64)
-    n_docs = len(o) - 1
-    return (buf, o, n_docs, np.zeros(n_docs + 1, dtype=np.int64), np.zeros(max(n_docs, 1), dtype=np.uint8),
-            np.zeros(max(n_docs, 1), dtype=np.int64), np.zeros(max(n_docs, 1), dtype=np.int64), np.zeros(8, dtype=np.int64))
-
-
-def _utf8_capacity(buf, o, policy, capacity):
-    """The bytes a repaired text can need (three times the documents' bytes under REPLACE, their bytes under IGNORE) where the caller
-    names none."""
-    if capacity is None and len(o) and 0 <= int(o[-1]) <= len(buf):
-        return (1 if policy == TD_UTF8_IGNORE else 3) * int(o[-1])
-    return int(capacity or 0)
-
-
 def utf8_host(text, doc_offsets, policy: int = TD_UTF8_REPLACE, capacity: int | None = None, want_text: bool = True):
     """td_utf8_host (host only, no device) -> (text uint8[counts[0]] | None, out_doc_offsets int64[n_docs + 1], flags uint8[n_docs]
     (0: well-formed), first_bad int64[n_docs] (-1: none), n_bad int64[n_docs], counts int64[8] = output bytes, documents ill-formed,
     subparts, bytes in subparts, documents that begin with a continuation byte, documents that end in a cut character, 0, 0).
     want_text=False: the sizing call.  capacity None: what the policy can need."""
     lib = load_library()
-    buf, o, n_docs, ooff, flags, first, nbad, counts = _utf8_args(text, doc_offsets)
+    buf, o, n_docs, ooff, flags, first, nbad, counts = _rewrite_args(text, doc_offsets, _UTF8_PER_DOC)
     if n_docs >= 0 and len(o) and int(o[-1]) > len(buf):
         raise TokenDaggerHipError(TD_E_INVALID, "td_utf8_host: doc_offsets end behind the text")
-    cap = _utf8_capacity(buf, o, policy, capacity) if want_text else 0
+    cap = _rewrite_capacity(buf, o, capacity, 1 if policy == TD_UTF8_IGNORE else 3) if want_text else 0
     out = np.empty(max(cap, 1), dtype=np.uint8)
     rc = lib.td_utf8_host(buf.ctypes.data if len(buf) else None, o.ctypes.data if len(o) else None, n_docs, policy,
                           out.ctypes.data if want_text else None, cap, ooff.ctypes.data, flags.ctypes.data, first.ctypes.data, nbad.ctypes.data,
                           counts.ctypes.data)
     if rc != TD_OK:
-        ex = TokenDaggerHipError(rc, "td_utf8_host: output capacity too small" if rc == TD_E_CAPACITY else "td_utf8_host: invalid offsets or arguments")
-        ex.counts = counts
-        raise ex
+        _raise_with_counts(rc, "td_utf8_host: output capacity too small" if rc == TD_E_CAPACITY else "td_utf8_host: invalid offsets or arguments", counts)
     return (out[:int(counts[0])] if want_text else None), ooff, flags[:n_docs], first[:n_docs], nbad[:n_docs], counts
 
 
@@ -1912,32 +1916,23 @@ class HipTokenizer:
 
     def nfc(self, text, doc_offsets, capacity: int | None = None, want_text: bool = True):
         """td_nfc: nfc_host's arguments and results, computed on the device."""
-        buf, o, n_docs, ooff, flags, changed, counts = _nfc_args(text, doc_offsets)
-        cap = _nfc_capacity(buf, o, capacity) if want_text else 0
+        buf, o, n_docs, ooff, flags, changed, counts = _rewrite_args(text, doc_offsets, _NFC_PER_DOC)
+        cap = _rewrite_capacity(buf, o, capacity) if want_text else 0
         out = np.empty(max(cap, 1), dtype=np.uint8)
         rc = self._lib.td_nfc(self._h, buf.ctypes.data if len(buf) else None, o.ctypes.data, n_docs, out.ctypes.data if want_text else None, cap,
                               ooff.ctypes.data, flags.ctypes.data, changed.ctypes.data, counts.ctypes.data)
         if rc != TD_OK:
-            ex = TokenDaggerHipError(rc, self._lib.td_last_error(self._h).decode("utf-8", "replace"))
-            ex.counts = counts
-            raise ex
+            _raise_with_counts(rc, self._lib.td_last_error(self._h).decode("utf-8", "replace"), counts)
         return (out[:int(counts[0])] if want_text else None), ooff, flags[:n_docs], changed[:n_docs], counts
 
     def encode_batch_nfc(self, text, doc_offsets, mode: int = TD_MODE_ENCODE, return_text: bool = False):
         """td_encode_batch_nfc: check, normalise where a document is flagged, encode -> (ids int32, tok_offsets int64[n_docs + 1],
         norm_text uint8 | None, norm_doc_offsets int64[n_docs + 1], changed uint8[n_docs], counts int64[8]).  Offsets refer to the
         normalised text."""
-        buf, o, n_docs, noff, _, changed, counts = _nfc_args(text, doc_offsets)
-        n = int(o[-1]) if len(o) and 0 <= int(o[-1]) <= len(buf) else 0
-        toff = np.zeros(n_docs + 1, dtype=np.int64)
-        for cap in (n + 64, 3 * n + 64):  # (NFC rarely grows a text: room for three times its bytes only when the first call asks for it)
-            ids = np.empty(cap, dtype=np.int32)
-            norm = np.empty(cap, dtype=np.uint8) if return_text else None
-            rc = self._lib.td_encode_batch_nfc(self._h, buf.ctypes.data if len(buf) else None, o.ctypes.data, n_docs, mode, ids.ctypes.data,
-                                               cap, toff.ctypes.data, _ptr(norm), cap if return_text else 0, noff.ctypes.data,
-                                               changed.ctypes.data, counts.ctypes.data)
-            if rc != TD_E_CAPACITY:
-                break
+        buf, o, n_docs, noff, _, changed, counts = _rewrite_args(text, doc_offsets, _NFC_PER_DOC)
+        rc, ids, toff, norm = _encode_rewritten(buf, o, n_docs, return_text, lambda ids, cap, toff, norm, norm_cap: self._lib.td_encode_batch_nfc(
+            self._h, buf.ctypes.data if len(buf) else None, o.ctypes.data, n_docs, mode, ids, cap, toff, norm, norm_cap, noff.ctypes.data,
+            changed.ctypes.data, counts.ctypes.data))
         self._check(rc)
         return ids[:int(toff[-1])], toff, (norm[:int(counts[0])] if return_text else None), noff, changed[:n_docs], counts
 
@@ -1960,17 +1955,15 @@ class HipTokenizer:
              check_only: bool = False):
         """td_utf8: utf8_host's arguments and results, computed on the device.  check_only: no output, no offsets and no n_bad are asked
         for, which makes the call the check (one pass at read speed) -> (None, None, flags, first_bad, None, counts with [1] alone)."""
-        buf, o, n_docs, ooff, flags, first, nbad, counts = _utf8_args(text, doc_offsets)
+        buf, o, n_docs, ooff, flags, first, nbad, counts = _rewrite_args(text, doc_offsets, _UTF8_PER_DOC)
         want_text = want_text and not check_only
-        cap = _utf8_capacity(buf, o, policy, capacity) if want_text else 0
+        cap = _rewrite_capacity(buf, o, capacity, 1 if policy == TD_UTF8_IGNORE else 3) if want_text else 0
         out = np.empty(max(cap, 1), dtype=np.uint8)
         rc = self._lib.td_utf8(self._h, buf.ctypes.data if len(buf) else None, o.ctypes.data, n_docs, policy, out.ctypes.data if want_text else None,
                                cap, None if check_only else ooff.ctypes.data, flags.ctypes.data, first.ctypes.data,
                                None if check_only else nbad.ctypes.data, counts.ctypes.data)
         if rc != TD_OK:
-            ex = TokenDaggerHipError(rc, self._lib.td_last_error(self._h).decode("utf-8", "replace"))
-            ex.counts = counts
-            raise ex
+            _raise_with_counts(rc, self._lib.td_last_error(self._h).decode("utf-8", "replace"), counts)
         if check_only:
             return None, None, flags[:n_docs], first[:n_docs], None, counts
         return (out[:int(counts[0])] if want_text else None), ooff, flags[:n_docs], first[:n_docs], nbad[:n_docs], counts
@@ -1979,17 +1972,10 @@ class HipTokenizer:
         """td_encode_batch_utf8: check, repair where a document is flagged, encode -> (ids int32, tok_offsets int64[n_docs + 1],
         fixed_text uint8 | None, fixed_doc_offsets int64[n_docs + 1], flags uint8[n_docs], first_bad int64[n_docs], n_bad int64[n_docs],
         counts int64[8]).  Offsets refer to the repaired text."""
-        buf, o, n_docs, foff, flags, first, nbad, counts = _utf8_args(text, doc_offsets)
-        n = int(o[-1]) if len(o) and 0 <= int(o[-1]) <= len(buf) else 0
-        toff = np.zeros(n_docs + 1, dtype=np.int64)
-        for cap in (n + 64, 3 * n + 64):  # (room for three times the bytes only when the first call asks for it)
-            ids = np.empty(cap, dtype=np.int32)
-            fixed = np.empty(cap, dtype=np.uint8) if return_text else None
-            rc = self._lib.td_encode_batch_utf8(self._h, buf.ctypes.data if len(buf) else None, o.ctypes.data, n_docs, mode, policy, ids.ctypes.data,
-                                                cap, toff.ctypes.data, _ptr(fixed), cap if return_text else 0, foff.ctypes.data,
-                                                flags.ctypes.data, first.ctypes.data, nbad.ctypes.data, counts.ctypes.data)
-            if rc != TD_E_CAPACITY:
-                break
+        buf, o, n_docs, foff, flags, first, nbad, counts = _rewrite_args(text, doc_offsets, _UTF8_PER_DOC)
+        rc, ids, toff, fixed = _encode_rewritten(buf, o, n_docs, return_text, lambda ids, cap, toff, fixed, fixed_cap: self._lib.td_encode_batch_utf8(
+            self._h, buf.ctypes.data if len(buf) else None, o.ctypes.data, n_docs, mode, policy, ids, cap, toff, fixed, fixed_cap, foff.ctypes.data,
+            flags.ctypes.data, first.ctypes.data, nbad.ctypes.data, counts.ctypes.data))
         self._check(rc)
         return (ids[:int(toff[-1])], toff, (fixed[:int(counts[0])] if return_text else None), foff, flags[:n_docs], first[:n_docs],
                 nbad[:n_docs], counts)

@@ -296,19 +296,12 @@ int rows_stage_host_src(td_tokenizer* t, const td_rows_labels* lab, int64_t tota
 int td::rows_encode_locked(td_tokenizer* t, const uint8_t* text, const int64_t* doc_offsets, int64_t n_docs, int mode, int64_t& dev_cap,
                        hipStream_t& s) {
     int rc;
-    if ((rc = check_offsets(t, "doc_offsets", doc_offsets, n_docs, text))) return rc;
+    if ((rc = stage_host_text(t, text, doc_offsets, n_docs, s))) return rc;
     const int64_t n = doc_offsets[n_docs];
     dev_cap = std::max<int64_t>(n, 1);  // (at most one id per byte)
-    if ((rc = ensure(t, t->h2d_text, (size_t)n + 64))) return rc;
-    if ((rc = ensure(t, t->h2d_offs, (size_t)(n_docs + 1) * 8))) return rc;
     if ((rc = ensure(t, t->d_offsets, (size_t)(n_docs + 1) * 8))) return rc;
     if ((rc = ensure(t, t->d_tokens, (size_t)dev_cap * 4))) return rc;
-    if ((rc = own_streams(t))) return rc;
-    s = t->s_own;
-    if ((rc = order_before(t, s))) return rc;
     if (n > 0) {
-        HIP_TRY(t, hipMemcpyAsync(t->h2d_text.p, text, (size_t)n, hipMemcpyHostToDevice, s));
-        HIP_TRY(t, hipMemcpyAsync(t->h2d_offs.p, doc_offsets, (size_t)(n_docs + 1) * 8, hipMemcpyHostToDevice, s));
         if ((rc = encode_device_locked(t, t->h2d_text.p, n, t->h2d_offs.p, n_docs, mode, t->d_tokens.p, dev_cap, t->d_offsets.p, s))) return rc;
     } else {  // (nothing but empty documents: no encode)
         HIP_TRY(t, hipMemsetAsync(t->d_offsets.p, 0, (size_t)(n_docs + 1) * 8, s));

@@ -18,6 +18,7 @@
 
 #include "../../include/tokendagger_hip.h"
 #include "td_kernels.h"
+#include "td_rewrite_args.h"
 #include "td_tables.h"
 
 namespace td {
@@ -192,6 +193,12 @@ struct SharedTables {
     }
 };
 
+// What either text rewrite keeps on the device: the bad-offsets / full words, the tiles' output bytes and bases, flags where the caller
+// has none; the host entry points' counts, rewritten text and its document offsets
+struct RewriteBufs {
+    DevBuf head, tiles, flags, counts, out, out_off;
+};
+
 // The tunables: td_create reads them from the environment (from_env), td_set_option changes most of them, td_clone copies them all.
 struct Options {
     bool fused = true;            // pre-tokenizer and lookup in one pass over the text (TD_OPT_FUSED; TD_FUSED=0 turns it off)
@@ -275,12 +282,10 @@ struct td_tokenizer {
     // MinHash signatures (td_minhash.hip): the bad-offsets word and the document counts, the permutation table and what it was built
     // for; the host entry points' signatures, band keys and counts on the device
     DevBuf mh_head, mh_table, mh_sig, mh_keys, mh_counts;
-    // NFC normalisation (td_nfc.hip): the bad-offsets / full words, the tiles' output bytes and bases, flags and changed where the
-    // caller has none; the host entry points' counts, normalised text and its document offsets on the device
-    DevBuf nfc_head, nfc_tiles, nfc_flags, nfc_changed, nfc_counts, nfc_out, nfc_out_off;
-    // UTF-8 validation and repair (td_utf8.hip): the bad-offsets / full words, the tiles' output bytes and bases, a byte a window for the
-    // documents' edges, flags where the caller has none; the host entry points' first_bad, n_bad, counts, repaired text and its offsets
-    DevBuf utf8_head, utf8_tiles, utf8_dirty, utf8_flags, utf8_first, utf8_nbad, utf8_counts, utf8_out, utf8_out_off;
+    // The text rewrites, NFC normalisation (td_nfc.hip) and UTF-8 validation and repair (td_utf8.hip): each one's RewriteBufs; changed
+    // where the caller has none; a byte a window for the documents' edges, the host entry points' first_bad and n_bad on the device
+    RewriteBufs nfc, utf8;
+    DevBuf nfc_changed, utf8_dirty, utf8_first, utf8_nbad;
     int64_t mh_table_perm = 0;     // 0: no table yet
     uint64_t mh_table_seed = 0;
     std::vector<int64_t> dcr_key;  // flags, then the distinct listed ids with their bits (sorted); empty: no table yet
@@ -412,6 +417,37 @@ int label_rows_to_host(td_tokenizer* t, const void* d_ids, const void* d_src, co
 // becomes, into d_tokens (room for dev_cap ids) / d_offsets; the encode's errors are returned as such before anything reads its ids.
 int rows_encode_locked(td_tokenizer* t, const uint8_t* text, const int64_t* doc_offsets, int64_t n_docs, int mode, int64_t& dev_cap,
                        hipStream_t& s);
+// ---- defined in td_api_rewrite.cpp: what the text rewrites' entry points (td_api_nfc.cpp, td_api_utf8.cpp) share -------------------------
+// The host forms' start (rows_encode_locked's too): the checks of the caller's text and offsets, and their upload into h2d_text /
+// h2d_offs on the handle's own stream, which `s` becomes.
+int stage_host_text(td_tokenizer* t, const uint8_t* text, const int64_t* doc_offsets, int64_t n_docs, hipStream_t& s);
+// One launch sequence of a pass on `s`.  `a` is the pass's arguments, zeroed but for what the pass adds; the text, the offsets, the flags
+// and the counts of c go into it with w's head and where errors are raised.  rewrite_check_locked (launch_*_check: c's outputs are not
+// looked at) zeroes the head on `s`; rewrite_locked (launch_nfc / launch_utf8 with `phases`) zeroes it in front of a measure phase and
+// adds c's outputs, w's tiles and, where c has no flags, w's.  launch() enqueues the pass's kernels.
+struct RewriteCall {
+    const void* d_text;
+    int64_t n_bytes;
+    const void* d_off;
+    int64_t n_docs;
+    void *d_flags, *d_counts, *d_out;
+    int64_t out_capacity;
+    void* d_out_off;
+};
+int rewrite_check_locked(td_tokenizer* t, RewriteBufs& w, RewriteArgs& a, const RewriteCall& c, hipStream_t s, const std::function<int()>& launch);
+int rewrite_locked(td_tokenizer* t, RewriteBufs& w, RewriteArgs& a, const RewriteCall& c, int phases, hipStream_t s, const std::function<int()>& launch);
+// check(): the pass's check of h2d_text / h2d_offs into w.flags and w.counts (both grown here); then the status, and w.counts to `counts`.
+int rewrite_check_staged(td_tokenizer* t, RewriteBufs& w, int64_t n_docs, int64_t* counts, hipStream_t s, const std::function<int()>& check);
+// run(d_out, out_capacity, phases): the pass's phases on h2d_text / h2d_offs (n bytes) into w.flags, w.counts, w.out_off and its own
+// per-document buffers.  Measured first, w.counts comes back in `counts`; where `write` is set, then written into w.out / w.out_off.
+// w.out is sized from counts[0], the bytes the text needs, not from the 3 x bound, which `what`'s total is held to.
+int rewrite_staged(td_tokenizer* t, RewriteBufs& w, int64_t n, int64_t n_docs, int64_t* counts, bool write, const char* what, hipStream_t s,
+                   const std::function<int(void* d_out, int64_t out_capacity, int phases)>& run);
+// The end of td_encode_batch_nfc / _utf8: the rewritten text d_text (the caller's own `text` where it is still h2d_text) of n_enc bytes
+// to out_text where there is one, its encode with d_off into d_tokens / d_offsets, the status, then the offsets and the ids.
+int encode_rewritten(td_tokenizer* t, const uint8_t* text, const void* d_text, const void* d_off, int64_t n_enc, int64_t n_docs, int mode,
+                     const char* text_name, uint8_t* out_text, int64_t text_capacity, int32_t* out_ids, int64_t ids_capacity,
+                     int64_t* out_tok_offsets, hipStream_t s);
 // ---- defined in td_api_labels.cpp ---------------------------------------------------------------------------------------------------
 int labels_outputs_to_host(td_tokenizer* t, int64_t total, int64_t n_docs, int32_t* labels, uint8_t* mask, int64_t* trained_offsets,
                            int64_t* counts, hipStream_t s, const std::function<int(void*, void*, void*, void*)>& launch);

@@ -1,18 +1,13 @@
 // Unicode NFC normalisation (td_nfc.hip): what the kernels, the host library (td_api_nfc.cpp) and the CPU model
 // (tests/twin/nfc_model.cpp) share: the table lookup, the UTF-8 unit decoder, the quick check, the segment scan and the segment
-// normaliser, the kernels' arguments and the tile constants.  The rule is the contract in include/tokendagger_hip.h; the tables are
-// generated/unicode_nfc.inc (tools/gen_unicode_nfc.py).
+// normaliser, and what the pass adds to the rewrites' arguments (td_rewrite_args.h).  The rule is the contract in
+// include/tokendagger_hip.h; the tables are generated/unicode_nfc.inc (tools/gen_unicode_nfc.py).
 #pragma once
-#include <hip/hip_runtime_api.h>
-#include <stdint.h>
-
 #include "generated/unicode_nfc.inc"  // (the constants; the tables themselves where TD_NFC_TABLE is defined)
+#include "td_rewrite_args.h"
 
 namespace td {
 
-constexpr int NFC_THREADS = 256;               // lanes of a workgroup (RC_THREADS)
-constexpr int NFC_LANE_BYTES = 16;             // the bytes a lane owns a step: one 16-byte load
-constexpr int NFC_TILE = NFC_THREADS * NFC_LANE_BYTES;  // bytes of a workgroup's tile
 constexpr uint32_t NFC_LEAD_MIN = 0xCC;        // the UTF-8 lead byte of U+0300, the lowest code point that is no boundary
 
 struct NfcTables {
@@ -312,29 +307,13 @@ __host__ __device__ inline int64_t nfc_rewrite(const NfcTables& T, const uint8_t
     return sink.n;
 }
 
-// ---- counts[8] ---------------------------------------------------------------------------------------------------------------------------
-enum { NFC_C_BYTES = 0, NFC_C_UNPROVEN = 1, NFC_C_CHANGED = 2, NFC_C_SEGMENTS = 3, NFC_C_CPS = 4, NFC_C_OPAQUE = 5, NFC_C_LONGEST = 6, NFC_C_WORDS = 8 };
+// ---- counts[8], and a lane's modes, under the pass's names (the statement below and the CPU model speak them) ------------------------------
+enum { NFC_C_BYTES = RW_C_BYTES, NFC_C_WORDS = RW_C_WORDS, NFC_MEASURE = RW_MEASURE, NFC_SIZE = RW_SIZE, NFC_WRITE = RW_WRITE };
+enum { NFC_C_UNPROVEN = 1, NFC_C_CHANGED = 2, NFC_C_SEGMENTS = 3, NFC_C_CPS = 4, NFC_C_OPAQUE = 5, NFC_C_LONGEST = 6 };
 
 // ---- the kernels' arguments ---------------------------------------------------------------------------------------------------------------
-// NfcArgs::head, zeroed before the launches: 2^62 - the lowest document with bad offsets (0: none), kept by an atomic maximum; 1 when
-// the output does not fit
-enum { NFC_H_BAD = 0, NFC_H_FULL = 1, NFC_H_WORDS = 4 };
-
-struct NfcArgs {
-    const uint8_t* text;       // [n_bytes]
-    int64_t n_bytes;
-    const int64_t* doc_off;    // [n_docs + 1]
-    int64_t n_docs;
-    uint8_t* flags;            // [n_docs]: the check
-    uint8_t* out;              // [out_capacity]: the normaliser
-    int64_t out_capacity;
-    int64_t* out_doc_off;      // [n_docs + 1]
+struct NfcArgs : RewriteArgs {  // (flags: 0 where the document is proven NFC)
     uint8_t* changed;          // [n_docs] or null
-    unsigned long long* counts;     // [8]
-    unsigned long long* tile_base;  // [tiles + 1]: the tiles' output bytes, then their exclusive prefixes
-    unsigned long long* head;       // [NFC_H_WORDS]
-    int* err;
-    long long* err_pos;
 };
 
 // The bytes >= 0xCC of the window [b, we) (inside the text) for the check: D, ds, de are the lane's document (D < 0: none yet),
@@ -357,8 +336,6 @@ __host__ __device__ inline void nfc_check_window(const NfcArgs& a, const NfcTabl
 struct NfcLaneStats {
     uint32_t segments, cps, opaque, longest;
 };
-
-enum { NFC_MEASURE = 0, NFC_SIZE = 1, NFC_WRITE = 2 };
 
 // The segments that start in the window [b, we) of the text (b < we <= total).  ub(x): the first document of the tile's table that starts
 // behind x, as an index of doc_off.  MEASURE: flags, changed and st.  WRITE: the bytes from out + opos on and the output offsets of

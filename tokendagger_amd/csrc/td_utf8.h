@@ -11,13 +11,12 @@ namespace td {
 // offsets are bad.
 hipError_t launch_utf8_check(const U8Args& a, hipStream_t stream);
 
-// U8_RUN_MEASURE: td_utf8_docs, td_utf8_prepare, td_utf8_tiles<measure>, td_utf8_scan and td_utf8_sums on `stream`: a.flags (not null),
+// RW_RUN_MEASURE: td_utf8_docs, td_utf8_prepare, td_utf8_tiles<measure>, td_utf8_scan and td_utf8_sums on `stream`: a.flags (not null),
 // a.first_bad and a.n_bad (may be null), a.counts, the tiles' places in a.tile_base (room for a word a tile of the text and one more),
 // TD_E_CAPACITY against a.out_capacity, and in a.out_doc_off the entries of the documents that start at the text's end; a.out is not
 // touched.  a.dirty (a byte a window of the text and one more) and a.head are zeroed by the caller on the same stream.
-// U8_RUN_WRITE: td_utf8_tiles<write>: a.out and the rest of a.out_doc_off from what the measure phase left in a.tile_base, a.dirty and
+// RW_RUN_WRITE: td_utf8_tiles<write>: a.out and the rest of a.out_doc_off from what the measure phase left in a.tile_base, a.dirty and
 // a.head (a phase of its own so that a host form can size a.out from counts[0] in between); nothing when the output did not fit.
-enum { U8_RUN_MEASURE = 1, U8_RUN_WRITE = 2 };
 hipError_t launch_utf8(const U8Args& a, hipStream_t stream, int phases);
 
 }  // namespace td

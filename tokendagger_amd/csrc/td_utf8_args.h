@@ -1,16 +1,14 @@
 // UTF-8 validation and repair (td_utf8.hip): what the kernels, the host library (td_api_utf8.cpp), the CPU model
 // (tests/twin/utf8_model.cpp) and the stand-alone sanitizer program (tools/sanitize/utf8_asan.cpp) share: the unit rule (unit length,
-// well-formedness, start test), the window screen, the lane walk, the kernels' arguments and the tile constants.  The rule is the
-// contract in include/tokendagger_hip.h.
+// well-formedness, start test), the window screen, the lane walk, and what the pass adds to the rewrites' arguments
+// (td_rewrite_args.h).  The rule is the contract in include/tokendagger_hip.h.
 #pragma once
-#include <hip/hip_runtime_api.h>
-#include <stdint.h>
 #include <string.h>
+
+#include "td_rewrite_args.h"
 
 namespace td {
 
-constexpr int U8_THREADS = 256;                      // lanes of a workgroup (RC_THREADS)
-constexpr int U8_TILE = U8_THREADS * 16;             // bytes of a workgroup's tile: a window of 16 bytes a lane
 constexpr int U8_REPLACE = 0, U8_IGNORE = 1;         // TD_UTF8_REPLACE, TD_UTF8_IGNORE
 
 // ---- the unit rule -------------------------------------------------------------------------------------------------------------------------
@@ -113,8 +111,9 @@ __host__ __device__ inline bool u8_window_suspect(const uint32_t s[6]) {
     return (err & U8_H) != 0;
 }
 
-// ---- counts[8] -----------------------------------------------------------------------------------------------------------------------------
-enum { U8_C_BYTES = 0, U8_C_DOCS = 1, U8_C_SUBPARTS = 2, U8_C_SUB_BYTES = 3, U8_C_BEGIN_CONT = 4, U8_C_END_LEAD = 5, U8_C_WORDS = 8 };
+// ---- counts[8], and a lane's modes, under the pass's names (the statements below and the CPU model speak them) --------------------------------
+enum { U8_C_BYTES = RW_C_BYTES, U8_C_WORDS = RW_C_WORDS, U8_MEASURE = RW_MEASURE, U8_SIZE = RW_SIZE, U8_WRITE = RW_WRITE };
+enum { U8_C_DOCS = 1, U8_C_SUBPARTS = 2, U8_C_SUB_BYTES = 3, U8_C_BEGIN_CONT = 4, U8_C_END_LEAD = 5 };
 
 // Whether the last unit of the document [ds, de), ds < de, is an ill-formed subpart led by a lead byte (C2 .. F4): a character cut short.
 __host__ __device__ inline bool u8_ends_cut(const uint8_t* text, int64_t ds, int64_t de) {
@@ -128,21 +127,14 @@ __host__ __device__ inline bool u8_ends_cut(const uint8_t* text, int64_t ds, int
 // Here, and not in the host library, so that it compiles without HIP's runtime (tools/sanitize/utf8_asan.cpp).
 enum { U8_HOST_OK = 0, U8_HOST_INVALID = 1, U8_HOST_CAPACITY = 2 };
 
-inline bool u8_overlap(const void* a, int64_t na, const void* b, int64_t nb) {
-    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-    return a && b && na > 0 && nb > 0 && a0 < b0 + (uintptr_t)nb && b0 < a0 + (uintptr_t)na;
-}
-
 // Documents one by one, units one by one.  Argument errors write nothing; an output that does not fit writes counts[0] alone.
 inline int u8_host(const uint8_t* text, const int64_t* doc_offsets, int64_t n_docs, int policy, uint8_t* out, int64_t out_capacity,
                    int64_t* out_doc_offsets, uint8_t* flags, int64_t* first_bad, int64_t* n_bad, int64_t* counts) {
     if (!doc_offsets || !counts || n_docs < 0 || out_capacity < 0 || (!out && out_capacity != 0) || (policy != U8_REPLACE && policy != U8_IGNORE))
         return U8_HOST_INVALID;
-    if (doc_offsets[0] != 0) return U8_HOST_INVALID;
-    for (int64_t d = 0; d < n_docs; ++d)
-        if (doc_offsets[d + 1] < doc_offsets[d]) return U8_HOST_INVALID;
+    if (!rewrite_offsets_ok(doc_offsets, n_docs)) return U8_HOST_INVALID;
     const int64_t total = doc_offsets[n_docs];
-    if ((total > 0 && !text) || u8_overlap(text, total, out, out_capacity)) return U8_HOST_INVALID;
+    if ((total > 0 && !text) || rewrite_overlap(text, total, out, out_capacity)) return U8_HOST_INVALID;
     int64_t c[U8_C_WORDS] = {0, 0, 0, 0, 0, 0, 0, 0};
     for (int pass = out ? 0 : 1; pass < 2; ++pass) {  // with an output: the bytes needed first
         int64_t n = 0;
@@ -191,28 +183,11 @@ inline int u8_host(const uint8_t* text, const int64_t* doc_offsets, int64_t n_do
 }
 
 // ---- the kernels' arguments ----------------------------------------------------------------------------------------------------------------
-// U8Args::head, zeroed before the launches: 2^62 - the lowest document with bad offsets (0: none), kept by an atomic maximum; 1 when
-// the output does not fit
-enum { U8_H_BAD = 0, U8_H_FULL = 1, U8_H_WORDS = 4 };
-
-struct U8Args {
-    const uint8_t* text;       // [n_bytes]
-    int64_t n_bytes;
-    const int64_t* doc_off;    // [n_docs + 1]
-    int64_t n_docs;
+struct U8Args : RewriteArgs {  // (flags: 0 where the document is well-formed)
     int policy;                // U8_REPLACE or U8_IGNORE
-    uint8_t* flags;            // [n_docs]
     unsigned long long* first_bad;  // [n_docs] or null: int64, -1 (all ones) where the document is well-formed, kept by an unsigned minimum
     unsigned long long* n_bad;      // [n_docs] or null
-    uint8_t* out;              // [out_capacity]
-    int64_t out_capacity;
-    int64_t* out_doc_off;      // [n_docs + 1]
-    unsigned long long* counts;     // [8]
-    unsigned long long* tile_base;  // [tiles + 1]: the tiles' output bytes, then their exclusive prefixes
     uint8_t* dirty;            // [windows] or null (the check): 1 where a unit near a document's edge makes a window's bytes ill-formed
-    unsigned long long* head;  // [U8_H_WORDS]
-    int* err;
-    long long* err_pos;
 };
 
 // The windows of a text whose base lies `shift` bytes behind a 16-byte aligned address: window g is text[16 g - shift, 16 g - shift + 16).
@@ -240,8 +215,6 @@ __host__ __device__ inline void u8_doc_edges(const uint8_t* text, int64_t ds, in
 struct U8LaneStats {
     uint32_t subparts, sub_bytes;
 };
-
-enum { U8_MEASURE = 0, U8_SIZE = 1, U8_WRITE = 2 };
 
 // The BYTES of the window [b, we) of the text (b < we <= total): a byte of a well-formed unit is one byte of output, the first byte of
 // an ill-formed subpart is EF BF BD or nothing, its other bytes are nothing.  So a window without a byte of a subpart is a copy.
