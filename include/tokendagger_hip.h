@@ -1070,6 +1070,53 @@ int td_encode_batch_utf8(td_tokenizer* t, const uint8_t* text, const int64_t* do
                          int32_t* out_ids, int64_t ids_capacity, int64_t* out_tok_offsets, uint8_t* fixed_text, int64_t fixed_capacity,
                          int64_t* fixed_doc_offsets, uint8_t* flags, int64_t* first_bad, int64_t* n_bad, int64_t* counts);
 
+/* ---- per-document text statistics for quality filtering (td_textstats.hip) ---------------------------------------------------------------
+ * The heuristic quality filters of Gopher, C4 and FineWeb are thresholds on sums and maxima over the per-byte character classes the
+ * splitter computes.  Text + doc_offsets[n_docs + 1] (int64: from 0, non-decreasing, ending at or below n_bytes) -> stats[n_docs][TD_TS_COLS]
+ * (int64, row-major) and totals[TD_TS_COLS].  No thresholds and no keep / drop policy: the caller builds a mask and hands it to
+ * td_select_docs.  Host and device compile the same statement of the rule (td_textstats_args.h).
+ *   INPUT      Per document d, over text[doc_offsets[d], doc_offsets[d + 1]): the value the splitter's classification (classify_at,
+ *              td_common.h) gives each byte INSIDE that document: a 4-bit class plus F_CONT.  Characters never cross a document start;
+ *              ill-formed bytes are C_OTHER characters.  The classes are those of the handle's tables (the cl100k / Qwen2 / GPT-2 pattern
+ *              kinds read marks as C_OTHER); td_text_stats_host uses the tables as probed, which are the Llama-4 and generic handles'.
+ *   TERMS      A CHARACTER is a byte without F_CONT with the F_CONT bytes behind it.  A SPACE is a character in M_S (\s).  A WORD is a
+ *              maximal run of non-space characters.  The LINES are the pieces of the document between bytes 0x0A (the LF is no part of
+ *              the line); a final empty piece is no line: "a\n\nb\n" has 3 lines, "" has 0.  A line's first / last VISIBLE character
+ *              is its first / last non-space character; a blank line has none.
+ *   COLUMNS    0 BYTES  1 CHARS  2 UPPER (C_UP)  3 LOWER (C_LW)  4 LETTER_OTHER (C_LB)  5 MARK (C_MK)  6 NUMBER (C_NUM)  7 SPACE
+ *              8 NON_ASCII (characters whose first byte is >= 0x80)  9 WORDS  10 WORDS_ALPHA (words with a character in M_L)
+ *              11 WORD_MAX_BYTES (0: no word)  12 LINES  13 LINES_BLANK  14 LINE_MAX_BYTES
+ *              15 LINES_END_TERMINAL (last visible character one of . ! ? " U+201D U+3002 U+FF01 U+FF1F)
+ *              16 LINES_END_ELLIPSIS (last visible character U+2026, or a '.' with ".." directly in front of it inside the line)
+ *              17 LINES_START_BULLET (first visible character one of - * U+2022 U+2023 U+25E6)
+ *              18 HASHES (bytes '#')  19 ELLIPSES (characters U+2026, plus maximal runs of three or more '.' bytes inside the document,
+ *              a run once)  20 CURLY (bytes '{' or '}')
+ *   totals     the sum over all documents of every column but 11 and 14, of which it holds the maximum.
+ *   groups     TD_TS_LOCAL: columns 0 - 9, 12, 18 - 20 (each decided by a character and at most three bytes on either side of it; the text
+ *              is read once).  TD_TS_RUNS: columns 10, 11, 13 - 17 (they need to know how far back the word or the line began: two more
+ *              passes).  Columns of a group that was not asked for are 0.  0, or a value with other bits, is TD_E_INVALID.
+ * Bytes behind the last document are not read.  Results are bitwise reproducible (integer sums and maxima only).  Out of scope:
+ * duplicate-line and duplicate-n-gram fractions, stop-word rules (td_token_counts serves them), built-in thresholds or presets, lengths in
+ * characters for the two maxima. */
+#define TD_TS_COLS 21
+#define TD_TS_LOCAL 1
+#define TD_TS_RUNS 2
+/* The contract's executable statement, on the host (no handle, no device).  totals may be NULL.  Argument errors (offsets that do not
+ * start at 0 or decrease, groups) are TD_E_INVALID and write nothing. */
+int td_text_stats_host(const uint8_t* text, const int64_t* doc_offsets, int64_t n_docs, int groups, int64_t* stats, int64_t* totals);
+/* DEVICE buffers, asynchronously on hip_stream (never the null stream): no synchronisation and no read-back.  d_doc_offsets, d_stats and
+ * d_totals are 8-byte aligned; d_text needs no alignment; d_totals may be NULL.  Offsets that do not start at 0, decrease, are negative or
+ * end above n_bytes raise TD_E_INVALID through td_device_status with err_pos = the lowest such document, and then NOTHING is written. */
+int td_text_stats_device(td_tokenizer* t, const void* d_text, int64_t n_bytes, const void* d_doc_offsets, int64_t n_docs, int groups,
+                         void* d_stats, void* d_totals, void* hip_stream);
+/* Host buffers, synchronously; td_text_stats_host's arguments behind the handle. */
+int td_text_stats(td_tokenizer* t, const uint8_t* text, const int64_t* doc_offsets, int64_t n_docs, int groups, int64_t* stats,
+                  int64_t* totals);
+/* td_encode_batch (TD_MODE_ENCODE / TD_MODE_ORDINARY only) and the statistics of the same upload: the text crosses PCIe once.
+ * out_tok_offsets[n_docs + 1]; totals may be NULL.  Synchronous. */
+int td_encode_batch_text_stats(td_tokenizer* t, const uint8_t* text, const int64_t* doc_offsets, int64_t n_docs, int mode, int groups,
+                               int32_t* out_ids, int64_t ids_capacity, int64_t* out_tok_offsets, int64_t* stats, int64_t* totals);
+
 /* Options. */
 #define TD_OPT_LONG_POOL_BYTES 1 /* scratch for pieces longer than 64 bytes (default max(64 MiB, 2 x input)) */
 #define TD_OPT_PROFILE 2         /* 1: bracket the kernels of every td_encode_device call with HIP events on the

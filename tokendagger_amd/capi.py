@@ -83,6 +83,7 @@ EXPORTS = [
     "td_ngram_matches", "td_encode_batch_ngram_matches",
     "td_minhash_params", "td_minhash_host", "td_minhash_device", "td_minhash", "td_encode_batch_minhash",
     "td_nfc_info", "td_nfc_host", "td_nfc_check_device", "td_nfc_device", "td_nfc", "td_encode_batch_nfc",
+    "td_text_stats_host", "td_text_stats_device", "td_text_stats", "td_encode_batch_text_stats",
 ]
 
 
@@ -258,6 +259,14 @@ def load_library():
     lib.td_utf8.argtypes = [vp, vp, vp, i64, i32, vp, i64, vp, vp, vp, vp, vp]
     lib.td_encode_batch_utf8.restype = i32
     lib.td_encode_batch_utf8.argtypes = [vp, vp, vp, i64, i32, i32, vp, i64, vp, vp, i64, vp, vp, vp, vp, vp]
+    lib.td_text_stats_host.restype = i32
+    lib.td_text_stats_host.argtypes = [vp, vp, i64, i32, vp, vp]
+    lib.td_text_stats_device.restype = i32
+    lib.td_text_stats_device.argtypes = [vp, vp, i64, vp, i64, i32, vp, vp, vp]
+    lib.td_text_stats.restype = i32
+    lib.td_text_stats.argtypes = [vp, vp, vp, i64, i32, vp, vp]
+    lib.td_encode_batch_text_stats.restype = i32
+    lib.td_encode_batch_text_stats.argtypes = [vp, vp, vp, i64, i32, i32, vp, i64, vp, vp, vp]
     lib.td_encode_batch_token_counts.restype = i32
     lib.td_encode_batch_token_counts.argtypes = [vp, vp, vp, i64, i32, vp, vp, vp, vp, ctypes.POINTER(i64)]
     lib.td_comm_unique_id.restype = i32
@@ -901,6 +910,35 @@ def utf8_host(text, doc_offsets, policy: int = TD_UTF8_REPLACE, capacity: int | 
     if rc != TD_OK:
         _raise_with_counts(rc, "td_utf8_host: output capacity too small" if rc == TD_E_CAPACITY else "td_utf8_host: invalid offsets or arguments", counts)
     return (out[:int(counts[0])] if want_text else None), ooff, flags[:n_docs], first[:n_docs], nbad[:n_docs], counts
+
+
+TD_TS_COLS, TD_TS_LOCAL, TD_TS_RUNS = 21, 1, 2
+TD_TS_ALL = TD_TS_LOCAL | TD_TS_RUNS
+# stats[:, c] by name (include/tokendagger_hip.h, COLUMNS)
+TS_COLUMNS = ("bytes", "chars", "upper", "lower", "letter_other", "mark", "number", "space", "non_ascii", "words", "words_alpha",
+              "word_max_bytes", "lines", "lines_blank", "line_max_bytes", "lines_end_terminal", "lines_end_ellipsis", "lines_start_bullet",
+              "hashes", "ellipses", "curly")
+
+
+def _text_stats_args(text, doc_offsets):
+    """-> (text uint8, offsets int64, n_docs, stats int64[max(n_docs, 1), 21], totals int64[21])"""
+    buf = _as_u8(text)
+    o = np.ascontiguousarray(doc_offsets, dtype=np.int64)
+    n_docs = len(o) - 1
+    return buf, o, n_docs, np.zeros((max(n_docs, 1), TD_TS_COLS), dtype=np.int64), np.zeros(TD_TS_COLS, dtype=np.int64)
+
+
+def text_stats_host(text, doc_offsets, groups: int = TD_TS_ALL):
+    """td_text_stats_host (host only, no device) -> (stats int64[n_docs, 21], totals int64[21])."""
+    lib = load_library()
+    buf, o, n_docs, stats, totals = _text_stats_args(text, doc_offsets)
+    if n_docs >= 0 and len(o) and int(o[-1]) > len(buf):
+        raise TokenDaggerHipError(TD_E_INVALID, "td_text_stats_host: doc_offsets end behind the text")
+    rc = lib.td_text_stats_host(buf.ctypes.data if len(buf) else None, o.ctypes.data if len(o) else None, n_docs, groups, stats.ctypes.data,
+                                totals.ctypes.data)
+    if rc != TD_OK:
+        raise TokenDaggerHipError(rc, "td_text_stats_host: invalid offsets, groups or arguments")
+    return stats[:n_docs], totals
 
 
 class NgramSet:
@@ -1979,6 +2017,31 @@ class HipTokenizer:
         self._check(rc)
         return (ids[:int(toff[-1])], toff, (fixed[:int(counts[0])] if return_text else None), foff, flags[:n_docs], first[:n_docs],
                 nbad[:n_docs], counts)
+
+    # ---- per-document text statistics -----------------------------------------------------------------------------
+    def text_stats_device(self, d_text: int, n_bytes: int, d_doc_offsets: int, n_docs: int, groups: int, d_stats: int, d_totals: int, stream: int):
+        """td_text_stats_device: raw device pointers (d_totals may be 0), asynchronous on `stream`, which must not be the null stream;
+        d_stats int64[n_docs, 21], d_totals int64[21]; check with device_status(stream)."""
+        self._check(self._lib.td_text_stats_device(self._h, d_text or None, n_bytes, d_doc_offsets or None, n_docs, groups, d_stats or None,
+                                                   d_totals or None, stream or None))
+
+    def text_stats(self, text, doc_offsets, groups: int = TD_TS_ALL):
+        """td_text_stats: text_stats_host's arguments and results, computed on the device."""
+        buf, o, n_docs, stats, totals = _text_stats_args(text, doc_offsets)
+        self._check(self._lib.td_text_stats(self._h, buf.ctypes.data if len(buf) else None, o.ctypes.data, n_docs, groups, stats.ctypes.data,
+                                            totals.ctypes.data))
+        return stats[:n_docs], totals
+
+    def encode_batch_text_stats(self, text, doc_offsets, mode: int = TD_MODE_ENCODE, groups: int = TD_TS_ALL):
+        """td_encode_batch_text_stats: one upload, the statistics and the encode -> (ids int32, tok_offsets int64[n_docs + 1],
+        stats int64[n_docs, 21], totals int64[21])."""
+        buf, o, n_docs, stats, totals = _text_stats_args(text, doc_offsets)
+        n = int(o[-1]) if len(o) and 0 <= int(o[-1]) <= len(buf) else 0
+        toff = np.zeros(n_docs + 1, dtype=np.int64)
+        ids = np.empty(n + 64, dtype=np.int32)
+        self._check(self._lib.td_encode_batch_text_stats(self._h, buf.ctypes.data if len(buf) else None, o.ctypes.data, n_docs, mode, groups,
+                                                         ids.ctypes.data, len(ids), toff.ctypes.data, stats.ctypes.data, totals.ctypes.data))
+        return ids[:int(toff[-1])], toff, stats[:n_docs], totals
 
     # ---- decode rows (td_decode_spec) ---------------------------------------------------------------------------
     def decode_rows(self, ids, spec: DecodeSpec, tok_offsets=None, lengths=None, n_segs: int | None = None, capacity: int | None = None):

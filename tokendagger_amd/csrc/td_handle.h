@@ -286,6 +286,10 @@ struct td_tokenizer {
     // where the caller has none; a byte a window for the documents' edges, the host entry points' first_bad and n_bad on the device
     RewriteBufs nfc, utf8;
     DevBuf nfc_changed, utf8_dirty, utf8_first, utf8_nbad;
+    // text statistics (td_textstats.hip): the bad-offsets word (its RewriteBufs' head alone), four last positions a tile; the host entry
+    // points' stats and totals on the device
+    RewriteBufs textstats;
+    DevBuf ts_carry, ts_stats, ts_totals;
     int64_t mh_table_perm = 0;     // 0: no table yet
     uint64_t mh_table_seed = 0;
     std::vector<int64_t> dcr_key;  // flags, then the distinct listed ids with their bits (sorted); empty: no table yet

@@ -44,6 +44,19 @@ static const char kGpt2[] =
 static const char kGpt2Possessive[] =  // tiktoken's later spelling of the same language
     "'(?:[sdmt]|ll|ve|re)| ?\\p{L}++| ?\\p{N}++| ?[^\\s\\p{L}\\p{N}]++|\\s++$|\\s+(?!\\S)|\\s";
 
+Tables class_tables() {
+    static const struct Ascii {
+        uint8_t v[128];
+        Ascii() { for (uint32_t c = 0; c < 128; ++c) v[c] = td_ucls_stage2[(uint32_t)td_ucls_stage1[0] * 256u + c]; }
+    } ascii;
+    Tables T;
+    memset(&T, 0, sizeof T);
+    T.ascii_cls = ascii.v;
+    T.ucls1 = td_ucls_stage1;
+    T.ucls2 = td_ucls_stage2;
+    return T;
+}
+
 const char* o200k_pattern() { return kO200k; }
 const char* tekken_pattern() { return kTekken; }
 const char* cl100k_pattern() { return kCl100k; }

@@ -68,6 +68,10 @@ int build_tables(const char* pattern, int64_t n_vocab, const uint8_t* token_byte
                  const int32_t* ranks, int64_t n_special, const uint8_t* special_bytes,
                  const int64_t* special_offsets, const int32_t* special_ranks, HostTables& out, std::string& err);
 
+// The class tables alone, as probed (no pattern's remap): ascii_cls, ucls1 and ucls2 of a Tables whose other members are zero.  What a
+// statement without a handle classifies by (td_text_stats_host).
+Tables class_tables();
+
 // Host reference of the device merge (ids + pair table): appends ids for piece[0,n) to out.
 // Returns TD_OK or TD_E_UNKNOWN_BYTE.  Used for the merge_closed self-check and by the CPU twin.
 int merge_piece_host(const Tables& T, const uint8_t* piece, uint32_t n, std::vector<int32_t>& out);

@@ -143,6 +143,65 @@ class RepairedText(NamedTuple):
                            # continuation byte, documents whose last unit is a subpart led by a lead byte, 0, 0
 
 
+class TextStats:
+    """Tokenizer.text_stats (the contract: include/tokendagger_hip.h, td_text_stats*): the statistics the heuristic quality filters are
+    built from.  No thresholds here: build a mask from the columns and the ratios and hand the kept documents to select_docs."""
+
+    def __init__(self, stats: np.ndarray, totals: np.ndarray):
+        self.stats = stats    # int64 [n_docs, 21]
+        self.totals = totals  # int64 [21]: the columns' sums, the maximum of word_max_bytes and line_max_bytes
+
+    def __getattr__(self, name):  # the named column views: .words, .lines_end_terminal, ... (capi.TS_COLUMNS)
+        if name in _capi.TS_COLUMNS:
+            return self.stats[:, _capi.TS_COLUMNS.index(name)]
+        raise AttributeError(name)
+
+    def _ratio(self, num, den) -> np.ndarray:
+        """num / den per document as float64, 0.0 where den is 0"""
+        num, den = np.asarray(num, dtype=np.float64), np.asarray(den, dtype=np.float64)
+        return np.divide(num, den, out=np.zeros_like(num), where=den != 0)
+
+    @property
+    def mean_word_bytes(self) -> np.ndarray:
+        """(bytes - space characters) / words: the words' mean length in bytes.  Exact where every space character is one byte; a space
+        of two or three bytes (U+00A0, U+3000, ...) leaves its other bytes with the words."""
+        return self._ratio(self.bytes - self.space, self.words)
+
+    @property
+    def alpha_word_fraction(self) -> np.ndarray:
+        return self._ratio(self.words_alpha, self.words)
+
+    @property
+    def terminal_line_fraction(self) -> np.ndarray:
+        return self._ratio(self.lines_end_terminal, self.lines)
+
+    @property
+    def ellipsis_line_fraction(self) -> np.ndarray:
+        return self._ratio(self.lines_end_ellipsis, self.lines)
+
+    @property
+    def bullet_line_fraction(self) -> np.ndarray:
+        return self._ratio(self.lines_start_bullet, self.lines)
+
+    @property
+    def symbol_word_ratio(self) -> np.ndarray:
+        """'#' bytes and ellipses over words"""
+        return self._ratio(self.hashes + self.ellipses, self.words)
+
+    @property
+    def upper_letter_fraction(self) -> np.ndarray:
+        return self._ratio(self.upper, self.upper + self.lower + self.letter_other)
+
+
+_TS_GROUPS = {"all": _capi.TD_TS_ALL, "local": _capi.TD_TS_LOCAL, "runs": _capi.TD_TS_RUNS}
+
+
+def _ts_groups(groups):
+    if groups not in _TS_GROUPS:
+        raise ValueError(f"groups must be 'all', 'local' or 'runs', not {groups!r}")
+    return _TS_GROUPS[groups]
+
+
 _UTF8_ERRORS = {"replace": _capi.TD_UTF8_REPLACE, "ignore": _capi.TD_UTF8_IGNORE}
 
 
@@ -456,6 +515,30 @@ class Tokenizer:
         except _capi.TokenDaggerHipError as ex:
             raise TokenDaggerError(f"Encoding failed: {ex}")
         return (ids, toff, RepairedText(fixed, foff, flags, first, nbad, counts)) if return_text else (ids, toff)
+
+    # ------------------------------------------------------------------ text statistics ---------
+    # What the heuristic quality filters (Gopher, C4, FineWeb) threshold, per document, on the device; "local" are the columns one pass
+    # over the text gives, "runs" the ones that need to know where a word or a line began.
+    def text_stats(self, text: np.ndarray | bytes, offsets: np.ndarray, groups: str = "all") -> TextStats:
+        """Concatenated bytes + int64 document offsets -> TextStats, on the GPU."""
+        g = _ts_groups(groups)
+        hip = _capi.HipTokenizer.borrow(self._core_bpe.handle())
+        buf = np.frombuffer(text, dtype=np.uint8) if isinstance(text, (bytes, bytearray)) else text
+        try:
+            return TextStats(*hip.text_stats(buf, np.asarray(offsets, dtype=np.int64), g))
+        except _capi.TokenDaggerHipError as ex:
+            raise TokenDaggerError(f"Text statistics failed: {ex}")
+
+    def encode_batch_to_numpy_with_stats(self, text: np.ndarray | bytes, offsets: np.ndarray, *, ordinary: bool = False):
+        """encode_batch_to_numpy and text_stats of one upload -> (int32 ids, int64 token offsets, TextStats)."""
+        hip = _capi.HipTokenizer.borrow(self._core_bpe.handle())
+        buf = np.frombuffer(text, dtype=np.uint8) if isinstance(text, (bytes, bytearray)) else text
+        try:
+            ids, toff, stats, totals = hip.encode_batch_text_stats(buf, np.asarray(offsets, dtype=np.int64),
+                                                                   MODE_ORDINARY if ordinary else MODE_ENCODE)
+        except _capi.TokenDaggerHipError as ex:
+            raise TokenDaggerError(f"Encoding failed: {ex}")
+        return ids, toff, TextStats(stats, totals)
 
     # ------------------------------------------------------------------ offsets ----------------
     # The start of a token is where its text begins in its document: in "bytes", the offset of its first UTF-8 byte; in "chars",

@@ -12,6 +12,13 @@ g++ $F $S/tab_asan.cpp $C/td_tables.cpp $C/td_regex.cpp -o /tmp/td_tab_asan
 python $S/vocab_files.py $seed 4000 /tmp/td_vocab_asan
 python $S/patterns.py $seed 20000 /tmp/td_rx_asan
 /tmp/td_tab_asan $seed 300
+# The statements the kernels share with the host, stand-alone (linked with the sanitizers, nothing preloaded): the UTF-8 repair and the
+# text statistics with the CPU model's window walk.
+H="-D__HIP_PLATFORM_AMD__ -I${ROCM_PATH:-/opt/rocm}/include"
+g++ $F $H $S/utf8_asan.cpp -o /tmp/td_utf8_asan
+g++ $F $H $S/textstats_asan.cpp $R/tests/twin/textstats_model.cpp $C/td_tables.cpp $C/td_regex.cpp -o /tmp/td_textstats_asan
+/tmp/td_utf8_asan
+/tmp/td_textstats_asan
 # The code the DEVICE shares with the host (td_common.h: scanners, exact-key probes, merge rounds; td_regex.h: the matcher) runs
 # in the CPU twin; under the sanitizers (round 3: the twin tests, the generic-pattern tests and 30 000 fuzz documents, no report):
 #   g++ -std=c++17 -O1 -g -fPIC -shared -fsanitize=address,undefined tests/twin/td_twin.cpp $C/td_tables.cpp $C/td_regex.cpp \
