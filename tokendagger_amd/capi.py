@@ -804,7 +804,9 @@ def _minhash_args(ids, tok_offsets, spec: MinhashSpec):
 
 
 def _minhash_outputs(n_docs: int, spec: MinhashSpec):
-    np_, nb = max(int(spec.num_perm), 1), max(int(spec.bands), 0)
+    # a spec outside the limits is for the library to refuse, so size the arrays for no more than a good one could need (bands * rows
+    # <= num_perm): where memory is not overcommitted, numpy raises MemoryError for bands = 2^32 before the library has seen the spec
+    np_, nb = max(min(int(spec.num_perm), TD_MINHASH_MAX_PERM), 1), max(min(int(spec.bands), TD_MINHASH_MAX_PERM), 0)
     sig = np.zeros((max(n_docs, 1), np_), dtype=np.uint32)
     keys = np.zeros((max(n_docs, 1), nb), dtype=np.uint64) if nb > 0 else None
     return sig, keys, np.zeros(4, dtype=np.int64)
