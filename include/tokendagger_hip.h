@@ -116,7 +116,15 @@ int td_encode_device(td_tokenizer* t, const void* d_text, int64_t n_bytes, const
 int td_reserve(td_tokenizer* t, int64_t max_bytes, int64_t max_docs);
 
 /* Synchronises `hip_stream` and returns the device error raised by calls made since the last status
- * check (TD_OK if none); *err_pos (optional) receives the byte offset it refers to. */
+ * check (TD_OK if none); *err_pos (optional) receives the byte offset it refers to.
+ * Chains of *_device calls with no status read between them (one call's device outputs are the next call's inputs):
+ *   - the FIRST error wins: the handle keeps one error, the first a kernel raises since the last read, with its position; later
+ *     errors of the same chain are not recorded, and no call clears it.  The read returns it and clears it: the next read is TD_OK.
+ *     A call whose contract says "nothing is written" on its error writes nothing; the calls in front of it and behind it run as usual;
+ *   - a call on another stream than the handle's previous call waits, on the device, for that call: outputs of any earlier call of
+ *     the handle are complete when a later call of the handle reads them, whatever streams the two are on;
+ *   - workspace growth is safe with calls in flight: a buffer that has to grow is replaced, and the old one is kept until the next
+ *     td_device_status on the stream of the handle's last call (or the next host-buffer call), never freed under a running kernel. */
 int td_device_status(td_tokenizer* t, void* hip_stream, int64_t* err_pos);
 
 /*
