@@ -1104,7 +1104,7 @@ int td_encode_batch_utf8(td_tokenizer* t, const uint8_t* text, const int64_t* do
  *              is read once).  TD_TS_RUNS: columns 10, 11, 13 - 17 (they need to know how far back the word or the line began: two more
  *              passes).  Columns of a group that was not asked for are 0.  0, or a value with other bits, is TD_E_INVALID.
  * Bytes behind the last document are not read.  Results are bitwise reproducible (integer sums and maxima only).  Out of scope:
- * duplicate-line and duplicate-n-gram fractions, stop-word rules (td_token_counts serves them), built-in thresholds or presets, lengths in
+ * duplicate-n-gram fractions (duplicate lines and paragraphs: td_repetition* below), stop-word rules (td_token_counts serves them), built-in thresholds or presets, lengths in
  * characters for the two maxima. */
 #define TD_TS_COLS 21
 #define TD_TS_LOCAL 1
@@ -1124,6 +1124,50 @@ int td_text_stats(td_tokenizer* t, const uint8_t* text, const int64_t* doc_offse
  * out_tok_offsets[n_docs + 1]; totals may be NULL.  Synchronous. */
 int td_encode_batch_text_stats(td_tokenizer* t, const uint8_t* text, const int64_t* doc_offsets, int64_t n_docs, int mode, int groups,
                                int32_t* out_ids, int64_t ids_capacity, int64_t* out_tok_offsets, int64_t* stats, int64_t* totals);
+
+/* ---- per-document duplicate lines and paragraphs for quality filtering (td_repetition.hip) ------------------------------------------------
+ * The repetition rules of Gopher's filter set, and FineWeb's char_duplicates_ratio, threshold the share of a document's lines and
+ * paragraphs that repeat an earlier one, by count and by characters.  Text + doc_offsets[n_docs + 1] (int64: from 0, non-decreasing,
+ * ending at or below n_bytes) -> stats[n_docs][TD_RP_COLS] (int64, row-major) and totals[TD_RP_COLS].  No thresholds: the caller forms the
+ * fractions, builds a mask and hands it to td_select_docs.  Host and device compile the same statement of the rule (td_repetition_args.h).
+ *   LINE       a maximal non-empty run of bytes other than 0x0A inside one document.  CR is content; nothing is trimmed.  "a\n\nb\n" has 2
+ *              lines, "" and "\n\n" have none.
+ *   PARAGRAPH  a maximal byte range of a document that begins and ends with a non-LF byte and contains no two adjacent LFs: what remains
+ *              between runs of two or more LFs, single leading and trailing LFs stripped.  "a\nb\n\n\nc\n" has "a\nb" and "c"; "\na" has "a".
+ *   DUPLICATE  a unit (line, paragraph) is one when an earlier unit of the same kind in the SAME document has the same bytes: DUP = units
+ *              - distinct units, and so for the bytes and the characters; which occurrence is called the first does not matter.  Equality
+ *              is equality of bytes, never of hashes: the results do not depend on the hash function.
+ *   CHARACTER  a byte outside 0x80 .. 0xBF.  No table of the handle is used: every pattern kind gives the same.
+ *   COLUMNS    0 LINES  1 LINE_BYTES  2 LINE_CHARS  3 DUP_LINES  4 DUP_LINE_BYTES  5 DUP_LINE_CHARS
+ *              6 PARAS  7 PARA_BYTES  8 PARA_CHARS  9 DUP_PARAS  10 DUP_PARA_BYTES  11 DUP_PARA_CHARS
+ *   totals     the columns' sums over all documents.
+ *   groups     TD_RP_LINES: columns 0 - 5; TD_RP_PARAS: columns 6 - 11; or both.  Columns of a group that was not asked for are 0.  0, or
+ *              a value with other bits, is TD_E_INVALID.
+ * Against Gopher and datatrove: they strip every line and paragraph, drop the empty ones, split paragraphs at "\n{2,}" of the stripped
+ * text and weigh duplicates by the characters of words; here nothing is stripped ("a" and "a " differ), and bytes and characters of
+ * the units themselves are counted.  Gopher's four fractions are DUP_LINES / LINES, DUP_LINE_CHARS / LINE_CHARS, DUP_PARAS / PARAS and
+ * DUP_PARA_CHARS / PARA_CHARS.  Bytes behind the last document are not read.  Results are bitwise reproducible (integer sums only).
+ * Out of scope: word and id n-gram repetition, duplicates across documents, thresholds or presets, a fused encode entry. */
+#define TD_RP_COLS 12
+#define TD_RP_LINES 1
+#define TD_RP_PARAS 2
+/* The contract's executable statement, on the host (no handle, no device).  totals may be NULL.  Argument errors (offsets that do not
+ * start at 0 or decrease, groups) are TD_E_INVALID and write nothing. */
+int td_repetition_host(const uint8_t* text, const int64_t* doc_offsets, int64_t n_docs, int groups, int64_t* stats, int64_t* totals);
+/* DEVICE buffers, asynchronously on hip_stream (never the null stream): no synchronisation and no read-back.  d_doc_offsets, d_stats and
+ * d_totals are 8-byte aligned; d_text needs no alignment; d_totals may be NULL.  n_bytes is below 2^40 (a unit's start is 40 bits of its
+ * table word): more is TD_E_INVALID.
+ *   max_units  sizes the call's table of distinct units in the handle's workspace: the power of two at or above max(64, 2 max_units)
+ *              words of 8 bytes.  0: n_bytes / 16 + n_docs + 1024.  The call counts its units (of the groups asked for) on the device
+ *              before it inserts any: more than max_units raise TD_E_CAPACITY through td_device_status with err_pos = the units
+ *              needed, and then NOTHING is written.
+ * Offsets that do not start at 0, decrease, are negative or end above n_bytes raise TD_E_INVALID through td_device_status with err_pos =
+ * the lowest such document, and then NOTHING is written. */
+int td_repetition_device(td_tokenizer* t, const void* d_text, int64_t n_bytes, const void* d_doc_offsets, int64_t n_docs, int groups,
+                         int64_t max_units, void* d_stats, void* d_totals, void* hip_stream);
+/* Host buffers, synchronously; td_repetition_host's arguments behind the handle.  Starts with max_units = 0 and, told TD_E_CAPACITY,
+ * runs once more with the need reported. */
+int td_repetition(td_tokenizer* t, const uint8_t* text, const int64_t* doc_offsets, int64_t n_docs, int groups, int64_t* stats, int64_t* totals);
 
 /* Options. */
 #define TD_OPT_LONG_POOL_BYTES 1 /* scratch for pieces longer than 64 bytes (default max(64 MiB, 2 x input)) */

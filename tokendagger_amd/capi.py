@@ -84,6 +84,7 @@ EXPORTS = [
     "td_minhash_params", "td_minhash_host", "td_minhash_device", "td_minhash", "td_encode_batch_minhash",
     "td_nfc_info", "td_nfc_host", "td_nfc_check_device", "td_nfc_device", "td_nfc", "td_encode_batch_nfc",
     "td_text_stats_host", "td_text_stats_device", "td_text_stats", "td_encode_batch_text_stats",
+    "td_repetition_host", "td_repetition_device", "td_repetition",
 ]
 
 
@@ -267,6 +268,12 @@ def load_library():
     lib.td_text_stats.argtypes = [vp, vp, vp, i64, i32, vp, vp]
     lib.td_encode_batch_text_stats.restype = i32
     lib.td_encode_batch_text_stats.argtypes = [vp, vp, vp, i64, i32, i32, vp, i64, vp, vp, vp]
+    lib.td_repetition_host.restype = i32
+    lib.td_repetition_host.argtypes = [vp, vp, i64, i32, vp, vp]
+    lib.td_repetition_device.restype = i32
+    lib.td_repetition_device.argtypes = [vp, vp, i64, vp, i64, i32, i64, vp, vp, vp]
+    lib.td_repetition.restype = i32
+    lib.td_repetition.argtypes = [vp, vp, vp, i64, i32, vp, vp]
     lib.td_encode_batch_token_counts.restype = i32
     lib.td_encode_batch_token_counts.argtypes = [vp, vp, vp, i64, i32, vp, vp, vp, vp, ctypes.POINTER(i64)]
     lib.td_comm_unique_id.restype = i32
@@ -940,6 +947,34 @@ def text_stats_host(text, doc_offsets, groups: int = TD_TS_ALL):
                                 totals.ctypes.data)
     if rc != TD_OK:
         raise TokenDaggerHipError(rc, "td_text_stats_host: invalid offsets, groups or arguments")
+    return stats[:n_docs], totals
+
+
+TD_RP_COLS, TD_RP_LINES, TD_RP_PARAS = 12, 1, 2
+TD_RP_ALL = TD_RP_LINES | TD_RP_PARAS
+# stats[:, c] by name (include/tokendagger_hip.h, td_repetition*, COLUMNS)
+RP_COLUMNS = ("lines", "line_bytes", "line_chars", "dup_lines", "dup_line_bytes", "dup_line_chars",
+              "paras", "para_bytes", "para_chars", "dup_paras", "dup_para_bytes", "dup_para_chars")
+
+
+def _repetition_args(text, doc_offsets):
+    """-> (text uint8, offsets int64, n_docs, stats int64[max(n_docs, 1), 12], totals int64[12])"""
+    buf = _as_u8(text)
+    o = np.ascontiguousarray(doc_offsets, dtype=np.int64)
+    n_docs = len(o) - 1
+    return buf, o, n_docs, np.zeros((max(n_docs, 1), TD_RP_COLS), dtype=np.int64), np.zeros(TD_RP_COLS, dtype=np.int64)
+
+
+def repetition_host(text, doc_offsets, groups: int = TD_RP_ALL):
+    """td_repetition_host (host only, no device) -> (stats int64[n_docs, 12], totals int64[12])."""
+    lib = load_library()
+    buf, o, n_docs, stats, totals = _repetition_args(text, doc_offsets)
+    if n_docs >= 0 and len(o) and int(o[-1]) > len(buf):
+        raise TokenDaggerHipError(TD_E_INVALID, "td_repetition_host: doc_offsets end behind the text")
+    rc = lib.td_repetition_host(buf.ctypes.data if len(buf) else None, o.ctypes.data if len(o) else None, n_docs, groups, stats.ctypes.data,
+                                totals.ctypes.data)
+    if rc != TD_OK:
+        raise TokenDaggerHipError(rc, "td_repetition_host: invalid offsets, groups or arguments")
     return stats[:n_docs], totals
 
 
@@ -2044,6 +2079,21 @@ class HipTokenizer:
         self._check(self._lib.td_encode_batch_text_stats(self._h, buf.ctypes.data if len(buf) else None, o.ctypes.data, n_docs, mode, groups,
                                                          ids.ctypes.data, len(ids), toff.ctypes.data, stats.ctypes.data, totals.ctypes.data))
         return ids[:int(toff[-1])], toff, stats[:n_docs], totals
+
+    # ---- per-document duplicate lines and paragraphs --------------------------------------------------------------
+    def repetition_device(self, d_text: int, n_bytes: int, d_doc_offsets: int, n_docs: int, groups: int, max_units: int, d_stats: int,
+                          d_totals: int, stream: int):
+        """td_repetition_device: raw device pointers (d_totals may be 0), asynchronous on `stream`, which must not be the null stream;
+        d_stats int64[n_docs, 12], d_totals int64[12]; max_units 0: the default; check with device_status(stream)."""
+        self._check(self._lib.td_repetition_device(self._h, d_text or None, n_bytes, d_doc_offsets or None, n_docs, groups, max_units,
+                                                   d_stats or None, d_totals or None, stream or None))
+
+    def repetition(self, text, doc_offsets, groups: int = TD_RP_ALL):
+        """td_repetition: repetition_host's arguments and results, computed on the device."""
+        buf, o, n_docs, stats, totals = _repetition_args(text, doc_offsets)
+        self._check(self._lib.td_repetition(self._h, buf.ctypes.data if len(buf) else None, o.ctypes.data, n_docs, groups, stats.ctypes.data,
+                                            totals.ctypes.data))
+        return stats[:n_docs], totals
 
     # ---- decode rows (td_decode_spec) ---------------------------------------------------------------------------
     def decode_rows(self, ids, spec: DecodeSpec, tok_offsets=None, lengths=None, n_segs: int | None = None, capacity: int | None = None):

@@ -290,6 +290,10 @@ struct td_tokenizer {
     // points' stats and totals on the device
     RewriteBufs textstats;
     DevBuf ts_carry, ts_stats, ts_totals;
+    // duplicate lines and paragraphs (td_repetition.hip): the bad-offsets, capacity, unit-count and slot-mask words (its RewriteBufs' head
+    // alone), two scan elements a tile, the call's table of units; the host entry point's stats and totals on the device
+    RewriteBufs repetition;
+    DevBuf rp_carry, rp_table, rp_stats, rp_totals;
     int64_t mh_table_perm = 0;     // 0: no table yet
     uint64_t mh_table_seed = 0;
     std::vector<int64_t> dcr_key;  // flags, then the distinct listed ids with their bits (sorted); empty: no table yet

@@ -69,6 +69,59 @@ __device__ __forceinline__ void rewrite_group_copy(uint8_t* dst, const uint8_t* 
     if (tail + tid < len) dst[tail + tid] = src[tail + tid];
 }
 
+// ---- a read-only pass over the windows (td_textstats.hip, td_repetition.hip): a window's load, a tile's place and its documents ----------------
+// the window at b0 into w: one 16-byte load where it lies in the text, byte by byte at the text's ends
+__device__ __forceinline__ void rw_load(const uint8_t* text, int64_t b0, int64_t b, int64_t we, uint32_t w[4]) {
+    if (b == b0 && we == b0 + 16) {
+        const uint4 v = *reinterpret_cast<const uint4*>(text + b0);
+        w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w;
+        return;
+    }
+    w[0] = w[1] = w[2] = w[3] = 0;
+#pragma unroll
+    for (int k = 0; k < 16; ++k)
+        if (b0 + k >= b && b0 + k < we) w[k >> 2] |= (uint32_t)text[b0 + k] << (8 * (k & 3));
+}
+
+struct RwTile {  // a tile's place in the text
+    int64_t base, t0, s1;  // 16-byte aligned start (may lie in front of the text), first and end byte
+};
+__device__ __forceinline__ RwTile rw_tile(int64_t t, int shift, int64_t total) {
+    RwTile r;
+    r.base = t * RW_TILE - shift;
+    r.t0 = r.base < 0 ? 0 : r.base;
+    r.s1 = r.base + RW_TILE < total ? r.base + RW_TILE : total;
+    return r;
+}
+
+// The tile's table of documents, as the rewrites' tile loop builds it: kb the last document that starts in front of t0 (t0 == 0: the
+// first), s_off[i] = doc_off[kb + i] - t0 clamped; lds: the table fits.  By the whole workgroup, between two barriers of the caller.
+struct RwTable {
+    int64_t kb, nk;
+    bool lds;
+};
+template <class Off>
+__device__ __forceinline__ RwTable rw_table(int32_t* s_off, Off off_of, int64_t n_docs, const RwTile& tl) {
+    RwTable r;
+    r.lds = true;
+    r.kb = tl.t0 > 0 ? group_last_le(off_of, 0, n_docs, tl.t0 - 1) : 0;
+    r.nk = tile_table(s_off, off_of, r.kb, n_docs, tl.t0, RW_OFF_LO, RW_OFF_HI, (int32_t)(tl.s1 - tl.t0), r.lds);
+    if (!r.lds) r.nk = group_last_le(off_of, r.kb, n_docs, tl.s1 - 1) - r.kb + 1;
+    return r;
+}
+// the document that holds byte x of the tile (t0 <= x < s1): the last one of the table that starts at or below x
+__device__ __forceinline__ int64_t rw_doc_of(const int64_t* doc_off, const int32_t* s_off, const RwTable& tb, int64_t t0, int64_t x) {
+    int64_t lo = 0, hi = tb.nk;  // the first entry of [0, nk] behind x lies in [lo, hi]
+    const int64_t r = x - t0;
+    while (lo < hi) {
+        const int64_t mid = (lo + hi) >> 1;
+        const int64_t rel = tb.lds ? (int64_t)s_off[mid] : doc_off[tb.kb + mid] - t0;
+        if (rel > r) hi = mid;
+        else lo = mid + 1;
+    }
+    return tb.kb + lo - 1;
+}
+
 __device__ __forceinline__ void rewrite_scan(const RewriteArgs& a) {
     __shared__ long long s_wave[RW_THREADS / 64];
     if (a.head[RW_H_BAD]) return;

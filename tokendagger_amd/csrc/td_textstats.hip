@@ -33,30 +33,6 @@ __device__ __forceinline__ void ts_global(unsigned long long* p, int c, unsigned
     else __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-// the window at b0 into w: one 16-byte load where it lies in the text, byte by byte at the text's ends
-__device__ __forceinline__ void ts_load(const uint8_t* text, int64_t b0, int64_t b, int64_t we, uint32_t w[4]) {
-    if (b == b0 && we == b0 + 16) {
-        const uint4 v = *reinterpret_cast<const uint4*>(text + b0);
-        w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w;
-        return;
-    }
-    w[0] = w[1] = w[2] = w[3] = 0;
-#pragma unroll
-    for (int k = 0; k < 16; ++k)
-        if (b0 + k >= b && b0 + k < we) w[k >> 2] |= (uint32_t)text[b0 + k] << (8 * (k & 3));
-}
-
-struct TsTile {  // a tile's place in the text
-    int64_t base, t0, s1;  // 16-byte aligned start (may lie in front of the text), first and end byte
-};
-__device__ __forceinline__ TsTile ts_tile(int64_t t, int shift, int64_t total) {
-    TsTile r;
-    r.base = t * RW_TILE - shift;
-    r.t0 = r.base < 0 ? 0 : r.base;
-    r.s1 = r.base + RW_TILE < total ? r.base + RW_TILE : total;
-    return r;
-}
-
 __global__ __launch_bounds__(RW_THREADS) void td_ts_docs(const TsArgs a) {
     rewrite_docs(a, blockIdx.x * (int64_t)blockDim.x + threadIdx.x, (int64_t)gridDim.x * blockDim.x);
 }
@@ -69,34 +45,6 @@ __global__ __launch_bounds__(RW_THREADS) void td_ts_reset(const TsArgs a) {
         const int64_t d = i / TS_COLS;
         a.stats[i] = (a.groups & TS_LOCAL) && i - d * TS_COLS == TS_BYTES ? (unsigned long long)(a.doc_off[d + 1] - a.doc_off[d]) : 0ull;
     }
-}
-
-// The tile's table of documents, as the rewrites' tile loop builds it: kb the last document that starts in front of t0 (t0 == 0: the
-// first), s_off[i] = doc_off[kb + i] - t0 clamped; lds: the table fits.  By the whole workgroup, between two barriers of the caller.
-struct TsTable {
-    int64_t kb, nk;
-    bool lds;
-};
-template <class Off>
-__device__ __forceinline__ TsTable ts_table(int32_t* s_off, Off off_of, int64_t n_docs, const TsTile& tl) {
-    TsTable r;
-    r.lds = true;
-    r.kb = tl.t0 > 0 ? group_last_le(off_of, 0, n_docs, tl.t0 - 1) : 0;
-    r.nk = tile_table(s_off, off_of, r.kb, n_docs, tl.t0, RW_OFF_LO, RW_OFF_HI, (int32_t)(tl.s1 - tl.t0), r.lds);
-    if (!r.lds) r.nk = group_last_le(off_of, r.kb, n_docs, tl.s1 - 1) - r.kb + 1;
-    return r;
-}
-// the document that holds byte x of the tile (t0 <= x < s1): the last one of the table that starts at or below x
-__device__ __forceinline__ int64_t ts_doc_of(const TsArgs& a, const int32_t* s_off, const TsTable& tb, int64_t t0, int64_t x) {
-    int64_t lo = 0, hi = tb.nk;  // the first entry of [0, nk] behind x lies in [lo, hi]
-    const int64_t r = x - t0;
-    while (lo < hi) {
-        const int64_t mid = (lo + hi) >> 1;
-        const int64_t rel = tb.lds ? (int64_t)s_off[mid] : a.doc_off[tb.kb + mid] - t0;
-        if (rel > r) hi = mid;
-        else lo = mid + 1;
-    }
-    return tb.kb + lo - 1;
 }
 
 // ---- TS_RUNS: the tiles' last positions, and their prefix maxima ------------------------------------------------------------------------
@@ -113,23 +61,23 @@ __global__ __launch_bounds__(RW_THREADS) void td_ts_carry(const TsArgs a) {
     const int64_t ntiles = total > 0 ? (total + shift + RW_TILE - 1) / RW_TILE : 0;
     const auto off_of = [off = a.doc_off](int64_t d) { return off[d]; };
     for (int64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
-        const TsTile tl = ts_tile(t, shift, total);
+        const RwTile tl = rw_tile(t, shift, total);
         const int64_t b0 = tl.base + 16 * tid, b = b0 < 0 ? 0 : b0, we = b0 + 16 < total ? b0 + 16 : total;
         const bool owns = b < we;
         uint32_t w[4] = {0, 0, 0, 0}, c[4];
-        if (owns) ts_load(a.text, b0, b, we, w);
+        if (owns) rw_load(a.text, b0, b, we, w);
         const bool need = owns && !ts_window_ascii(w);
-        TsTable tb = {0, 0, true};
+        RwTable tb = {0, 0, true};
         __syncthreads();  // (the tile before has read its table; s_ascii is written)
         if (__syncthreads_or(need)) {
-            tb = ts_table(s_off, off_of, a.n_docs, tl);
+            tb = rw_table(s_off, off_of, a.n_docs, tl);
             __syncthreads();
         }
         TsLane S = {-1, -1, -1, -1, false};
         if (owns) {
             TsCursor cur = {0, 0, 0};
             if (need) {
-                cur.D = ts_doc_of(a, s_off, tb, tl.t0, b);
+                cur.D = rw_doc_of(a.doc_off, s_off, tb, tl.t0, b);
                 cur.ds = a.doc_off[cur.D];
                 cur.de = a.doc_off[cur.D + 1];
             }
@@ -239,18 +187,18 @@ __global__ __launch_bounds__(RW_THREADS) void td_ts_tiles(const TsArgs a) {
     const int64_t ntiles = total > 0 ? (total + shift + RW_TILE - 1) / RW_TILE : 0;
     const auto off_of = [off = a.doc_off](int64_t d) { return off[d]; };
     for (int64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
-        const TsTile tl = ts_tile(t, shift, total);
+        const RwTile tl = rw_tile(t, shift, total);
         const int64_t b0 = tl.base + 16 * tid, b = b0 < 0 ? 0 : b0, we = b0 + 16 < total ? b0 + 16 : total;
         const bool owns = b < we;
         uint32_t w[4] = {0, 0, 0, 0}, c[4] = {0, 0, 0, 0};
-        if (owns) ts_load(a.text, b0, b, we, w);
+        if (owns) rw_load(a.text, b0, b, we, w);
         __syncthreads();  // (the tile before has read its table and emptied s_acc; s_ascii and s_acc are written)
-        const TsTable tb = ts_table(s_off, off_of, a.n_docs, tl);
+        const RwTable tb = rw_table(s_off, off_of, a.n_docs, tl);
         __syncthreads();
         TsCursor cur = {-1, 0, 0};
         TsLane S = {-1, -1, -1, -1, false};
         if (owns) {
-            cur.D = ts_doc_of(a, s_off, tb, tl.t0, b);
+            cur.D = rw_doc_of(a.doc_off, s_off, tb, tl.t0, b);
             cur.ds = a.doc_off[cur.D];
             cur.de = a.doc_off[cur.D + 1];
             ts_window_classes(T, s_ascii, a.text, a.doc_off, b0, b, we, w, cur, c, S);

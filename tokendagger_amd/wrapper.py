@@ -193,6 +193,44 @@ class TextStats:
         return self._ratio(self.upper, self.upper + self.lower + self.letter_other)
 
 
+class RepetitionStats:
+    """Tokenizer.repetition_stats (the contract: include/tokendagger_hip.h, td_repetition*): a document's lines and paragraphs and the
+    ones that repeat an earlier one of the same document, by count, bytes and characters.  No thresholds here: build a mask from the
+    fractions and hand the kept documents to select_docs."""
+
+    def __init__(self, stats: np.ndarray, totals: np.ndarray):
+        self.stats = stats    # int64 [n_docs, 12]
+        self.totals = totals  # int64 [12]: the columns' sums
+
+    def __getattr__(self, name):  # the named column views: .lines, .dup_line_chars, ... (capi.RP_COLUMNS)
+        if name in _capi.RP_COLUMNS:
+            return self.stats[:, _capi.RP_COLUMNS.index(name)]
+        raise AttributeError(name)
+
+    def _ratio(self, num, den) -> np.ndarray:
+        """num / den per document as float64, 0.0 where den is 0"""
+        num, den = np.asarray(num, dtype=np.float64), np.asarray(den, dtype=np.float64)
+        return np.divide(num, den, out=np.zeros_like(num), where=den != 0)
+
+    @property
+    def dup_line_fraction(self) -> np.ndarray:
+        return self._ratio(self.dup_lines, self.lines)
+
+    @property
+    def dup_line_char_fraction(self) -> np.ndarray:
+        return self._ratio(self.dup_line_chars, self.line_chars)
+
+    @property
+    def dup_para_fraction(self) -> np.ndarray:
+        return self._ratio(self.dup_paras, self.paras)
+
+    @property
+    def dup_para_char_fraction(self) -> np.ndarray:
+        return self._ratio(self.dup_para_chars, self.para_chars)
+
+
+_RP_GROUPS = {"all": _capi.TD_RP_ALL, "lines": _capi.TD_RP_LINES, "paras": _capi.TD_RP_PARAS}
+
 _TS_GROUPS = {"all": _capi.TD_TS_ALL, "local": _capi.TD_TS_LOCAL, "runs": _capi.TD_TS_RUNS}
 
 
@@ -528,6 +566,17 @@ class Tokenizer:
             return TextStats(*hip.text_stats(buf, np.asarray(offsets, dtype=np.int64), g))
         except _capi.TokenDaggerHipError as ex:
             raise TokenDaggerError(f"Text statistics failed: {ex}")
+
+    def repetition_stats(self, text: np.ndarray | bytes, offsets: np.ndarray, groups: str = "all") -> RepetitionStats:
+        """Concatenated bytes + int64 document offsets -> RepetitionStats (duplicate lines and paragraphs per document), on the GPU."""
+        if groups not in _RP_GROUPS:
+            raise ValueError(f"groups must be 'all', 'lines' or 'paras', not {groups!r}")
+        hip = _capi.HipTokenizer.borrow(self._core_bpe.handle())
+        buf = np.frombuffer(text, dtype=np.uint8) if isinstance(text, (bytes, bytearray)) else text
+        try:
+            return RepetitionStats(*hip.repetition(buf, np.asarray(offsets, dtype=np.int64), _RP_GROUPS[groups]))
+        except _capi.TokenDaggerHipError as ex:
+            raise TokenDaggerError(f"Repetition statistics failed: {ex}")
 
     def encode_batch_to_numpy_with_stats(self, text: np.ndarray | bytes, offsets: np.ndarray, *, ordinary: bool = False):
         """encode_batch_to_numpy and text_stats of one upload -> (int32 ids, int64 token offsets, TextStats)."""

@@ -1,0 +1,69 @@
+// AddressSanitizer + UBSan over the duplicate-line and duplicate-paragraph host statement (rp_host of td_repetition_args.h, which
+// td_repetition_host is): it looks one byte in front of a position and two behind it, inside the document only, and compares units'
+// bytes: this is where a read past a document's or the text's end would show.  Random texts of an alphabet that makes short units and
+// duplicates dense, each in a heap buffer of exactly its size, with offsets in a heap buffer of exactly theirs, cut into documents at
+// random positions; the columns must add up (duplicates below units, both groups the two single ones side by side).  CPU only:
+//   g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-omit-frame-pointer -D__HIP_PLATFORM_AMD__ -I${ROCM_PATH:-/opt/rocm}/include \
+//       -Itokendagger_amd/csrc -Iinclude tools/sanitize/repetition_asan.cpp -o /tmp/td_repetition_asan && /tmp/td_repetition_asan
+#include <stdint.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include <vector>
+
+#include "td_repetition_args.h"
+
+namespace {
+
+const char* kAlphabet[] = {"a", "b", "\n", "\n", "\xC3\xA9", "\r", "ab"};
+constexpr int kSyms = sizeof kAlphabet / sizeof kAlphabet[0], kCols = td::RP_COLS;
+
+uint64_t g_state = 88172645463325252ull;
+uint32_t rnd(uint32_t n) {
+    g_state ^= g_state << 13; g_state ^= g_state >> 7; g_state ^= g_state << 17;
+    return (uint32_t)((g_state >> 11) % n);
+}
+
+}  // namespace
+
+int main(int argc, char** argv) {
+    const int rounds = argc > 1 ? atoi(argv[1]) : 4000;
+    long long calls = 0;
+    for (int r = 0; r < rounds; ++r) {
+        std::vector<uint8_t> s;
+        const int syms = (int)rnd(r % 50 == 0 ? 700 : 70);
+        for (int i = 0; i < syms; ++i) {
+            const char* a = kAlphabet[rnd(kSyms)];
+            s.insert(s.end(), a, a + strlen(a));
+        }
+        const int64_t n = (int64_t)s.size(), n_docs = 1 + rnd(7);
+        uint8_t* text = n ? (uint8_t*)malloc((size_t)n) : nullptr;
+        if (n) memcpy(text, s.data(), (size_t)n);
+        int64_t* off = (int64_t*)malloc(sizeof(int64_t) * (size_t)(n_docs + 1));
+        off[0] = 0;
+        off[n_docs] = n;
+        for (int64_t d = 1; d < n_docs; ++d) off[d] = rnd((uint32_t)n + 1);
+        for (int64_t d = 1; d < n_docs; ++d)  // (sorted: an insertion sort over at most six entries)
+            for (int64_t e = d; e > 1 && off[e - 1] > off[e]; --e) { const int64_t x = off[e]; off[e] = off[e - 1]; off[e - 1] = x; }
+        int64_t* rows[4];
+        int64_t tot[4][kCols];
+        for (int groups = 1; groups <= 3; ++groups) {
+            rows[groups] = (int64_t*)malloc(sizeof(int64_t) * (size_t)(n_docs * kCols));
+            if (td::rp_host(text, off, n_docs, groups, rows[groups], tot[groups]) != 0) abort();
+            ++calls;
+        }
+        for (int64_t i = 0; i < n_docs * kCols; ++i) {
+            const int64_t c = i % kCols, both = rows[3][i];
+            if (both != rows[1][i] + rows[2][i] || both < 0 || (c % 6 >= 3 && both > rows[3][i - 3]) || (c % 6 == 1 && both > off[i / kCols + 1] - off[i / kCols])) {
+                fprintf(stderr, "the columns do not add up: round %d entry %lld\n", r, (long long)i);
+                return 1;
+            }
+        }
+        for (int groups = 1; groups <= 3; ++groups) free(rows[groups]);
+        free(off);
+        free(text);
+    }
+    printf("repetition_asan: %lld calls, no report\n", calls);
+    return 0;
+}
