@@ -1147,7 +1147,8 @@ int td_encode_batch_text_stats(td_tokenizer* t, const uint8_t* text, const int64
  * text and weigh duplicates by the characters of words; here nothing is stripped ("a" and "a " differ), and bytes and characters of
  * the units themselves are counted.  Gopher's four fractions are DUP_LINES / LINES, DUP_LINE_CHARS / LINE_CHARS, DUP_PARAS / PARAS and
  * DUP_PARA_CHARS / PARA_CHARS.  Bytes behind the last document are not read.  Results are bitwise reproducible (integer sums only).
- * Out of scope: word and id n-gram repetition, duplicates across documents, thresholds or presets, a fused encode entry. */
+ * Out of scope: word n-gram repetition (td_word_ngrams* below), id n-gram repetition, duplicates across documents, thresholds or
+ * presets, a fused encode entry. */
 #define TD_RP_COLS 12
 #define TD_RP_LINES 1
 #define TD_RP_PARAS 2
@@ -1168,6 +1169,63 @@ int td_repetition_device(td_tokenizer* t, const void* d_text, int64_t n_bytes, c
 /* Host buffers, synchronously; td_repetition_host's arguments behind the handle.  Starts with max_units = 0 and, told TD_E_CAPACITY,
  * runs once more with the need reported. */
 int td_repetition(td_tokenizer* t, const uint8_t* text, const int64_t* doc_offsets, int64_t n_docs, int groups, int64_t* stats, int64_t* totals);
+
+/* ---- per-document word n-gram repetition for quality filtering (td_wordgrams.hip) ----------------------------------------------------------
+ * The other half of Gopher's repetition rules: the share of a document that its most frequent 2-, 3- and 4-gram of words takes, and the
+ * share that lies inside 5- to 10-grams that occur twice.  Text + doc_offsets[n_docs + 1] (int64: from 0, non-decreasing, ending at or
+ * below n_bytes, n_bytes below 2^40) -> stats[n_docs][TD_WG_COLS] (int64, row-major) and totals[TD_WG_COLS].  No thresholds: the caller
+ * forms the fractions, builds a mask and hands it to td_select_docs.  Host and device compile the same statement of the rule
+ * (td_wordgrams_args.h).  No table of the handle is used: every pattern kind gives the same.
+ *   SPACE      a byte 0x09 - 0x0D or 0x20: what Python's bytes.split() splits on.
+ *   WORD       a maximal run of non-space bytes inside one document.  Nothing else splits a word: punctuation stays with its word, and
+ *              U+00A0 and U+3000 are word content.
+ *   CHARACTER  a byte outside 0x80 .. 0xBF, as in td_repetition*.
+ *   N-GRAM     n consecutive words of one document.  Two n-grams are equal when their words are pairwise equal as bytes; the separators
+ *              between the words do not count: "x y", "x  y" and "x\ny" hold the same 2-gram.  An n-gram's CHARS are the characters of
+ *              its words, separators not counted.  Occurrences may overlap: "a a a" holds the 2-gram "a a" twice.  Equality is equality
+ *              of bytes, never of hashes: the results do not depend on the hash function.
+ *   TOP_n      n = 2, 3, 4.  TOPn_COUNT: the largest number of occurrences any n-gram of the document has; TOPn_CHARS: the CHARS of that
+ *              n-gram, and among n-grams that reach the same count the most CHARS: the lexicographic maximum of (count, chars) over the
+ *              distinct n-grams, which does not depend on the order of evaluation.  Fewer than n words: 0 and 0.
+ *   DUP_n      n = 5 .. 10.  DUPn_CHARS: the characters of the words that lie inside at least one occurrence of an n-gram that occurs at
+ *              least twice in the document; a word is counted once however many such occurrences cover it.
+ *   COLUMNS    0 WORDS  1 WORD_CHARS  2 CHARS (all characters of the document, spaces included)
+ *              3 TOP2_COUNT  4 TOP2_CHARS  5 TOP3_COUNT  6 TOP3_CHARS  7 TOP4_COUNT  8 TOP4_CHARS
+ *              9 DUP5_CHARS  10 DUP6_CHARS  11 DUP7_CHARS  12 DUP8_CHARS  13 DUP9_CHARS  14 DUP10_CHARS
+ *   totals     the sums of columns 0 - 2 and 9 - 14, and the maximum over the documents of each of columns 3 - 8 on its own.
+ *   groups     TD_WG_TOP: columns 3 - 8; TD_WG_DUP: columns 9 - 14; or both.  Columns 0 - 2 are always written; columns of a group that
+ *              was not asked for are 0.  0, or a value with other bits, is TD_E_INVALID.
+ *   flags      TD_WG_NO_LDS sends every document through the global table (for tests and A/B runs; the results are the same).  Other
+ *              bits are TD_E_INVALID.
+ * Against Gopher and datatrove: their word splitters are language-aware and cut punctuation off; this one cuts at ASCII white space only.
+ * Gopher's top_n_gram fraction is TOPn_COUNT * (TOPn_CHARS + n - 1) / CHARS in datatrove's form (it joins the words with one space), or
+ * without the "+ n - 1" in the paper's wording.  datatrove takes the first-seen n-gram among equal counts; here it is the one with the
+ * most characters, so this fraction is the larger of the candidates.  datatrove's find_all_duplicate is a serial greedy walk that skips
+ * n words after a hit; DUPn_CHARS follows the paper's wording (characters inside duplicate n-grams, overlaps counted once) and is never
+ * smaller than the walk's value on the same words: every n-gram the walk counts occurs earlier in the document, so it occurs twice.
+ * The duplicate fraction is DUPn_CHARS / WORD_CHARS.  Bytes behind the last document are not read.  Results are bitwise reproducible
+ * (integer sums and maxima only).  Out of scope: other values of n, n-grams of ids, n-grams across documents, case folding, thresholds
+ * or presets, a fused encode entry. */
+#define TD_WG_COLS 15
+#define TD_WG_TOP 1
+#define TD_WG_DUP 2
+#define TD_WG_NO_LDS 1
+/* The contract's executable statement, on the host (no handle, no device, no hash: it sorts).  totals may be NULL.  Argument errors
+ * (offsets that do not start at 0 or decrease, groups) are TD_E_INVALID and write nothing. */
+int td_word_ngrams_host(const uint8_t* text, const int64_t* doc_offsets, int64_t n_docs, int groups, int64_t* stats, int64_t* totals);
+/* DEVICE buffers, asynchronously on hip_stream (never the null stream): no synchronisation and no read-back.  d_doc_offsets, d_stats and
+ * d_totals are 8-byte aligned; d_text needs no alignment; d_totals may be NULL.  n_bytes at or above 2^40 is TD_E_INVALID.
+ *   max_words  sizes the words' records and the global table in the handle's workspace (33 bytes a word, and 16 a slot of the power of
+ *              two at or above max(64, 2 max_words)).  0: n_bytes / 4 + n_docs + 1024; a word takes at least two bytes with its
+ *              separator, so n_bytes / 2 + n_docs always suffices.  The call counts its words on the device before it stores any: more
+ *              than max_words raise TD_E_CAPACITY through td_device_status with err_pos = the words needed, and then NOTHING is written.
+ * Offsets that do not start at 0, decrease, are negative or end above n_bytes raise TD_E_INVALID through td_device_status with err_pos =
+ * the lowest such document, and then NOTHING is written. */
+int td_word_ngrams_device(td_tokenizer* t, const void* d_text, int64_t n_bytes, const void* d_doc_offsets, int64_t n_docs, int groups,
+                          int flags, int64_t max_words, void* d_stats, void* d_totals, void* hip_stream);
+/* Host buffers, synchronously; td_word_ngrams_host's arguments behind the handle.  Starts with max_words = 0 and, told TD_E_CAPACITY,
+ * runs once more with the need reported. */
+int td_word_ngrams(td_tokenizer* t, const uint8_t* text, const int64_t* doc_offsets, int64_t n_docs, int groups, int64_t* stats, int64_t* totals);
 
 /* Options. */
 #define TD_OPT_LONG_POOL_BYTES 1 /* scratch for pieces longer than 64 bytes (default max(64 MiB, 2 x input)) */

@@ -85,6 +85,7 @@ EXPORTS = [
     "td_nfc_info", "td_nfc_host", "td_nfc_check_device", "td_nfc_device", "td_nfc", "td_encode_batch_nfc",
     "td_text_stats_host", "td_text_stats_device", "td_text_stats", "td_encode_batch_text_stats",
     "td_repetition_host", "td_repetition_device", "td_repetition",
+    "td_word_ngrams_host", "td_word_ngrams_device", "td_word_ngrams",
 ]
 
 
@@ -274,6 +275,12 @@ def load_library():
     lib.td_repetition_device.argtypes = [vp, vp, i64, vp, i64, i32, i64, vp, vp, vp]
     lib.td_repetition.restype = i32
     lib.td_repetition.argtypes = [vp, vp, vp, i64, i32, vp, vp]
+    lib.td_word_ngrams_host.restype = i32
+    lib.td_word_ngrams_host.argtypes = [vp, vp, i64, i32, vp, vp]
+    lib.td_word_ngrams_device.restype = i32
+    lib.td_word_ngrams_device.argtypes = [vp, vp, i64, vp, i64, i32, i32, i64, vp, vp, vp]
+    lib.td_word_ngrams.restype = i32
+    lib.td_word_ngrams.argtypes = [vp, vp, vp, i64, i32, vp, vp]
     lib.td_encode_batch_token_counts.restype = i32
     lib.td_encode_batch_token_counts.argtypes = [vp, vp, vp, i64, i32, vp, vp, vp, vp, ctypes.POINTER(i64)]
     lib.td_comm_unique_id.restype = i32
@@ -975,6 +982,34 @@ def repetition_host(text, doc_offsets, groups: int = TD_RP_ALL):
                                 totals.ctypes.data)
     if rc != TD_OK:
         raise TokenDaggerHipError(rc, "td_repetition_host: invalid offsets, groups or arguments")
+    return stats[:n_docs], totals
+
+
+TD_WG_COLS, TD_WG_TOP, TD_WG_DUP, TD_WG_NO_LDS = 15, 1, 2, 1
+TD_WG_ALL = TD_WG_TOP | TD_WG_DUP
+# stats[:, c] by name (include/tokendagger_hip.h, td_word_ngrams*, COLUMNS)
+WG_COLUMNS = ("words", "word_chars", "chars", "top2_count", "top2_chars", "top3_count", "top3_chars", "top4_count", "top4_chars",
+              "dup5_chars", "dup6_chars", "dup7_chars", "dup8_chars", "dup9_chars", "dup10_chars")
+
+
+def _word_ngrams_args(text, doc_offsets):
+    """-> (text uint8, offsets int64, n_docs, stats int64[max(n_docs, 1), 15], totals int64[15])"""
+    buf = _as_u8(text)
+    o = np.ascontiguousarray(doc_offsets, dtype=np.int64)
+    n_docs = len(o) - 1
+    return buf, o, n_docs, np.zeros((max(n_docs, 1), TD_WG_COLS), dtype=np.int64), np.zeros(TD_WG_COLS, dtype=np.int64)
+
+
+def word_ngrams_host(text, doc_offsets, groups: int = TD_WG_ALL):
+    """td_word_ngrams_host (host only, no device) -> (stats int64[n_docs, 15], totals int64[15])."""
+    lib = load_library()
+    buf, o, n_docs, stats, totals = _word_ngrams_args(text, doc_offsets)
+    if n_docs >= 0 and len(o) and int(o[-1]) > len(buf):
+        raise TokenDaggerHipError(TD_E_INVALID, "td_word_ngrams_host: doc_offsets end behind the text")
+    rc = lib.td_word_ngrams_host(buf.ctypes.data if len(buf) else None, o.ctypes.data if len(o) else None, n_docs, groups, stats.ctypes.data,
+                                 totals.ctypes.data)
+    if rc != TD_OK:
+        raise TokenDaggerHipError(rc, "td_word_ngrams_host: invalid offsets, groups or arguments")
     return stats[:n_docs], totals
 
 
@@ -2093,6 +2128,21 @@ class HipTokenizer:
         buf, o, n_docs, stats, totals = _repetition_args(text, doc_offsets)
         self._check(self._lib.td_repetition(self._h, buf.ctypes.data if len(buf) else None, o.ctypes.data, n_docs, groups, stats.ctypes.data,
                                             totals.ctypes.data))
+        return stats[:n_docs], totals
+
+    # ---- per-document word n-gram repetition -----------------------------------------------------------------------
+    def word_ngrams_device(self, d_text: int, n_bytes: int, d_doc_offsets: int, n_docs: int, groups: int, flags: int, max_words: int,
+                           d_stats: int, d_totals: int, stream: int):
+        """td_word_ngrams_device: raw device pointers (d_totals may be 0), asynchronous on `stream`, which must not be the null stream;
+        d_stats int64[n_docs, 15], d_totals int64[15]; flags 0 or TD_WG_NO_LDS; max_words 0: the default; check with device_status(stream)."""
+        self._check(self._lib.td_word_ngrams_device(self._h, d_text or None, n_bytes, d_doc_offsets or None, n_docs, groups, flags, max_words,
+                                                    d_stats or None, d_totals or None, stream or None))
+
+    def word_ngrams(self, text, doc_offsets, groups: int = TD_WG_ALL):
+        """td_word_ngrams: word_ngrams_host's arguments and results, computed on the device."""
+        buf, o, n_docs, stats, totals = _word_ngrams_args(text, doc_offsets)
+        self._check(self._lib.td_word_ngrams(self._h, buf.ctypes.data if len(buf) else None, o.ctypes.data, n_docs, groups, stats.ctypes.data,
+                                             totals.ctypes.data))
         return stats[:n_docs], totals
 
     # ---- decode rows (td_decode_spec) ---------------------------------------------------------------------------

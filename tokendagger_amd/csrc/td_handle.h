@@ -294,6 +294,12 @@ struct td_tokenizer {
     // alone), two scan elements a tile, the call's table of units; the host entry point's stats and totals on the device
     RewriteBufs repetition;
     DevBuf rp_carry, rp_table, rp_stats, rp_totals;
+    // word n-gram repetition (td_wordgrams.hip): its RewriteBufs' head alone, two scan elements a tile, the words' records, the word
+    // characters in front of each, the documents' first words, the global table's words and counts, an occurrence's slot or count and
+    // its flag, the documents of the global path with their words in front of each and their counts; the host entry point's stats and
+    // totals on the device
+    RewriteBufs wordgrams;
+    DevBuf wg_carry, wg_rec, wg_cum, wg_first, wg_table, wg_cnt, wg_occ, wg_flag, wg_long_doc, wg_long_first, wg_lhead, wg_stats, wg_totals;
     int64_t mh_table_perm = 0;     // 0: no table yet
     uint64_t mh_table_seed = 0;
     std::vector<int64_t> dcr_key;  // flags, then the distinct listed ids with their bits (sorted); empty: no table yet

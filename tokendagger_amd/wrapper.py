@@ -229,6 +229,42 @@ class RepetitionStats:
         return self._ratio(self.dup_para_chars, self.para_chars)
 
 
+class WordNgramStats:
+    """Tokenizer.word_ngram_stats (the contract: include/tokendagger_hip.h, td_word_ngrams*): a document's words, its most frequent 2-,
+    3- and 4-gram of words and the characters inside 5- to 10-grams that occur twice.  No thresholds here: build a mask from the
+    fractions and hand the kept documents to select_docs."""
+
+    def __init__(self, stats: np.ndarray, totals: np.ndarray):
+        self.stats = stats    # int64 [n_docs, 15]
+        self.totals = totals  # int64 [15]: the columns' sums; of the six TOP columns the maximum
+
+    def __getattr__(self, name):  # the named column views: .words, .top2_count, .dup10_chars, ... (capi.WG_COLUMNS)
+        if name in _capi.WG_COLUMNS:
+            return self.stats[:, _capi.WG_COLUMNS.index(name)]
+        raise AttributeError(name)
+
+    def _ratio(self, num, den) -> np.ndarray:
+        """num / den per document as float64, 0.0 where den is 0"""
+        num, den = np.asarray(num, dtype=np.float64), np.asarray(den, dtype=np.float64)
+        return np.divide(num, den, out=np.zeros_like(num), where=den != 0)
+
+    def top_fraction(self, n: int, joined: bool = True) -> np.ndarray:
+        """Gopher's top n-gram fraction, n = 2, 3, 4: count * characters of the most frequent n-gram over the document's characters;
+        joined: with the n - 1 single spaces datatrove joins the words by."""
+        if n not in (2, 3, 4):
+            raise ValueError(f"n must be 2, 3 or 4, not {n!r}")
+        count, chars = getattr(self, f"top{n}_count"), getattr(self, f"top{n}_chars")
+        return self._ratio(count * (chars + (n - 1 if joined else 0)), self.chars)
+
+    def dup_fraction(self, n: int) -> np.ndarray:
+        """Gopher's duplicate n-gram fraction, n = 5 .. 10: the characters inside duplicate n-grams over the words' characters"""
+        if n not in range(5, 11):
+            raise ValueError(f"n must be 5 .. 10, not {n!r}")
+        return self._ratio(getattr(self, f"dup{n}_chars"), self.word_chars)
+
+
+_WG_GROUPS = {"all": _capi.TD_WG_ALL, "top": _capi.TD_WG_TOP, "dup": _capi.TD_WG_DUP}
+
 _RP_GROUPS = {"all": _capi.TD_RP_ALL, "lines": _capi.TD_RP_LINES, "paras": _capi.TD_RP_PARAS}
 
 _TS_GROUPS = {"all": _capi.TD_TS_ALL, "local": _capi.TD_TS_LOCAL, "runs": _capi.TD_TS_RUNS}
@@ -577,6 +613,17 @@ class Tokenizer:
             return RepetitionStats(*hip.repetition(buf, np.asarray(offsets, dtype=np.int64), _RP_GROUPS[groups]))
         except _capi.TokenDaggerHipError as ex:
             raise TokenDaggerError(f"Repetition statistics failed: {ex}")
+
+    def word_ngram_stats(self, text: np.ndarray | bytes, offsets: np.ndarray, groups: str = "all") -> WordNgramStats:
+        """Concatenated bytes + int64 document offsets -> WordNgramStats (word n-gram repetition per document), on the GPU."""
+        if groups not in _WG_GROUPS:
+            raise ValueError(f"groups must be 'all', 'top' or 'dup', not {groups!r}")
+        hip = _capi.HipTokenizer.borrow(self._core_bpe.handle())
+        buf = np.frombuffer(text, dtype=np.uint8) if isinstance(text, (bytes, bytearray)) else text
+        try:
+            return WordNgramStats(*hip.word_ngrams(buf, np.asarray(offsets, dtype=np.int64), _WG_GROUPS[groups]))
+        except _capi.TokenDaggerHipError as ex:
+            raise TokenDaggerError(f"Word n-gram statistics failed: {ex}")
 
     def encode_batch_to_numpy_with_stats(self, text: np.ndarray | bytes, offsets: np.ndarray, *, ordinary: bool = False):
         """encode_batch_to_numpy and text_stats of one upload -> (int32 ids, int64 token offsets, TextStats)."""

@@ -21,7 +21,13 @@ g++ $F $H $S/textstats_asan.cpp $R/tests/twin/textstats_model.cpp $C/td_tables.c
 /tmp/td_textstats_asan
 # The duplicate-line and duplicate-paragraph statement (rp_host of td_repetition_args.h, which td_repetition_host is), the same way.
 g++ $F $H $S/repetition_asan.cpp -o /tmp/td_repetition_asan
+# The word n-gram repetition statement (wg_host of td_wordgrams_args.h, which td_word_ngrams_host is), the same way.
+g++ $F $H $S/wordgrams_asan.cpp -o /tmp/td_wordgrams_asan
+/tmp/td_wordgrams_asan
 /tmp/td_repetition_asan
+# The word n-gram repetition statement (wg_host of td_wordgrams_args.h, which td_word_ngrams_host is), the same way.
+g++ $F $H $S/wordgrams_asan.cpp -o /tmp/td_wordgrams_asan
+/tmp/td_wordgrams_asan
 # The code the DEVICE shares with the host (td_common.h: scanners, exact-key probes, merge rounds; td_regex.h: the matcher) runs
 # in the CPU twin; under the sanitizers (round 3: the twin tests, the generic-pattern tests and 30 000 fuzz documents, no report):
 #   g++ -std=c++17 -O1 -g -fPIC -shared -fsanitize=address,undefined tests/twin/td_twin.cpp $C/td_tables.cpp $C/td_regex.cpp \
