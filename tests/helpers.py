@@ -394,3 +394,14 @@ def random_unicode_string(rng: random.Random, max_len: int = 24) -> str:
             cp = 0x4E2D
         out.append(chr(cp))
     return "".join(out)
+
+
+def every_case(cases, one):
+    """one(name, *case) for EVERY case: a case that fails does not hide the ones behind it; all failures are reported together."""
+    failed = {}
+    for name, case in cases.items():
+        try:
+            one(name, *case)
+        except AssertionError as e:
+            failed[name] = str(e)[:300]
+    assert not failed, (f"{len(failed)} of {len(cases)} cases differ", list(failed), failed)
