@@ -1227,6 +1227,67 @@ int td_word_ngrams_device(td_tokenizer* t, const void* d_text, int64_t n_bytes, 
  * runs once more with the need reported. */
 int td_word_ngrams(td_tokenizer* t, const uint8_t* text, const int64_t* doc_offsets, int64_t n_docs, int groups, int64_t* stats, int64_t* totals);
 
+/* ---- line filtering: drop lines by rule and rewrite the text (td_linefilter.hip) ------------------------------------------------------------
+ * The line-level half of C4's and FineWeb's filters: text + doc_offsets[n_docs + 1] (int64: from 0, non-decreasing, ending at or below
+ * n_bytes) -> the text with the failing lines removed, out_doc_offsets[n_docs + 1], stats[n_docs][TD_LF_COLS] (int64, row-major) and
+ * totals[TD_LF_COLS].  Only lines are decided: the caller drops DOCUMENTS through td_select_docs, from stats.  No presets.  Host and
+ * device compile the same statement of the rule (td_linefilter_args.h).  No table of the handle is used: every pattern kind gives the same.
+ *   SPACE      a byte 0x09 - 0x0D or 0x20, as in td_word_ngrams*.  A WORD is a maximal run of non-space bytes inside a line.
+ *   LINES      the pieces of a document between its 0x0A bytes; a final empty piece is no line, as in td_text_stats*: "a\n\nb\n" has 3
+ *              lines, "" has 0.  A line OWNS the LF that ends it; a document's last line may have none.  A line never crosses a document
+ *              start.
+ *   PER LINE   WORDS; WORD_MAX, in bytes; TERMINAL: the line's last non-space byte closes one of . ! ? " U+201D U+3002 U+FF01 U+FF1F with
+ *              all of that character's bytes inside the line (decided from that byte and the two in front of it).  A phrase p OCCURS at
+ *              byte i when text[i, i + len_p), ASCII upper case mapped to lower case, equals p and the range lies inside the line;
+ *              occurrences may overlap.
+ *   RULES      td_line_rules, by value: min_words (0: off), max_word_bytes (0: off), flags (TD_LF_NEED_TERMINAL), n_phrases <=
+ *              TD_LF_MAX_PHRASES, each phrase a length of 1 .. TD_LF_PHRASE_BYTES, a kind and its bytes.  A phrase that holds 0x0A or an
+ *              ASCII upper-case byte, a length outside 1 .. 32, more than 16 phrases, a kind other than the two, unknown flag bits and
+ *              negative limits are TD_E_INVALID and write nothing.
+ *   KEPT       a line is kept when none of these holds, each counted on its own: (1) WORDS < min_words; (2) TD_LF_NEED_TERMINAL and
+ *              not TERMINAL; (3) max_word_bytes > 0 and WORD_MAX > max_word_bytes; (4) a TD_LF_PHRASE_DROP_LINE phrase occurs in it.
+ *   OUTPUT     per document the kept lines' bytes with their own LFs, in order; nothing is inserted or trimmed.  Empty rules: the identity.
+ *   COLUMNS    0 LINES  1 KEPT_LINES  2 KEPT_BYTES (the output document's length)  3 FAIL_WORDS  4 FAIL_TERMINAL  5 FAIL_LONG_WORD
+ *              6 FAIL_PHRASE  7 DOC_PHRASE_HITS (occurrences of TD_LF_PHRASE_COUNT_DOC phrases in any line of the document, kept or not)
+ *   totals     the columns' sums over all documents.
+ * Against C4 and datatrove: they strip every line before they count its words and look at its end, join the kept lines with "\n" and
+ * compare against str.lower(); here nothing is trimmed (trailing spaces are skipped for TERMINAL only, and stay in the output), a kept
+ * line keeps its own LF or lack of one, and only ASCII is folded.  Bytes behind the last document are not read.  Results are bitwise
+ * reproducible (integer sums only).  Out of scope: presets, dropping documents, a fused encode entry, non-ASCII case folding. */
+#define TD_LF_COLS 8
+#define TD_LF_MAX_PHRASES 16
+#define TD_LF_PHRASE_BYTES 32
+#define TD_LF_NEED_TERMINAL 1
+#define TD_LF_PHRASE_DROP_LINE 0
+#define TD_LF_PHRASE_COUNT_DOC 1
+typedef struct td_line_phrase {
+    uint8_t len, kind;
+    uint8_t bytes[TD_LF_PHRASE_BYTES];
+} td_line_phrase;
+typedef struct td_line_rules {
+    int64_t min_words, max_word_bytes;
+    int32_t flags, n_phrases;
+    td_line_phrase phrases[TD_LF_MAX_PHRASES];
+} td_line_rules;
+/* The contract's executable statement, on the host (no handle, no device).  out may be NULL with out_capacity == 0: the offsets (may be
+ * NULL), stats and totals (may be NULL) alone.  Argument errors are TD_E_INVALID, an output that does not fit is TD_E_CAPACITY: both
+ * write nothing. */
+int td_line_filter_host(const uint8_t* text, const int64_t* doc_offsets, int64_t n_docs, const td_line_rules* rules, uint8_t* out,
+                        int64_t out_capacity, int64_t* out_doc_offsets, int64_t* stats, int64_t* totals);
+/* DEVICE buffers, asynchronously on hip_stream (never the null stream): no synchronisation and no read-back; the rules travel in the
+ * kernels' arguments.  d_doc_offsets, d_out_doc_offsets, d_stats, d_totals and d_counts (int64[8]: [0] the output's bytes, the rest 0)
+ * are 8-byte aligned; d_text needs no alignment.  d_out, d_out_doc_offsets and d_totals may be NULL; with all three NULL the call is
+ * stats-only.  d_out must not overlap d_text.  Offsets that do not start at 0, decrease, are negative or end above n_bytes raise
+ * TD_E_INVALID through td_device_status with err_pos = the lowest such document, and then NOTHING is written.  An output that does not
+ * fit raises TD_E_CAPACITY through td_device_status; d_counts[0] holds the bytes needed then, d_out and d_out_doc_offsets are not written. */
+int td_line_filter_device(td_tokenizer* t, const void* d_text, int64_t n_bytes, const void* d_doc_offsets, int64_t n_docs,
+                          const td_line_rules* rules, void* d_out, int64_t out_capacity, void* d_out_doc_offsets, void* d_stats,
+                          void* d_totals, void* d_counts, void* hip_stream);
+/* Host buffers, synchronously; td_line_filter_host's arguments behind the handle.  out_capacity too small: TD_E_CAPACITY, the message
+ * names the bytes needed. */
+int td_line_filter(td_tokenizer* t, const uint8_t* text, const int64_t* doc_offsets, int64_t n_docs, const td_line_rules* rules,
+                   uint8_t* out, int64_t out_capacity, int64_t* out_doc_offsets, int64_t* stats, int64_t* totals);
+
 /* Options. */
 #define TD_OPT_LONG_POOL_BYTES 1 /* scratch for pieces longer than 64 bytes (default max(64 MiB, 2 x input)) */
 #define TD_OPT_PROFILE 2         /* 1: bracket the kernels of every td_encode_device call with HIP events on the

@@ -86,6 +86,7 @@ EXPORTS = [
     "td_text_stats_host", "td_text_stats_device", "td_text_stats", "td_encode_batch_text_stats",
     "td_repetition_host", "td_repetition_device", "td_repetition",
     "td_word_ngrams_host", "td_word_ngrams_device", "td_word_ngrams",
+    "td_line_filter_host", "td_line_filter_device", "td_line_filter",
 ]
 
 
@@ -281,6 +282,12 @@ def load_library():
     lib.td_word_ngrams_device.argtypes = [vp, vp, i64, vp, i64, i32, i32, i64, vp, vp, vp]
     lib.td_word_ngrams.restype = i32
     lib.td_word_ngrams.argtypes = [vp, vp, vp, i64, i32, vp, vp]
+    lib.td_line_filter_host.restype = i32
+    lib.td_line_filter_host.argtypes = [vp, vp, i64, vp, vp, i64, vp, vp, vp]
+    lib.td_line_filter_device.restype = i32
+    lib.td_line_filter_device.argtypes = [vp, vp, i64, vp, i64, vp, vp, i64, vp, vp, vp, vp, vp]
+    lib.td_line_filter.restype = i32
+    lib.td_line_filter.argtypes = [vp, vp, vp, i64, vp, vp, i64, vp, vp, vp]
     lib.td_encode_batch_token_counts.restype = i32
     lib.td_encode_batch_token_counts.argtypes = [vp, vp, vp, i64, i32, vp, vp, vp, vp, ctypes.POINTER(i64)]
     lib.td_comm_unique_id.restype = i32
@@ -1011,6 +1018,59 @@ def word_ngrams_host(text, doc_offsets, groups: int = TD_WG_ALL):
     if rc != TD_OK:
         raise TokenDaggerHipError(rc, "td_word_ngrams_host: invalid offsets, groups or arguments")
     return stats[:n_docs], totals
+
+
+TD_LF_COLS, TD_LF_MAX_PHRASES, TD_LF_PHRASE_BYTES, TD_LF_NEED_TERMINAL = 8, 16, 32, 1
+TD_LF_PHRASE_DROP_LINE, TD_LF_PHRASE_COUNT_DOC = 0, 1
+# stats[:, c] by name (include/tokendagger_hip.h, td_line_filter*, COLUMNS)
+LF_COLUMNS = ("lines", "kept_lines", "kept_bytes", "fail_words", "fail_terminal", "fail_long_word", "fail_phrase", "doc_phrase_hits")
+
+
+class LinePhrase(ctypes.Structure):
+    _fields_ = [("len", ctypes.c_uint8), ("kind", ctypes.c_uint8), ("bytes", ctypes.c_uint8 * TD_LF_PHRASE_BYTES)]
+
+
+class LineRules(ctypes.Structure):
+    """td_line_rules.  make() takes the phrases as (kind, bytes) pairs and checks nothing: the library does."""
+    _fields_ = [("min_words", ctypes.c_int64), ("max_word_bytes", ctypes.c_int64), ("flags", ctypes.c_int32), ("n_phrases", ctypes.c_int32),
+                ("phrases", LinePhrase * TD_LF_MAX_PHRASES)]
+
+    @classmethod
+    def make(cls, min_words: int = 0, max_word_bytes: int = 0, flags: int = 0, phrases=()):
+        # (what the struct cannot hold is handed on as what the library refuses: a 17th phrase, a length of 0 or above 32)
+        r = cls(min_words, max_word_bytes, flags, len(phrases))
+        for j, (kind, b) in enumerate(list(phrases)[:TD_LF_MAX_PHRASES]):
+            b = bytes(b)
+            r.phrases[j].len, r.phrases[j].kind = (len(b) if len(b) <= TD_LF_PHRASE_BYTES else 255), kind
+            for k, c in enumerate(b[:TD_LF_PHRASE_BYTES]):
+                r.phrases[j].bytes[k] = c
+        return r
+
+
+def _line_filter_args(text, doc_offsets):
+    """-> (text uint8, offsets int64, n_docs, out_doc_offsets int64[n_docs + 1], stats int64[max(n_docs, 1), 8], totals int64[8])"""
+    buf = _as_u8(text)
+    o = np.ascontiguousarray(doc_offsets, dtype=np.int64)
+    n_docs = len(o) - 1
+    return (buf, o, n_docs, np.zeros(max(n_docs + 1, 1), dtype=np.int64), np.zeros((max(n_docs, 1), TD_LF_COLS), dtype=np.int64),
+            np.zeros(TD_LF_COLS, dtype=np.int64))
+
+
+def line_filter_host(text, doc_offsets, rules: LineRules, capacity: int | None = None, want_text: bool = True):
+    """td_line_filter_host (host only, no device) -> (text uint8 | None, out_doc_offsets int64[n_docs + 1], stats int64[n_docs, 8],
+    totals int64[8]).  capacity None: the input's bytes, which always suffice."""
+    lib = load_library()
+    buf, o, n_docs, ooff, stats, totals = _line_filter_args(text, doc_offsets)
+    if n_docs >= 0 and len(o) and int(o[-1]) > len(buf):
+        raise TokenDaggerHipError(TD_E_INVALID, "td_line_filter_host: doc_offsets end behind the text")
+    cap = (len(buf) if capacity is None else capacity) if want_text else 0
+    out = np.empty(max(cap, 1), dtype=np.uint8)
+    rc = lib.td_line_filter_host(buf.ctypes.data if len(buf) else None, o.ctypes.data if len(o) else None, n_docs, ctypes.byref(rules),
+                                 out.ctypes.data if want_text else None, cap, ooff.ctypes.data, stats.ctypes.data, totals.ctypes.data)
+    if rc != TD_OK:
+        raise TokenDaggerHipError(rc, "td_line_filter_host: output capacity too small" if rc == TD_E_CAPACITY
+                                  else "td_line_filter_host: invalid offsets, rules or arguments")
+    return (out[:int(ooff[n_docs])] if want_text else None), ooff[:n_docs + 1], stats[:n_docs], totals
 
 
 class NgramSet:
@@ -2144,6 +2204,25 @@ class HipTokenizer:
         self._check(self._lib.td_word_ngrams(self._h, buf.ctypes.data if len(buf) else None, o.ctypes.data, n_docs, groups, stats.ctypes.data,
                                              totals.ctypes.data))
         return stats[:n_docs], totals
+
+    # ---- line filtering ---------------------------------------------------------------------------------------------
+    def line_filter_device(self, d_text: int, n_bytes: int, d_doc_offsets: int, n_docs: int, rules: LineRules, d_out: int, out_capacity: int,
+                           d_out_doc_offsets: int, d_stats: int, d_totals: int, d_counts: int, stream: int):
+        """td_line_filter_device: raw device pointers (d_out, d_out_doc_offsets and d_totals may be 0), asynchronous on `stream`, which
+        must not be the null stream; d_stats int64[n_docs, 8], d_totals int64[8], d_counts int64[8]; check with device_status(stream)."""
+        self._check(self._lib.td_line_filter_device(self._h, d_text or None, n_bytes, d_doc_offsets or None, n_docs, ctypes.byref(rules),
+                                                    d_out or None, out_capacity, d_out_doc_offsets or None, d_stats or None, d_totals or None,
+                                                    d_counts or None, stream or None))
+
+    def line_filter(self, text, doc_offsets, rules: LineRules, capacity: int | None = None, want_text: bool = True):
+        """td_line_filter: line_filter_host's arguments and results, computed on the device."""
+        buf, o, n_docs, ooff, stats, totals = _line_filter_args(text, doc_offsets)
+        cap = (len(buf) if capacity is None else capacity) if want_text else 0
+        out = np.empty(max(cap, 1), dtype=np.uint8)
+        self._check(self._lib.td_line_filter(self._h, buf.ctypes.data if len(buf) else None, o.ctypes.data, n_docs, ctypes.byref(rules),
+                                             out.ctypes.data if want_text else None, cap, ooff.ctypes.data, stats.ctypes.data,
+                                             totals.ctypes.data))
+        return (out[:int(ooff[n_docs])] if want_text else None), ooff[:n_docs + 1], stats[:n_docs], totals
 
     # ---- decode rows (td_decode_spec) ---------------------------------------------------------------------------
     def decode_rows(self, ids, spec: DecodeSpec, tok_offsets=None, lengths=None, n_segs: int | None = None, capacity: int | None = None):

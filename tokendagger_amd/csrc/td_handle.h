@@ -300,6 +300,10 @@ struct td_tokenizer {
     // totals on the device
     RewriteBufs wordgrams;
     DevBuf wg_carry, wg_rec, wg_cum, wg_first, wg_table, wg_cnt, wg_occ, wg_flag, wg_long_doc, wg_long_first, wg_lhead, wg_stats, wg_totals;
+    // line filtering (td_linefilter.hip): its RewriteBufs (out_off also where a device caller has no offsets), an element a tile, two
+    // pieces a tile, 16 bits a window; the host entry point's stats and totals on the device
+    RewriteBufs linefilter;
+    DevBuf lf_elems, lf_carry, lf_masks, lf_stats, lf_totals;
     int64_t mh_table_perm = 0;     // 0: no table yet
     uint64_t mh_table_seed = 0;
     std::vector<int64_t> dcr_key;  // flags, then the distinct listed ids with their bits (sorted); empty: no table yet

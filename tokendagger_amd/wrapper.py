@@ -143,6 +143,27 @@ class RepairedText(NamedTuple):
                            # continuation byte, documents whose last unit is a subpart led by a lead byte, 0, 0
 
 
+class FilteredText:
+    """Tokenizer.filter_lines (the contract: include/tokendagger_hip.h, td_line_filter*): text + offsets go to every bulk method as they
+    stand.  Only lines are dropped here: build a document mask from the columns and hand the kept documents to select_docs."""
+
+    def __init__(self, text: np.ndarray, offsets: np.ndarray, stats: np.ndarray, totals: np.ndarray):
+        self.text = text        # uint8: the documents' kept lines, concatenated
+        self.offsets = offsets  # int64 [n_docs + 1]
+        self.stats = stats      # int64 [n_docs, 8]
+        self.totals = totals    # int64 [8]: the columns' sums
+
+    def __getattr__(self, name):  # the named column views: .lines, .kept_lines, .doc_phrase_hits, ... (capi.LF_COLUMNS)
+        if name in _capi.LF_COLUMNS:
+            return self.stats[:, _capi.LF_COLUMNS.index(name)]
+        raise AttributeError(name)
+
+
+def _lf_phrase(p) -> bytes:
+    """a phrase as the rule compares it: bytes, ASCII upper case folded"""
+    return (p.encode("utf-8") if isinstance(p, str) else bytes(p)).lower()
+
+
 class TextStats:
     """Tokenizer.text_stats (the contract: include/tokendagger_hip.h, td_text_stats*): the statistics the heuristic quality filters are
     built from.  No thresholds here: build a mask from the columns and the ratios and hand the kept documents to select_docs."""
@@ -602,6 +623,21 @@ class Tokenizer:
             return TextStats(*hip.text_stats(buf, np.asarray(offsets, dtype=np.int64), g))
         except _capi.TokenDaggerHipError as ex:
             raise TokenDaggerError(f"Text statistics failed: {ex}")
+
+    def filter_lines(self, text: np.ndarray | bytes, offsets: np.ndarray, min_words: int = 0, max_word_bytes: int = 0,
+                     need_terminal: bool = False, drop_line_phrases=(), count_doc_phrases=()) -> FilteredText:
+        """Concatenated bytes + int64 document offsets -> FilteredText: the lines that pass the rules, on the GPU.  A line is dropped
+        when it has fewer than min_words words, no terminal punctuation mark at its end (need_terminal), a word of more than
+        max_word_bytes bytes, or one of drop_line_phrases in it (ASCII case folded); count_doc_phrases are counted per document."""
+        phrases = ([(_capi.TD_LF_PHRASE_DROP_LINE, _lf_phrase(p)) for p in drop_line_phrases] +
+                   [(_capi.TD_LF_PHRASE_COUNT_DOC, _lf_phrase(p)) for p in count_doc_phrases])
+        rules = _capi.LineRules.make(min_words, max_word_bytes, _capi.TD_LF_NEED_TERMINAL if need_terminal else 0, phrases)
+        hip = _capi.HipTokenizer.borrow(self._core_bpe.handle())
+        buf = np.frombuffer(text, dtype=np.uint8) if isinstance(text, (bytes, bytearray)) else text
+        try:
+            return FilteredText(*hip.line_filter(buf, np.asarray(offsets, dtype=np.int64), rules))
+        except _capi.TokenDaggerHipError as ex:
+            raise TokenDaggerError(f"Line filtering failed: {ex}")
 
     def repetition_stats(self, text: np.ndarray | bytes, offsets: np.ndarray, groups: str = "all") -> RepetitionStats:
         """Concatenated bytes + int64 document offsets -> RepetitionStats (duplicate lines and paragraphs per document), on the GPU."""
