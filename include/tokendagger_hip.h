@@ -1288,6 +1288,64 @@ int td_line_filter_device(td_tokenizer* t, const void* d_text, int64_t n_bytes, 
 int td_line_filter(td_tokenizer* t, const uint8_t* text, const int64_t* doc_offsets, int64_t n_docs, const td_line_rules* rules,
                    uint8_t* out, int64_t out_capacity, int64_t* out_doc_offsets, int64_t* stats, int64_t* totals);
 
+/* ---- address masking: replace e-mail and IPv4 addresses by placeholders (td_mask.hip) ----------------------------------------------------
+ * The personal-data step in front of tokenisation (datatrove's PIIFormatter): text + doc_offsets[n_docs + 1] (int64: from 0, non-decreasing,
+ * ending at or below n_bytes) -> the text with every matched address replaced, out_doc_offsets[n_docs + 1], stats[n_docs][TD_MA_COLS]
+ * (int64, row-major) and totals[TD_MA_COLS].  No presets.  Host and device compile the same statement of the rule (td_mask_args.h).  No
+ * table of the handle is used.  All classes are ASCII bytes: L = [A-Za-z0-9._%+-], D = [A-Za-z0-9.-].  Nothing reaches across a document's
+ * start or end: "none" below is the document's edge.
+ *   E-MAIL     every byte '@' at position a is decided on its own.  LOCAL is the maximal run of L bytes that ends at a - 1: 1 .. 64 bytes,
+ *              its first and last byte not '.', the byte in front of it none or not '@'.  RUN is the maximal run of D bytes from a + 1:
+ *              1 .. 254 bytes, the byte behind it none or not '@'.  DOMAIN is RUN without one trailing '.' (that dot stays in the text);
+ *              split at '.', it has at least two labels, every label 1 .. 63 bytes and neither starting nor ending with '-', the last label
+ *              2 .. 24 letters.  The match is LOCAL '@' DOMAIN, at most 254 bytes.
+ *   IPV4       o.o.o.o at [p, q): each o 1 .. 3 digits of value at most 255 with no leading zero but "0" itself; the byte at p - 1 none or
+ *              not in L ('@' is allowed there); the byte n1 at q none, or not in L and not '@', or '.' with the byte behind it none or not
+ *              in L and not '@'.  With TD_MA_KEEP_PRIVATE_IPS a match in 0/8, 10/8, 127/8, 169.254/16, 172.16/12, 192.168/16 or 224/3 is
+ *              counted (IPS_KEPT) and left as it is.
+ *              No two matches overlap and none depends on another: "a@b.co@d.org" matches nowhere, and no IPv4 lies inside a matched e-mail.
+ *   RULES      td_mask_rules, by value: flags (TD_MA_EMAILS, TD_MA_IPS, TD_MA_KEEP_PRIVATE_IPS) and per kind 1 .. TD_MA_MAX_LITERALS
+ *              replacement literals of 0 .. TD_MA_LITERAL_BYTES bytes.  A match is replaced by literal number FNV-1a-32(matched bytes) % n
+ *              of its kind: the same address always gets the same placeholder, whatever the batch.  Unknown flag bits, a kind that is on
+ *              with no literal, a count outside 0 .. 8 and a length above 32 are TD_E_INVALID and write nothing.  No flag: the identity.
+ *   COLUMNS    0 EMAILS replaced  1 IPS replaced  2 IPS_KEPT  3 BYTES_OUT_OF (matched bytes removed)  4 BYTES_IN (placeholder bytes
+ *              inserted)  5 OUT_BYTES (the output document's length)
+ *   totals     the columns' sums over all documents.
+ * Against datatrove: the boundaries are stricter (its patterns accept an address next to more of the same class), the placeholder is chosen
+ * by hash and not by random.choice, addresses are ASCII only, and the private ranges above stand in for ipaddress.is_global.  Bytes behind
+ * the last document are not read.  Results are bitwise reproducible.  Out of scope: IPv6, phone numbers, URLs, internationalised addresses,
+ * a list of the matches' positions, a fused encode entry. */
+#define TD_MA_COLS 6
+#define TD_MA_MAX_LITERALS 8
+#define TD_MA_LITERAL_BYTES 32
+#define TD_MA_EMAILS 1
+#define TD_MA_IPS 2
+#define TD_MA_KEEP_PRIVATE_IPS 4
+typedef struct td_mask_literal {
+    uint8_t len;
+    uint8_t bytes[TD_MA_LITERAL_BYTES];
+} td_mask_literal;
+typedef struct td_mask_rules {
+    int32_t flags, n_emails, n_ips;
+    td_mask_literal emails[TD_MA_MAX_LITERALS], ips[TD_MA_MAX_LITERALS];
+} td_mask_rules;
+/* The contract's executable statement, on the host (no handle, no device).  out may be NULL with out_capacity == 0: the offsets (may be
+ * NULL), stats and totals (may be NULL) alone.  Argument errors are TD_E_INVALID, an output that does not fit is TD_E_CAPACITY: both
+ * write nothing. */
+int td_mask_addresses_host(const uint8_t* text, const int64_t* doc_offsets, int64_t n_docs, const td_mask_rules* rules, uint8_t* out,
+                           int64_t out_capacity, int64_t* out_doc_offsets, int64_t* stats, int64_t* totals);
+/* DEVICE buffers, asynchronously on hip_stream (never the null stream): no synchronisation and no read-back; the rules travel in the
+ * kernels' arguments.  Alignment, the arguments that may be NULL, bad offsets (TD_E_INVALID at the lowest bad document, nothing written)
+ * and an output that does not fit (TD_E_CAPACITY, d_counts[0] the bytes needed, d_out and d_out_doc_offsets not written) are as in
+ * td_line_filter_device.  d_counts: int64[8], [0] the output's bytes, the rest 0.  The output may be LONGER than the text. */
+int td_mask_addresses_device(td_tokenizer* t, const void* d_text, int64_t n_bytes, const void* d_doc_offsets, int64_t n_docs,
+                             const td_mask_rules* rules, void* d_out, int64_t out_capacity, void* d_out_doc_offsets, void* d_stats,
+                             void* d_totals, void* d_counts, void* hip_stream);
+/* Host buffers, synchronously; td_mask_addresses_host's arguments behind the handle.  out_capacity too small: TD_E_CAPACITY, the message
+ * names the bytes needed. */
+int td_mask_addresses(td_tokenizer* t, const uint8_t* text, const int64_t* doc_offsets, int64_t n_docs, const td_mask_rules* rules,
+                      uint8_t* out, int64_t out_capacity, int64_t* out_doc_offsets, int64_t* stats, int64_t* totals);
+
 /* Options. */
 #define TD_OPT_LONG_POOL_BYTES 1 /* scratch for pieces longer than 64 bytes (default max(64 MiB, 2 x input)) */
 #define TD_OPT_PROFILE 2         /* 1: bracket the kernels of every td_encode_device call with HIP events on the

@@ -87,6 +87,7 @@ EXPORTS = [
     "td_repetition_host", "td_repetition_device", "td_repetition",
     "td_word_ngrams_host", "td_word_ngrams_device", "td_word_ngrams",
     "td_line_filter_host", "td_line_filter_device", "td_line_filter",
+    "td_mask_addresses_host", "td_mask_addresses_device", "td_mask_addresses",
 ]
 
 
@@ -288,6 +289,12 @@ def load_library():
     lib.td_line_filter_device.argtypes = [vp, vp, i64, vp, i64, vp, vp, i64, vp, vp, vp, vp, vp]
     lib.td_line_filter.restype = i32
     lib.td_line_filter.argtypes = [vp, vp, vp, i64, vp, vp, i64, vp, vp, vp]
+    lib.td_mask_addresses_host.restype = i32
+    lib.td_mask_addresses_host.argtypes = [vp, vp, i64, vp, vp, i64, vp, vp, vp]
+    lib.td_mask_addresses_device.restype = i32
+    lib.td_mask_addresses_device.argtypes = [vp, vp, i64, vp, i64, vp, vp, i64, vp, vp, vp, vp, vp]
+    lib.td_mask_addresses.restype = i32
+    lib.td_mask_addresses.argtypes = [vp, vp, vp, i64, vp, vp, i64, vp, vp, vp]
     lib.td_encode_batch_token_counts.restype = i32
     lib.td_encode_batch_token_counts.argtypes = [vp, vp, vp, i64, i32, vp, vp, vp, vp, ctypes.POINTER(i64)]
     lib.td_comm_unique_id.restype = i32
@@ -1071,6 +1078,72 @@ def line_filter_host(text, doc_offsets, rules: LineRules, capacity: int | None =
         raise TokenDaggerHipError(rc, "td_line_filter_host: output capacity too small" if rc == TD_E_CAPACITY
                                   else "td_line_filter_host: invalid offsets, rules or arguments")
     return (out[:int(ooff[n_docs])] if want_text else None), ooff[:n_docs + 1], stats[:n_docs], totals
+
+
+TD_MA_COLS, TD_MA_MAX_LITERALS, TD_MA_LITERAL_BYTES = 6, 8, 32
+TD_MA_EMAILS, TD_MA_IPS, TD_MA_KEEP_PRIVATE_IPS = 1, 2, 4
+# stats[:, c] by name (include/tokendagger_hip.h, td_mask_addresses*, COLUMNS)
+MA_COLUMNS = ("emails", "ips", "ips_kept", "bytes_out_of", "bytes_in", "out_bytes")
+
+
+class MaskLiteral(ctypes.Structure):
+    _fields_ = [("len", ctypes.c_uint8), ("bytes", ctypes.c_uint8 * TD_MA_LITERAL_BYTES)]
+
+
+class MaskRules(ctypes.Structure):
+    """td_mask_rules.  make() takes the replacement literals of either kind and checks nothing: the library does."""
+    _fields_ = [("flags", ctypes.c_int32), ("n_emails", ctypes.c_int32), ("n_ips", ctypes.c_int32),
+                ("emails", MaskLiteral * TD_MA_MAX_LITERALS), ("ips", MaskLiteral * TD_MA_MAX_LITERALS)]
+
+    @classmethod
+    def make(cls, flags: int = 0, emails=(), ips=()):
+        # (what the struct cannot hold is handed on as what the library refuses: a 9th literal, a length above 32)
+        r = cls(flags, len(emails), len(ips))
+        for dst, lits in ((r.emails, emails), (r.ips, ips)):
+            for j, b in enumerate(list(lits)[:TD_MA_MAX_LITERALS]):
+                b = bytes(b)
+                dst[j].len = len(b) if len(b) <= TD_MA_LITERAL_BYTES else 255
+                for k, c in enumerate(b[:TD_MA_LITERAL_BYTES]):
+                    dst[j].bytes[k] = c
+        return r
+
+
+def _mask_args(text, doc_offsets):
+    """-> (text uint8, offsets int64, n_docs, out_doc_offsets int64[n_docs + 1], stats int64[max(n_docs, 1), 6], totals int64[6])"""
+    buf = _as_u8(text)
+    o = np.ascontiguousarray(doc_offsets, dtype=np.int64)
+    n_docs = len(o) - 1
+    return (buf, o, n_docs, np.zeros(max(n_docs + 1, 1), dtype=np.int64), np.zeros((max(n_docs, 1), TD_MA_COLS), dtype=np.int64),
+            np.zeros(TD_MA_COLS, dtype=np.int64))
+
+
+def _mask_call(fn, what, text, doc_offsets, rules, capacity, want_text):
+    """fn(text, offsets, n_docs, rules, out, capacity, out_doc_offsets, stats, totals) -> a status.  capacity None: the output's own
+    bytes, from a call for the stats alone (the output may be longer than the text)."""
+    buf, o, n_docs, ooff, stats, totals = _mask_args(text, doc_offsets)
+    if n_docs >= 0 and len(o) and int(o[-1]) > len(buf):
+        raise TokenDaggerHipError(TD_E_INVALID, f"{what}: doc_offsets end behind the text")
+    args = (buf.ctypes.data if len(buf) else None, o.ctypes.data if len(o) else None, n_docs, ctypes.byref(rules))
+    if want_text and capacity is None:
+        fn(*args, None, 0, None, stats.ctypes.data, totals.ctypes.data)
+        capacity = int(totals[TD_MA_COLS - 1])
+    cap = capacity if want_text else 0
+    out = np.empty(max(cap, 1), dtype=np.uint8)
+    fn(*args, out.ctypes.data if want_text else None, cap, ooff.ctypes.data, stats.ctypes.data, totals.ctypes.data)
+    return (out[:int(ooff[n_docs])] if want_text else None), ooff[:n_docs + 1], stats[:n_docs], totals
+
+
+def mask_addresses_host(text, doc_offsets, rules: MaskRules, capacity: int | None = None, want_text: bool = True):
+    """td_mask_addresses_host (host only, no device) -> (text uint8 | None, out_doc_offsets int64[n_docs + 1], stats int64[n_docs, 6],
+    totals int64[6])."""
+    lib = load_library()
+
+    def fn(*args):
+        rc = lib.td_mask_addresses_host(*args)
+        if rc != TD_OK:
+            raise TokenDaggerHipError(rc, "td_mask_addresses_host: output capacity too small" if rc == TD_E_CAPACITY
+                                      else "td_mask_addresses_host: invalid offsets, rules or arguments")
+    return _mask_call(fn, "td_mask_addresses_host", text, doc_offsets, rules, capacity, want_text)
 
 
 class NgramSet:
@@ -2223,6 +2296,21 @@ class HipTokenizer:
                                              out.ctypes.data if want_text else None, cap, ooff.ctypes.data, stats.ctypes.data,
                                              totals.ctypes.data))
         return (out[:int(ooff[n_docs])] if want_text else None), ooff[:n_docs + 1], stats[:n_docs], totals
+
+    # ---- address masking --------------------------------------------------------------------------------------------
+    def mask_addresses_device(self, d_text: int, n_bytes: int, d_doc_offsets: int, n_docs: int, rules: MaskRules, d_out: int,
+                              out_capacity: int, d_out_doc_offsets: int, d_stats: int, d_totals: int, d_counts: int, stream: int):
+        """td_mask_addresses_device: raw device pointers (d_out, d_out_doc_offsets and d_totals may be 0), asynchronous on `stream`,
+        which must not be the null stream; d_stats int64[n_docs, 6], d_totals int64[6], d_counts int64[8]; check with
+        device_status(stream)."""
+        self._check(self._lib.td_mask_addresses_device(self._h, d_text or None, n_bytes, d_doc_offsets or None, n_docs, ctypes.byref(rules),
+                                                       d_out or None, out_capacity, d_out_doc_offsets or None, d_stats or None,
+                                                       d_totals or None, d_counts or None, stream or None))
+
+    def mask_addresses(self, text, doc_offsets, rules: MaskRules, capacity: int | None = None, want_text: bool = True):
+        """td_mask_addresses: mask_addresses_host's arguments and results, computed on the device."""
+        return _mask_call(lambda *args: self._check(self._lib.td_mask_addresses(self._h, *args)), "td_mask_addresses", text, doc_offsets,
+                          rules, capacity, want_text)
 
     # ---- decode rows (td_decode_spec) ---------------------------------------------------------------------------
     def decode_rows(self, ids, spec: DecodeSpec, tok_offsets=None, lengths=None, n_segs: int | None = None, capacity: int | None = None):

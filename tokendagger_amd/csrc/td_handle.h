@@ -304,6 +304,10 @@ struct td_tokenizer {
     // pieces a tile, 16 bits a window; the host entry point's stats and totals on the device
     RewriteBufs linefilter;
     DevBuf lf_elems, lf_carry, lf_masks, lf_stats, lf_totals;
+    // address masking (td_mask.hip): its RewriteBufs (out_off also where a device caller has no offsets), a word a tile; the host entry
+    // point's stats and totals on the device
+    RewriteBufs mask;
+    DevBuf ma_dirty, ma_stats, ma_totals;
     int64_t mh_table_perm = 0;     // 0: no table yet
     uint64_t mh_table_seed = 0;
     std::vector<int64_t> dcr_key;  // flags, then the distinct listed ids with their bits (sorted); empty: no table yet

@@ -159,6 +159,22 @@ class FilteredText:
         raise AttributeError(name)
 
 
+class MaskedText:
+    """Tokenizer.mask_addresses (the contract: include/tokendagger_hip.h, td_mask_addresses*): text + offsets go to every bulk method as
+    they stand."""
+
+    def __init__(self, text: np.ndarray, offsets: np.ndarray, stats: np.ndarray, totals: np.ndarray):
+        self.text = text        # uint8: the documents with their addresses replaced, concatenated
+        self.offsets = offsets  # int64 [n_docs + 1]
+        self.stats = stats      # int64 [n_docs, 6]
+        self.totals = totals    # int64 [6]: the columns' sums
+
+    def __getattr__(self, name):  # the named column views: .emails, .ips, .ips_kept, ... (capi.MA_COLUMNS)
+        if name in _capi.MA_COLUMNS:
+            return self.stats[:, _capi.MA_COLUMNS.index(name)]
+        raise AttributeError(name)
+
+
 def _lf_phrase(p) -> bytes:
     """a phrase as the rule compares it: bytes, ASCII upper case folded"""
     return (p.encode("utf-8") if isinstance(p, str) else bytes(p)).lower()
@@ -638,6 +654,23 @@ class Tokenizer:
             return FilteredText(*hip.line_filter(buf, np.asarray(offsets, dtype=np.int64), rules))
         except _capi.TokenDaggerHipError as ex:
             raise TokenDaggerError(f"Line filtering failed: {ex}")
+
+    def mask_addresses(self, text: np.ndarray | bytes, offsets: np.ndarray, emails=(b"email@example.com",),
+                       ips=(b"22.214.171.124", b"126.96.36.199", b"188.8.131.52", b"184.108.40.206", b"220.127.116.11", b"18.104.22.168"),
+                       keep_private_ips: bool = True) -> MaskedText:
+        """Concatenated bytes + int64 document offsets -> MaskedText: every e-mail address replaced by one of `emails` and every IPv4
+        address by one of `ips` (up to 8 literals of up to 32 bytes each, chosen by a hash of the address; an empty tuple leaves the kind
+        alone), on the GPU.  keep_private_ips: addresses of the private, loopback, link-local and multicast ranges stay and are counted."""
+        lits = [[x.encode("utf-8") if isinstance(x, str) else bytes(x) for x in kind] for kind in (emails, ips)]
+        flags = ((_capi.TD_MA_EMAILS if lits[0] else 0) | (_capi.TD_MA_IPS if lits[1] else 0) |
+                 (_capi.TD_MA_KEEP_PRIVATE_IPS if keep_private_ips else 0))
+        rules = _capi.MaskRules.make(flags, lits[0], lits[1])
+        hip = _capi.HipTokenizer.borrow(self._core_bpe.handle())
+        buf = np.frombuffer(text, dtype=np.uint8) if isinstance(text, (bytes, bytearray)) else text
+        try:
+            return MaskedText(*hip.mask_addresses(buf, np.asarray(offsets, dtype=np.int64), rules))
+        except _capi.TokenDaggerHipError as ex:
+            raise TokenDaggerError(f"Address masking failed: {ex}")
 
     def repetition_stats(self, text: np.ndarray | bytes, offsets: np.ndarray, groups: str = "all") -> RepetitionStats:
         """Concatenated bytes + int64 document offsets -> RepetitionStats (duplicate lines and paragraphs per document), on the GPU."""
