@@ -1346,6 +1346,74 @@ int td_mask_addresses_device(td_tokenizer* t, const void* d_text, int64_t n_byte
 int td_mask_addresses(td_tokenizer* t, const uint8_t* text, const int64_t* doc_offsets, int64_t n_docs, const td_mask_rules* rules,
                       uint8_t* out, int64_t out_capacity, int64_t* out_doc_offsets, int64_t* stats, int64_t* totals);
 
+/* ---- word-list matches: listed words and phrases counted per document (td_wordlist.hip) ----------------------------------------------------
+ * "Does this document contain words from a list?": Gopher's stop-word rule, C4's bad-words rule, boilerplate phrases, licence markers,
+ * canary strings given as text, per-language marker words.  Text + doc_offsets[n_docs + 1] (int64: from 0, non-decreasing, ending at or
+ * below n_bytes) + a word set -> stats[n_docs][TD_WL_COLS] (int64, row-major), totals[TD_WL_COLS] and entry_hits[n_entries].  No
+ * thresholds and no lists here: the caller builds a mask from the columns and hands it to td_select_docs.  Host and device compile the
+ * same statement of the rule (td_wordlist_args.h).  No table of the handle is used: every pattern kind gives the same.
+ *   DOCUMENTS  are independent: nothing reaches across a document's start or end; "edge" below is the document's edge.
+ *   FOLD       with TD_WL_FOLD_ASCII the text's bytes 'A' .. 'Z' compare as 'a' .. 'z'; nothing else folds.  An entry that holds an ASCII
+ *              upper-case byte under this flag is TD_E_INVALID.
+ *   WORD BYTE  [0-9A-Za-z_] or any byte >= 0x80: every byte of a multi-byte character is word content, so "the" beside U+00E9 is no match.
+ *              Against Python's \W: U+2019, U+00A0 and every other non-ASCII punctuation or space are word content here, so "the" beside
+ *              a curly quote or a no-break space is no match either.
+ *   OCCURRENCE entry e of L bytes occurs at byte p when the folded text[p, p + L) equals e, the range lies inside the document,
+ *              text[p - 1] is the edge or no word byte, and text[p + L] is the edge or no word byte.  With the set's flag TD_WL_ANYWHERE
+ *              both conditions on the neighbours are dropped (lists for Chinese, Japanese and Thai).  In either mode occurrences of
+ *              different entries may overlap and nest ("new york", "york") and each one counts; the condition on the neighbours is the
+ *              same whatever bytes an entry begins or ends with ("c++", ".net"); an entry may hold spaces or punctuation and is matched
+ *              byte for byte: "a  b" with two spaces is not "a b".
+ *   SET        1 .. TD_WL_MAX_ENTRIES entries: entry_bytes (flat), entry_offsets[n_entries + 1] (int64, from 0) and entry_groups[n_entries]
+ *              (int32, NULL: all 0); each entry 1 .. TD_WL_ENTRY_BYTES bytes with a group in 0 .. 63; flags TD_WL_FOLD_ASCII,
+ *              TD_WL_ANYWHERE.  TD_E_INVALID with *err_pos (may be NULL) the lowest entry that is empty, longer than 64 bytes, of a group
+ *              outside 0 .. 63, upper case under TD_WL_FOLD_ASCII, or equal to an earlier entry (the second one is named); -1 where no
+ *              entry is to blame (the count, unknown flag bits, a NULL pointer, offsets that do not start at 0).
+ *   COLUMNS    0 HITS (occurrences)  1 GROUPS (bit g is set iff an entry of group g occurs; read it as unsigned: bit 63 is a group)
+ *              2 FIRST_HIT (the lowest p - document start of any occurrence, or -1)  3 HIT_BYTES (the occurrences' lengths, overlaps
+ *              counted each time)
+ *   totals     [0] and [3] the columns' sums, [1] the OR of the documents' GROUPS, [2] the documents with a hit.
+ *   entry_hits the occurrences of each entry over the call, in the order the entries were given.
+ * Gopher's stop-word rule is eight entries of one group each and popcount(GROUPS) >= 2; C4's bad-words rule is HITS == 0.  The lookup
+ * hashes a start's bytes only to FIND an entry and compares the bytes before it counts anything; results are integer sums, ORs and
+ * minima: bitwise reproducible, and never a function of the hash.  Bytes behind the last document are not read.  Out of scope: non-ASCII
+ * case folding, a list of the matches' positions, masking the matched bytes, regex entries, a fused encode entry, built-in lists. */
+#define TD_WL_COLS 4
+#define TD_WL_ENTRY_BYTES 64
+#define TD_WL_MAX_ENTRIES 65535
+#define TD_WL_FOLD_ASCII 1
+#define TD_WL_ANYWHERE 2
+#define TD_WL_NO_LDS 1
+typedef struct td_word_set td_word_set;
+/* Checks the list, builds the lookup table on the host and uploads it to t's device (synchronous).  The set is immutable afterwards: any
+ * handle on that device, td_clone's included, may use it on any stream, concurrently.  It does not keep t. */
+int td_word_set_create(td_tokenizer* t, const uint8_t* entry_bytes, const int64_t* entry_offsets, const int32_t* entry_groups,
+                       int64_t n_entries, int flags, td_word_set** out, int64_t* err_pos);
+/* Frees the set's device memory at once, like hipFree: the caller must have finished (synchronised) the work that uses the set. */
+void td_word_set_destroy(td_word_set* set);
+#define TD_WORD_INFO_ENTRIES 1     /* the entries */
+#define TD_WORD_INFO_MAX_LEN 2     /* the longest, in bytes: what a tile reads behind itself */
+#define TD_WORD_INFO_FLAGS 3       /* the set's flags */
+#define TD_WORD_INFO_TABLE_BYTES 4 /* the table, the entries' offsets, bytes and groups: the device memory the set holds */
+#define TD_WORD_INFO_RESIDENT 5    /* 1: that fits the kernels' LDS budget and every workgroup probes its own copy there; 0: probed in global memory */
+int64_t td_word_set_info(const td_word_set* set, int what); /* -1: no such value */
+/* The contract's executable statement, on the host (no handle, no device, no set, no hash: the list itself, sorted).  totals and
+ * entry_hits may be NULL.  Argument errors (a bad list, offsets that do not start at 0 or decrease) are TD_E_INVALID and write nothing
+ * but *err_pos. */
+int td_word_matches_host(const uint8_t* entry_bytes, const int64_t* entry_offsets, const int32_t* entry_groups, int64_t n_entries, int flags,
+                         const uint8_t* text, const int64_t* doc_offsets, int64_t n_docs, int64_t* stats, int64_t* totals,
+                         int64_t* entry_hits, int64_t* err_pos);
+/* DEVICE buffers, asynchronously on hip_stream (never the null stream): no synchronisation and no read-back; the zeroing of the outputs
+ * is part of the launches.  d_doc_offsets, d_stats, d_totals and d_entry_hits are 8-byte aligned; d_text needs no alignment; d_totals and
+ * d_entry_hits may be NULL.  flags: 0, or TD_WL_NO_LDS, which probes a resident set in global memory too (for tests and A/B runs; the
+ * results are the same).  Offsets that do not start at 0, decrease, are negative or end above n_bytes raise TD_E_INVALID through
+ * td_device_status with err_pos = the lowest such document, and then NOTHING is written. */
+int td_word_matches_device(td_tokenizer* t, const td_word_set* set, const void* d_text, int64_t n_bytes, const void* d_doc_offsets,
+                           int64_t n_docs, int flags, void* d_stats, void* d_totals, void* d_entry_hits, void* hip_stream);
+/* Host buffers, synchronously; the offsets are checked like every host entry point's, before any launch. */
+int td_word_matches(td_tokenizer* t, const td_word_set* set, const uint8_t* text, const int64_t* doc_offsets, int64_t n_docs, int64_t* stats,
+                    int64_t* totals, int64_t* entry_hits);
+
 /* Options. */
 #define TD_OPT_LONG_POOL_BYTES 1 /* scratch for pieces longer than 64 bytes (default max(64 MiB, 2 x input)) */
 #define TD_OPT_PROFILE 2         /* 1: bracket the kernels of every td_encode_device call with HIP events on the

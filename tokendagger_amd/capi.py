@@ -88,6 +88,7 @@ EXPORTS = [
     "td_word_ngrams_host", "td_word_ngrams_device", "td_word_ngrams",
     "td_line_filter_host", "td_line_filter_device", "td_line_filter",
     "td_mask_addresses_host", "td_mask_addresses_device", "td_mask_addresses",
+    "td_word_set_create", "td_word_set_destroy", "td_word_set_info", "td_word_matches_host", "td_word_matches_device", "td_word_matches",
 ]
 
 
@@ -295,6 +296,18 @@ def load_library():
     lib.td_mask_addresses_device.argtypes = [vp, vp, i64, vp, i64, vp, vp, i64, vp, vp, vp, vp, vp]
     lib.td_mask_addresses.restype = i32
     lib.td_mask_addresses.argtypes = [vp, vp, vp, i64, vp, vp, i64, vp, vp, vp]
+    lib.td_word_set_create.restype = i32
+    lib.td_word_set_create.argtypes = [vp, vp, vp, vp, i64, i32, ctypes.POINTER(vp), ctypes.POINTER(i64)]
+    lib.td_word_set_destroy.restype = None
+    lib.td_word_set_destroy.argtypes = [vp]
+    lib.td_word_set_info.restype = i64
+    lib.td_word_set_info.argtypes = [vp, i32]
+    lib.td_word_matches_host.restype = i32
+    lib.td_word_matches_host.argtypes = [vp, vp, vp, i64, i32, vp, vp, i64, vp, vp, vp, ctypes.POINTER(i64)]
+    lib.td_word_matches_device.restype = i32
+    lib.td_word_matches_device.argtypes = [vp, vp, vp, i64, vp, i64, i32, vp, vp, vp, vp]
+    lib.td_word_matches.restype = i32
+    lib.td_word_matches.argtypes = [vp, vp, vp, vp, i64, vp, vp, vp]
     lib.td_encode_batch_token_counts.restype = i32
     lib.td_encode_batch_token_counts.argtypes = [vp, vp, vp, i64, i32, vp, vp, vp, vp, ctypes.POINTER(i64)]
     lib.td_comm_unique_id.restype = i32
@@ -1144,6 +1157,88 @@ def mask_addresses_host(text, doc_offsets, rules: MaskRules, capacity: int | Non
             raise TokenDaggerHipError(rc, "td_mask_addresses_host: output capacity too small" if rc == TD_E_CAPACITY
                                       else "td_mask_addresses_host: invalid offsets, rules or arguments")
     return _mask_call(fn, "td_mask_addresses_host", text, doc_offsets, rules, capacity, want_text)
+
+
+TD_WL_COLS, TD_WL_ENTRY_BYTES, TD_WL_MAX_ENTRIES = 4, 64, 65535
+TD_WL_FOLD_ASCII, TD_WL_ANYWHERE, TD_WL_NO_LDS = 1, 2, 1
+TD_WORD_INFO = {"entries": 1, "max_len": 2, "flags": 3, "table_bytes": 4, "resident": 5}
+# stats[:, c] by name (include/tokendagger_hip.h, td_word_matches*, COLUMNS)
+WL_COLUMNS = ("hits", "groups", "first_hit", "hit_bytes")
+
+
+def word_list(entries, groups=None):
+    """a list of bytes entries -> (bytes uint8 flat, offsets int64[n + 1], groups int32[n] | None); nothing is checked: the library does"""
+    entries = [bytes(e) for e in entries]
+    flat = np.frombuffer(b"".join(entries), dtype=np.uint8) if entries else np.zeros(0, dtype=np.uint8)
+    off = np.zeros(len(entries) + 1, dtype=np.int64)
+    off[1:] = np.cumsum([len(e) for e in entries])
+    return np.ascontiguousarray(flat), off, None if groups is None else np.ascontiguousarray(groups, dtype=np.int32)
+
+
+def _word_matches_args(text, doc_offsets, n_entries):
+    """-> (text uint8, offsets int64, n_docs, stats int64[max(n_docs, 1), 4], totals int64[4], entry_hits int64[max(n_entries, 1)])"""
+    buf = _as_u8(text)
+    o = np.ascontiguousarray(doc_offsets, dtype=np.int64)
+    n_docs = len(o) - 1
+    return (buf, o, n_docs, np.zeros((max(n_docs, 1), TD_WL_COLS), dtype=np.int64), np.zeros(TD_WL_COLS, dtype=np.int64),
+            np.zeros(max(n_entries, 1), dtype=np.int64))
+
+
+def word_matches_host(entries, groups, flags: int, text, doc_offsets):
+    """td_word_matches_host (host only, no device) -> (stats int64[n_docs, 4], totals int64[4], entry_hits int64[n_entries]).  A bad list
+    raises TokenDaggerHipError with .pos, the entry to blame or -1."""
+    lib = load_library()
+    eb, eo, eg = word_list(entries, groups)
+    buf, o, n_docs, stats, totals, hits = _word_matches_args(text, doc_offsets, len(eo) - 1)
+    if n_docs >= 0 and len(o) and int(o[-1]) > len(buf):
+        raise TokenDaggerHipError(TD_E_INVALID, "td_word_matches_host: doc_offsets end behind the text")
+    pos = ctypes.c_int64(-1)
+    rc = lib.td_word_matches_host(eb.ctypes.data if len(eb) else None, eo.ctypes.data, eg.ctypes.data if eg is not None else None, len(eo) - 1,
+                                  flags, buf.ctypes.data if len(buf) else None, o.ctypes.data if len(o) else None, n_docs, stats.ctypes.data,
+                                  totals.ctypes.data, hits.ctypes.data, ctypes.byref(pos))
+    if rc != TD_OK:
+        ex = TokenDaggerHipError(rc, f"td_word_matches_host: invalid list (entry {pos.value}), offsets or arguments")
+        ex.pos = pos.value
+        raise ex
+    return stats[:n_docs], totals, hits[:len(eo) - 1]
+
+
+class WordSet:
+    """Owns one td_word_set: a checked word list and its lookup table on a tokenizer's device.  Immutable; any handle on that device may
+    use it.  A context manager; close() frees the device memory at once, so the work that uses the set must be done.  A bad list raises
+    TokenDaggerHipError with .pos, the entry to blame or -1."""
+
+    def __init__(self, tok: "HipTokenizer", entries, groups=None, flags: int = TD_WL_FOLD_ASCII):
+        self._lib = tok._lib
+        self._h = None
+        eb, eo, eg = word_list(entries, groups)
+        h, pos = ctypes.c_void_p(), ctypes.c_int64(-1)
+        try:
+            tok._check(self._lib.td_word_set_create(tok._h, eb.ctypes.data if len(eb) else None, eo.ctypes.data,
+                                                    eg.ctypes.data if eg is not None else None, len(eo) - 1, flags, ctypes.byref(h), ctypes.byref(pos)))
+        except TokenDaggerHipError as ex:
+            ex.pos = pos.value
+            raise
+        self._h = h
+        self.n_entries = len(eo) - 1
+
+    @property
+    def info(self) -> dict[str, int]:
+        """entries, max_len, flags, table_bytes, resident."""
+        return {k: int(self._lib.td_word_set_info(self._h, v)) for k, v in TD_WORD_INFO.items()}
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.td_word_set_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
 
 
 class NgramSet:
@@ -2311,6 +2406,26 @@ class HipTokenizer:
         """td_mask_addresses: mask_addresses_host's arguments and results, computed on the device."""
         return _mask_call(lambda *args: self._check(self._lib.td_mask_addresses(self._h, *args)), "td_mask_addresses", text, doc_offsets,
                           rules, capacity, want_text)
+
+    # ---- word-list matches (td_word_set) ------------------------------------------------------------------------------
+    def word_set(self, entries, groups=None, flags: int = TD_WL_FOLD_ASCII) -> WordSet:
+        """td_word_set_create: a list of bytes entries, their groups (0 .. 63; None: all 0) and TD_WL_FOLD_ASCII | TD_WL_ANYWHERE."""
+        return WordSet(self, entries, groups, flags)
+
+    def word_matches_device(self, wset: WordSet, d_text: int, n_bytes: int, d_doc_offsets: int, n_docs: int, flags: int, d_stats: int,
+                            d_totals: int, d_entry_hits: int, stream: int):
+        """td_word_matches_device: raw device pointers (d_totals and d_entry_hits may be 0), asynchronous on `stream`, which must not be
+        the null stream; flags 0 or TD_WL_NO_LDS; d_stats int64[n_docs, 4], d_totals int64[4], d_entry_hits int64[n_entries]; check with
+        device_status(stream)."""
+        self._check(self._lib.td_word_matches_device(self._h, wset._h, d_text or None, n_bytes, d_doc_offsets or None, n_docs, flags,
+                                                     d_stats or None, d_totals or None, d_entry_hits or None, stream or None))
+
+    def word_matches(self, wset: WordSet, text, doc_offsets):
+        """td_word_matches: word_matches_host's results, computed on the device."""
+        buf, o, n_docs, stats, totals, hits = _word_matches_args(text, doc_offsets, wset.n_entries)
+        self._check(self._lib.td_word_matches(self._h, wset._h, buf.ctypes.data if len(buf) else None, o.ctypes.data, n_docs, stats.ctypes.data,
+                                              totals.ctypes.data, hits.ctypes.data))
+        return stats[:n_docs], totals, hits[:wset.n_entries]
 
     # ---- decode rows (td_decode_spec) ---------------------------------------------------------------------------
     def decode_rows(self, ids, spec: DecodeSpec, tok_offsets=None, lengths=None, n_segs: int | None = None, capacity: int | None = None):

@@ -308,6 +308,10 @@ struct td_tokenizer {
     // point's stats and totals on the device
     RewriteBufs mask;
     DevBuf ma_dirty, ma_stats, ma_totals;
+    // word-list matches (td_wordlist.hip): the bad-offsets word (its RewriteBufs' head alone); the host entry point's stats, totals and
+    // entry hits on the device
+    RewriteBufs wordlist;
+    DevBuf wl_stats, wl_totals, wl_hits;
     int64_t mh_table_perm = 0;     // 0: no table yet
     uint64_t mh_table_seed = 0;
     std::vector<int64_t> dcr_key;  // flags, then the distinct listed ids with their bits (sorted); empty: no table yet

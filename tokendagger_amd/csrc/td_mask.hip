@@ -66,16 +66,7 @@ __device__ __forceinline__ void ma_load_rules(const MaArgs& a, MaLds& s) {
     if (tid < 2) s.n[tid] = (uint8_t)(tid ? a.rules.n_ips : a.rules.n_emails);
 }
 
-// ---- a window's classes: four bytes a dword at a time, bit 7 of a byte the answer, then four bits a dword -------------------------------
-__device__ __forceinline__ uint32_t ma_eq(uint32_t x, uint32_t c) {
-    x ^= c * 0x01010101u;
-    return ~(((x & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | x) & 0x80808080u;
-}
-__device__ __forceinline__ uint32_t ma_in(uint32_t x, uint32_t lo, uint32_t hi) {  // lo <= byte <= hi < 0x80
-    const uint32_t x7 = x & 0x7F7F7F7Fu;
-    return (x7 + (0x80u - lo) * 0x01010101u) & ~(x7 + (0x7Fu - hi) * 0x01010101u) & ~x & 0x80808080u;
-}
-__device__ __forceinline__ uint32_t ma_pack(uint32_t m) { return ((m >> 7) * 0x00204081u >> 21) & 0xFu; }
+// ---- a window's classes: ma_eq, ma_in and ma_pack of td_rewrite_common.h, four bits a dword ------------------------------------------------
 
 struct MaCls {  // bit k: byte k of the window
     uint32_t at, dig, dot, L;

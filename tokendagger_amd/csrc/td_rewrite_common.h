@@ -83,6 +83,18 @@ __device__ __forceinline__ void rw_load(const uint8_t* text, int64_t b0, int64_t
         if (b0 + k >= b && b0 + k < we) w[k >> 2] |= (uint32_t)text[b0 + k] << (8 * (k & 3));
 }
 
+// A window's byte classes, four bytes a dword at a time (td_mask.hip, td_wordlist.hip): bit 7 of a byte is the answer of ma_eq and
+// ma_in; ma_pack brings a dword's four answers to its low four bits.
+__device__ __forceinline__ uint32_t ma_eq(uint32_t x, uint32_t c) {
+    x ^= c * 0x01010101u;
+    return ~(((x & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | x) & 0x80808080u;
+}
+__device__ __forceinline__ uint32_t ma_in(uint32_t x, uint32_t lo, uint32_t hi) {  // lo <= byte <= hi < 0x80
+    const uint32_t x7 = x & 0x7F7F7F7Fu;
+    return (x7 + (0x80u - lo) * 0x01010101u) & ~(x7 + (0x7Fu - hi) * 0x01010101u) & ~x & 0x80808080u;
+}
+__device__ __forceinline__ uint32_t ma_pack(uint32_t m) { return ((m >> 7) * 0x00204081u >> 21) & 0xFu; }
+
 struct RwTile {  // a tile's place in the text
     int64_t base, t0, s1;  // 16-byte aligned start (may lie in front of the text), first and end byte
 };

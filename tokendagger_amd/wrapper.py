@@ -175,6 +175,28 @@ class MaskedText:
         raise AttributeError(name)
 
 
+class WordMatches:
+    """Tokenizer.word_matches (the contract: include/tokendagger_hip.h, td_word_matches*): how often the entries of a word set occur in
+    every document.  No thresholds here: build a mask from the columns (Gopher's stop words: distinct_groups >= 2; C4's bad words:
+    hits == 0) and hand the kept documents to select_docs."""
+
+    def __init__(self, stats: np.ndarray, totals: np.ndarray, entry_hits: np.ndarray):
+        self.stats = stats            # int64 [n_docs, 4]
+        self.totals = totals          # int64 [4]: hits, the OR of groups, documents with a hit, hit bytes
+        self.entry_hits = entry_hits  # int64 [n_entries]: the occurrences of each entry the set kept, in the set's order
+
+    def __getattr__(self, name):  # the named column views: .hits, .groups, .first_hit, .hit_bytes (capi.WL_COLUMNS)
+        if name in _capi.WL_COLUMNS:
+            return self.stats[:, _capi.WL_COLUMNS.index(name)]
+        raise AttributeError(name)
+
+    @property
+    def distinct_groups(self) -> np.ndarray:
+        """the groups with an occurrence per document: the popcount of GROUPS, read as unsigned"""
+        bits = np.unpackbits(np.ascontiguousarray(self.groups).view(np.uint8).reshape(-1, 8), axis=1)
+        return bits.sum(axis=1, dtype=np.int64)
+
+
 def _lf_phrase(p) -> bytes:
     """a phrase as the rule compares it: bytes, ASCII upper case folded"""
     return (p.encode("utf-8") if isinstance(p, str) else bytes(p)).lower()
@@ -671,6 +693,42 @@ class Tokenizer:
             return MaskedText(*hip.mask_addresses(buf, np.asarray(offsets, dtype=np.int64), rules))
         except _capi.TokenDaggerHipError as ex:
             raise TokenDaggerError(f"Address masking failed: {ex}")
+
+    def word_set(self, words, groups=None, fold: bool = True, anywhere: bool = False) -> "_capi.WordSet":
+        """A list of words or phrases (str or bytes) -> a word set on this tokenizer's device, for word_matches.  fold: ASCII case is
+        ignored, and the entries are lower-cased here.  anywhere: no word boundary is asked for (lists for Chinese, Japanese, Thai).
+        groups: None puts every entry in group 0, "each" numbers up to 64 entries 0, 1, ..., or one group in 0 .. 63 per word.  Exact
+        duplicates (after folding) are dropped, the first one kept: the set's .dropped lists their indices, and entry_hits follows the
+        kept entries."""
+        entries = [w.encode("utf-8") if isinstance(w, str) else bytes(w) for w in words]
+        if fold:
+            entries = [e.lower() for e in entries]  # (bytes.lower: ASCII only)
+        if isinstance(groups, str):
+            if groups != "each" or len(entries) > 64:
+                raise ValueError("groups must be None, 'each' (at most 64 words) or one group per word")
+            groups = list(range(len(entries)))
+        seen, keep = set(), []
+        for i, e in enumerate(entries):
+            if e not in seen:
+                seen.add(e)
+                keep.append(i)
+        hip = _capi.HipTokenizer.borrow(self._core_bpe.handle())
+        flags = (_capi.TD_WL_FOLD_ASCII if fold else 0) | (_capi.TD_WL_ANYWHERE if anywhere else 0)
+        try:
+            ws = hip.word_set([entries[i] for i in keep], None if groups is None else [groups[i] for i in keep], flags)
+        except _capi.TokenDaggerHipError as ex:
+            raise TokenDaggerError(f"Word set failed: {ex}")
+        ws.dropped = [i for i in range(len(entries)) if i not in set(keep)]
+        return ws
+
+    def word_matches(self, text: np.ndarray | bytes, offsets: np.ndarray, word_set: "_capi.WordSet") -> WordMatches:
+        """Concatenated bytes + int64 document offsets + a word set -> WordMatches, on the GPU."""
+        hip = _capi.HipTokenizer.borrow(self._core_bpe.handle())
+        buf = np.frombuffer(text, dtype=np.uint8) if isinstance(text, (bytes, bytearray)) else text
+        try:
+            return WordMatches(*hip.word_matches(word_set, buf, np.asarray(offsets, dtype=np.int64)))
+        except _capi.TokenDaggerHipError as ex:
+            raise TokenDaggerError(f"Word matches failed: {ex}")
 
     def repetition_stats(self, text: np.ndarray | bytes, offsets: np.ndarray, groups: str = "all") -> RepetitionStats:
         """Concatenated bytes + int64 document offsets -> RepetitionStats (duplicate lines and paragraphs per document), on the GPU."""

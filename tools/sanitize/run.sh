@@ -34,6 +34,10 @@ g++ $F $H $S/linefilter_asan.cpp -o /tmp/td_linefilter_asan
 # The address mask's statement (ma_host of td_mask_args.h, which td_mask_addresses_host is), the same way.
 g++ $F $H $S/mask_asan.cpp -o /tmp/td_mask_asan
 /tmp/td_mask_asan
+# The word-list statement and the set's builder (wl_host and wl_build of td_wordlist_args.h, which td_word_matches_host and
+# td_word_set_create are), the same way.
+g++ $F $H $S/wordlist_asan.cpp -o /tmp/td_wordlist_asan
+/tmp/td_wordlist_asan
 # The code the DEVICE shares with the host (td_common.h: scanners, exact-key probes, merge rounds; td_regex.h: the matcher) runs
 # in the CPU twin; under the sanitizers (round 3: the twin tests, the generic-pattern tests and 30 000 fuzz documents, no report):
 #   g++ -std=c++17 -O1 -g -fPIC -shared -fsanitize=address,undefined tests/twin/td_twin.cpp $C/td_tables.cpp $C/td_regex.cpp \
