@@ -1414,6 +1414,85 @@ int td_word_matches_device(td_tokenizer* t, const td_word_set* set, const void* 
 int td_word_matches(td_tokenizer* t, const td_word_set* set, const uint8_t* text, const int64_t* doc_offsets, int64_t n_docs, int64_t* stats,
                     int64_t* totals, int64_t* entry_hits);
 
+/* ---- bag models: fastText-style linear classifiers over hashed word and character n-grams (td_bag.hip) ---------------------------------------
+ * Language identification (lid.176-shaped models) and quality classifiers (DCLM-shaped ones) on text that is already on the device.
+ * Text + doc_offsets[n_docs + 1] (int64: from 0, non-decreasing, ending at or below n_bytes) + a bag model -> each document's best label
+ * and its probability, optionally every label's probability and the hidden vector, and exact integer counts.  One document is one
+ * fastText "line".  Host statement, model builder and kernels compile the same statement of the rule (td_bag_args.h).  The rule follows
+ * fastText's Dictionary::getLine and Model::predict as read from their source; parity with the fastText library on a real model file is
+ * NOT checked anywhere.
+ *   DOCUMENTS   are independent; "edge" is the document's edge.
+ *   TOKENS      a delimiter is one of the bytes 0x20 0x0A 0x0D 0x09 0x0B 0x0C 0x00; a token is a maximal run of other bytes inside a
+ *               document.  A token longer than TD_BAG_TOKEN_BYTES is skipped whole: no feature, absent from the word sequence, counted
+ *               in LONG (departure 1 from fastText).
+ *   HASH        h = 2166136261; for each byte c: h = (h ^ (uint32_t)(int8_t)c) * 16777619 (the sign extension is part of the rule).
+ *   WORD        a token whose bytes are a word of the dictionary (compared by bytes) emits row w, its index.
+ *   CHAR GRAMS  maxn > 0: s = '<' + token + '>'; for every i with (s[i] & 0xC0) != 0x80, n = 1 .. maxn: a step takes one byte and every
+ *               following byte with (b & 0xC0) == 0x80, and stops at the end of s; behind step n, with j the position behind the n-gram,
+ *               row nwords + hash(s[i, j)) % bucket is emitted if n >= minn and not (n == 1 and (i == 0 or j == len(s))).
+ *   END         with TD_BAG_EOS one token "</s>" follows a document's last token: its word row if "</s>" is a word, never character
+ *               n-grams; its hash joins the word sequence.  A literal "</s>" in the text is an ordinary token that gets the word row and
+ *               no character n-grams (departure 2).  Tokens that begin with "__label__" are ordinary tokens (departure 3).
+ *   WORD GRAMS  word_ngrams = N: H[0, m) the kept tokens' hashes as int32, EOS last; for every i: h = (uint64)(int64)H[i]; for j = i + 1
+ *               .. min(m, i + N) - 1: h = h * 116049371 + (uint64)(int64)H[j], row nwords + h % bucket emitted after each j.
+ *   HIDDEN      the fp32 sum of the emitted rows divided by their count n (FEATURES), one fp32 division a column.  n == 0: hidden and
+ *               probabilities are 0 and best is -1.
+ *   OUTPUT      TD_BAG_SOFTMAX: softmax(Wo . hidden) over n_labels rows; TD_BAG_OVA: a sigmoid a row; TD_BAG_HS: Wo has n_labels - 1
+ *               rows, the tree is fastText's buildTree over label_counts (non-increasing), and
+ *               log p[l] = sum_k log(code_k ? s(f_k) : 1 - s(f_k)), f_k = Wo[path_k] . hidden, with exact sigmoid and log (no tables).
+ *               best is the lowest index of the largest probability.
+ *   MODEL       word_bytes (flat), word_offsets[n_words + 1] (int64, from 0), input [n_words + bucket, dim] and output [n_labels, dim]
+ *               ([n_labels - 1, dim] under TD_BAG_HS), row-major fp32 on the host; label_counts[n_labels] (int64; read under TD_BAG_HS
+ *               only).  1 <= dim <= 512; 1 <= n_labels <= 4096 (HS: >= 2); 0 <= minn <= maxn <= 8 with minn >= 1 unless both are 0;
+ *               1 <= word_ngrams <= 5; 0 <= bucket <= 2^31, and 0 only with maxn == 0 and word_ngrams == 1; n_words <= 2^26;
+ *               n_words + bucket >= 1 (the input matrix has a row).  TD_E_INVALID with
+ *               *err_pos (may be NULL) the lowest word that is empty, holds a delimiter or equals an earlier word (the second one is
+ *               named); -1 where no word is to blame.  A word longer than TD_BAG_TOKEN_BYTES is accepted and never matches.
+ *   COLUMNS     stats[n_docs][TD_BAG_COLS] and totals (int64): 0 TOKENS (kept, EOS included)  1 IN_VOCAB  2 FEATURES  3 LONG
+ * Every column of a sum is added in an order fixed by the text and the model alone (no floating-point atomics): two calls give the
+ * same bits.  Out of scope: quantised or pruned models, other dtypes, top-k lists. */
+#define TD_BAG_COLS 4
+#define TD_BAG_TOKEN_BYTES 1024
+#define TD_BAG_SOFTMAX 0
+#define TD_BAG_OVA 1
+#define TD_BAG_HS 2
+#define TD_BAG_EOS 1 /* a classify call's flag */
+typedef struct td_bag_params {
+    int32_t dim, n_labels, minn, maxn, word_ngrams, loss;
+    int64_t bucket;
+} td_bag_params;
+typedef struct td_bag_model td_bag_model;
+/* Checks the model, builds the dictionary's table and the tree on the host and uploads them with the matrices to t's device
+ * (synchronous).  The model is immutable afterwards: any handle on that device may use it on any stream.  It does not keep t. */
+int td_bag_model_create(td_tokenizer* t, const uint8_t* word_bytes, const int64_t* word_offsets, int64_t n_words, const float* input,
+                        const float* output, const int64_t* label_counts, const td_bag_params* params, td_bag_model** out, int64_t* err_pos);
+/* Frees the model's device memory at once, like hipFree: the caller must have finished the work that uses it. */
+void td_bag_model_destroy(td_bag_model* model);
+#define TD_BAG_INFO_WORDS 1        /* the dictionary's words */
+#define TD_BAG_INFO_DIM 2
+#define TD_BAG_INFO_LABELS 3
+#define TD_BAG_INFO_DEVICE_BYTES 4 /* the device memory the model holds */
+#define TD_BAG_INFO_EOS_INDEX 5    /* the word index of "</s>", or -1 */
+#define TD_BAG_INFO_TREE_DEPTH 6   /* TD_BAG_HS: the longest path; otherwise 0 */
+int64_t td_bag_model_info(const td_bag_model* model, int what); /* -1: no such value */
+/* The contract's executable statement, on the host (no handle, no device, no hash table: the dictionary itself, sorted; sums in
+ * double).  probs [n_docs, n_labels], hidden [n_docs, dim] and totals may be NULL.  Argument errors write nothing but *err_pos. */
+int td_bag_classify_host(const uint8_t* word_bytes, const int64_t* word_offsets, int64_t n_words, const float* input, const float* output,
+                         const int64_t* label_counts, const td_bag_params* params, const uint8_t* text, const int64_t* doc_offsets,
+                         int64_t n_docs, int flags, int32_t* best, float* best_prob, float* probs, float* hidden, int64_t* stats,
+                         int64_t* totals, int64_t* err_pos);
+/* DEVICE buffers, asynchronously on hip_stream (never the null stream).  d_best int32[n_docs], d_best_prob fp32[n_docs], d_stats
+ * int64[n_docs, 4], d_totals int64[4] (may be NULL), d_probs fp32[n_docs, n_labels] and d_hidden fp32[n_docs, dim] (NULL: not written).
+ * d_doc_offsets, d_stats and d_totals are 8-byte aligned, the fp32 and int32 outputs 4-byte aligned; d_text needs no alignment.
+ * flags: 0 or TD_BAG_EOS.  Bad offsets raise TD_E_INVALID through td_device_status with err_pos = the lowest such document, and then
+ * NOTHING is written.  The handle's scratch grows with the text (16 bytes a token, a padded row of the input matrix a document). */
+int td_bag_classify_device(td_tokenizer* t, const td_bag_model* model, const void* d_text, int64_t n_bytes, const void* d_doc_offsets,
+                           int64_t n_docs, int flags, void* d_best, void* d_best_prob, void* d_probs, void* d_hidden, void* d_stats,
+                           void* d_totals, void* hip_stream);
+/* Host buffers, synchronously; probs, hidden and totals may be NULL. */
+int td_bag_classify(td_tokenizer* t, const td_bag_model* model, const uint8_t* text, const int64_t* doc_offsets, int64_t n_docs, int flags,
+                    int32_t* best, float* best_prob, float* probs, float* hidden, int64_t* stats, int64_t* totals);
+
 /* Options. */
 #define TD_OPT_LONG_POOL_BYTES 1 /* scratch for pieces longer than 64 bytes (default max(64 MiB, 2 x input)) */
 #define TD_OPT_PROFILE 2         /* 1: bracket the kernels of every td_encode_device call with HIP events on the

@@ -89,6 +89,7 @@ EXPORTS = [
     "td_line_filter_host", "td_line_filter_device", "td_line_filter",
     "td_mask_addresses_host", "td_mask_addresses_device", "td_mask_addresses",
     "td_word_set_create", "td_word_set_destroy", "td_word_set_info", "td_word_matches_host", "td_word_matches_device", "td_word_matches",
+    "td_bag_model_create", "td_bag_model_destroy", "td_bag_model_info", "td_bag_classify_host", "td_bag_classify_device", "td_bag_classify",
 ]
 
 
@@ -308,6 +309,18 @@ def load_library():
     lib.td_word_matches_device.argtypes = [vp, vp, vp, i64, vp, i64, i32, vp, vp, vp, vp]
     lib.td_word_matches.restype = i32
     lib.td_word_matches.argtypes = [vp, vp, vp, vp, i64, vp, vp, vp]
+    lib.td_bag_model_create.restype = i32
+    lib.td_bag_model_create.argtypes = [vp, vp, vp, i64, vp, vp, vp, vp, ctypes.POINTER(vp), ctypes.POINTER(i64)]
+    lib.td_bag_model_destroy.restype = None
+    lib.td_bag_model_destroy.argtypes = [vp]
+    lib.td_bag_model_info.restype = i64
+    lib.td_bag_model_info.argtypes = [vp, i32]
+    lib.td_bag_classify_host.restype = i32
+    lib.td_bag_classify_host.argtypes = [vp, vp, i64, vp, vp, vp, vp, vp, vp, i64, i32, vp, vp, vp, vp, vp, vp, ctypes.POINTER(i64)]
+    lib.td_bag_classify_device.restype = i32
+    lib.td_bag_classify_device.argtypes = [vp, vp, vp, i64, vp, i64, i32, vp, vp, vp, vp, vp, vp, vp]
+    lib.td_bag_classify.restype = i32
+    lib.td_bag_classify.argtypes = [vp, vp, vp, vp, i64, i32, vp, vp, vp, vp, vp, vp]
     lib.td_encode_batch_token_counts.restype = i32
     lib.td_encode_batch_token_counts.argtypes = [vp, vp, vp, i64, i32, vp, vp, vp, vp, ctypes.POINTER(i64)]
     lib.td_comm_unique_id.restype = i32
@@ -1230,6 +1243,112 @@ class WordSet:
     def close(self):
         if getattr(self, "_h", None):
             self._lib.td_word_set_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+TD_BAG_COLS, TD_BAG_TOKEN_BYTES, TD_BAG_EOS = 4, 1024, 1
+TD_BAG_SOFTMAX, TD_BAG_OVA, TD_BAG_HS = 0, 1, 2
+TD_BAG_INFO = {"words": 1, "dim": 2, "labels": 3, "device_bytes": 4, "eos_index": 5, "tree_depth": 6}
+# stats[:, c] by name (include/tokendagger_hip.h, td_bag_classify*, COLUMNS)
+BAG_COLUMNS = ("tokens", "in_vocab", "features", "long")
+
+
+class BagParams(ctypes.Structure):
+    """td_bag_params"""
+    _fields_ = [("dim", ctypes.c_int32), ("n_labels", ctypes.c_int32), ("minn", ctypes.c_int32), ("maxn", ctypes.c_int32),
+                ("word_ngrams", ctypes.c_int32), ("loss", ctypes.c_int32), ("bucket", ctypes.c_int64)]
+
+
+class BagSpec:
+    """A bag model on the host, as the C ABI takes it: the dictionary flat, the matrices fp32 and contiguous, the parameters.  The
+    arrays' shapes are checked here against one another (ValueError), because the library sees pointers and cannot; everything else the
+    library checks."""
+
+    def __init__(self, words, input_matrix, output_matrix, *, bucket, minn=0, maxn=0, word_ngrams=1, loss=TD_BAG_SOFTMAX, label_counts=None):
+        self.wb, self.wo, _ = word_list(words)
+        self.input = np.ascontiguousarray(input_matrix, dtype=np.float32)
+        self.output = np.ascontiguousarray(output_matrix, dtype=np.float32)
+        self.counts = None if label_counts is None else np.ascontiguousarray(label_counts, dtype=np.int64)
+        self.n_labels = self.output.shape[0] + (1 if loss == TD_BAG_HS else 0)
+        self.dim = self.input.shape[1] if self.input.ndim == 2 else 0
+        if self.input.ndim != 2 or self.output.ndim != 2 or self.input.shape[1] != self.output.shape[1]:
+            raise ValueError("input_matrix and output_matrix must be two-dimensional with the same number of columns")
+        if self.input.shape[0] != len(self.wo) - 1 + max(int(bucket), 0):
+            raise ValueError(f"input_matrix has {self.input.shape[0]} rows, not len(words) + bucket = {len(self.wo) - 1 + max(int(bucket), 0)}")
+        if loss == TD_BAG_HS and self.counts is not None and len(self.counts) != self.n_labels:
+            raise ValueError(f"label_counts has {len(self.counts)} entries, not n_labels = output_matrix rows + 1 = {self.n_labels}")
+        self.params = BagParams(self.dim, self.n_labels, minn, maxn, word_ngrams, loss, bucket)
+
+    def args(self):
+        """the model's arguments in the order td_bag_model_create and td_bag_classify_host take them"""
+        return (self.wb.ctypes.data if len(self.wb) else None, self.wo.ctypes.data, len(self.wo) - 1, self.input.ctypes.data,
+                self.output.ctypes.data, self.counts.ctypes.data if self.counts is not None else None, ctypes.byref(self.params))
+
+
+def _bag_outputs(n_docs, n_labels, dim, probs, hidden):
+    d = max(n_docs, 1)
+    return (np.zeros(d, dtype=np.int32), np.zeros(d, dtype=np.float32), np.zeros((d, n_labels), dtype=np.float32) if probs else None,
+            np.zeros((d, dim), dtype=np.float32) if hidden else None, np.zeros((d, TD_BAG_COLS), dtype=np.int64), np.zeros(TD_BAG_COLS, dtype=np.int64))
+
+
+def _bag_result(n_docs, best, bprob, pr, hid, stats, totals):
+    return {"best": best[:n_docs], "best_prob": bprob[:n_docs], "probs": None if pr is None else pr[:n_docs],
+            "hidden": None if hid is None else hid[:n_docs], "stats": stats[:n_docs], "totals": totals}
+
+
+def bag_classify_host(spec: BagSpec, text, doc_offsets, flags: int = TD_BAG_EOS, probs: bool = True, hidden: bool = True):
+    """td_bag_classify_host (host only, no device) -> a dict of best, best_prob, probs, hidden, stats, totals.  A bad model raises
+    TokenDaggerHipError with .pos, the word to blame or -1."""
+    lib = load_library()
+    buf = _as_u8(text)
+    o = np.ascontiguousarray(doc_offsets, dtype=np.int64)
+    n_docs = len(o) - 1
+    if n_docs >= 0 and len(o) and int(o[-1]) > len(buf):
+        raise TokenDaggerHipError(TD_E_INVALID, "td_bag_classify_host: doc_offsets end behind the text")
+    out = _bag_outputs(n_docs, spec.n_labels, spec.dim, probs, hidden)
+    pos = ctypes.c_int64(-1)
+    rc = lib.td_bag_classify_host(*spec.args(), buf.ctypes.data if len(buf) else None, o.ctypes.data if len(o) else None, n_docs, flags,
+                                  *(x.ctypes.data if x is not None else None for x in out), ctypes.byref(pos))
+    if rc != TD_OK:
+        ex = TokenDaggerHipError(rc, f"td_bag_classify_host: invalid model (word {pos.value}), offsets or arguments")
+        ex.pos = pos.value
+        raise ex
+    return _bag_result(n_docs, *out)
+
+
+class BagModel:
+    """Owns one td_bag_model: a checked dictionary, the matrices and the tree on a tokenizer's device.  Immutable; any handle on that
+    device may use it.  A context manager; close() frees the device memory at once, so the work that uses the model must be done.  A bad
+    model raises TokenDaggerHipError with .pos, the word to blame or -1."""
+
+    def __init__(self, tok: "HipTokenizer", spec: BagSpec, labels=None):
+        self._lib = tok._lib
+        self._h = None
+        h, pos = ctypes.c_void_p(), ctypes.c_int64(-1)
+        try:
+            tok._check(self._lib.td_bag_model_create(tok._h, *spec.args(), ctypes.byref(h), ctypes.byref(pos)))
+        except TokenDaggerHipError as ex:
+            ex.pos = pos.value
+            raise
+        self._h = h
+        self.n_labels, self.dim, self.labels = spec.n_labels, spec.dim, None if labels is None else list(labels)
+
+    @property
+    def info(self) -> dict[str, int]:
+        """words, dim, labels, device_bytes, eos_index, tree_depth."""
+        return {k: int(self._lib.td_bag_model_info(self._h, v)) for k, v in TD_BAG_INFO.items()}
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.td_bag_model_destroy(self._h)
             self._h = None
 
     __del__ = close
@@ -2426,6 +2545,29 @@ class HipTokenizer:
         self._check(self._lib.td_word_matches(self._h, wset._h, buf.ctypes.data if len(buf) else None, o.ctypes.data, n_docs, stats.ctypes.data,
                                               totals.ctypes.data, hits.ctypes.data))
         return stats[:n_docs], totals, hits[:wset.n_entries]
+
+    # ---- bag models (td_bag_model) ------------------------------------------------------------------------------------------
+    def bag_model(self, spec: BagSpec, labels=None) -> BagModel:
+        """td_bag_model_create from a BagSpec."""
+        return BagModel(self, spec, labels)
+
+    def bag_classify_device(self, model: BagModel, d_text: int, n_bytes: int, d_doc_offsets: int, n_docs: int, flags: int, d_best: int,
+                            d_best_prob: int, d_probs: int, d_hidden: int, d_stats: int, d_totals: int, stream: int):
+        """td_bag_classify_device: raw device pointers (d_probs, d_hidden and d_totals may be 0), asynchronous on `stream`, which must not
+        be the null stream; flags 0 or TD_BAG_EOS; check with device_status(stream)."""
+        self._check(self._lib.td_bag_classify_device(self._h, model._h, d_text or None, n_bytes, d_doc_offsets or None, n_docs, flags,
+                                                     d_best or None, d_best_prob or None, d_probs or None, d_hidden or None, d_stats or None,
+                                                     d_totals or None, stream or None))
+
+    def bag_classify(self, model: BagModel, text, doc_offsets, flags: int = TD_BAG_EOS, probs: bool = False, hidden: bool = False):
+        """td_bag_classify: bag_classify_host's results, computed on the device."""
+        buf = _as_u8(text)
+        o = np.ascontiguousarray(doc_offsets, dtype=np.int64)
+        n_docs = len(o) - 1
+        out = _bag_outputs(n_docs, model.n_labels, model.dim, probs, hidden)
+        self._check(self._lib.td_bag_classify(self._h, model._h, buf.ctypes.data if len(buf) else None, o.ctypes.data, n_docs, flags,
+                                              *(x.ctypes.data if x is not None else None for x in out)))
+        return _bag_result(n_docs, *out)
 
     # ---- decode rows (td_decode_spec) ---------------------------------------------------------------------------
     def decode_rows(self, ids, spec: DecodeSpec, tok_offsets=None, lengths=None, n_segs: int | None = None, capacity: int | None = None):

@@ -312,6 +312,11 @@ struct td_tokenizer {
     // entry hits on the device
     RewriteBufs wordlist;
     DevBuf wl_stats, wl_totals, wl_hits;
+    // bag models (td_bag.hip): the bad-offsets word and the tiles' records (its RewriteBufs' head and tiles), the tokens' records, the
+    // records in front of each document, the documents' sums and the chunks' partials, the call's records; the host entry point's
+    // outputs on the device
+    RewriteBufs bag;
+    DevBuf bag_rec, bag_first, bag_hsum, bag_part, bag_head, bag_best, bag_bprob, bag_probs, bag_hidden, bag_stats, bag_totals;
     int64_t mh_table_perm = 0;     // 0: no table yet
     uint64_t mh_table_seed = 0;
     std::vector<int64_t> dcr_key;  // flags, then the distinct listed ids with their bits (sorted); empty: no table yet

@@ -175,6 +175,34 @@ class MaskedText:
         raise AttributeError(name)
 
 
+class BagResult:
+    """Tokenizer.classify (the contract: include/tokendagger_hip.h, td_bag_classify*): each document's best label and its probability,
+    the integer columns, and where asked for every label's probability and the hidden vector."""
+
+    def __init__(self, model, res: dict):
+        self.model = model
+        self.best = res["best"]            # int32 [n_docs]; -1: a document without a feature
+        self.best_prob = res["best_prob"]  # float32 [n_docs]
+        self.probs = res["probs"]          # float32 [n_docs, n_labels] or None
+        self.hidden = res["hidden"]        # float32 [n_docs, dim] or None
+        self.stats = res["stats"]          # int64 [n_docs, 4]
+        self.totals = res["totals"]        # int64 [4]
+
+    def __getattr__(self, name):  # the named column views: .tokens, .in_vocab, .features, .long (capi.BAG_COLUMNS)
+        if name in _capi.BAG_COLUMNS:
+            return self.stats[:, _capi.BAG_COLUMNS.index(name)]
+        raise AttributeError(name)
+
+    def mask(self, label, min_prob: float = 0.0) -> np.ndarray:
+        """bool [n_docs]: the documents whose best label is `label` (an index, or a name of the model's labels) with at least
+        min_prob: what select_docs keeps."""
+        if not isinstance(label, (int, np.integer)):
+            if self.model.labels is None:
+                raise ValueError("the model was made without labels: pass the label's index")
+            label = self.model.labels.index(label)
+        return (self.best == label) & (self.best_prob >= min_prob)
+
+
 class WordMatches:
     """Tokenizer.word_matches (the contract: include/tokendagger_hip.h, td_word_matches*): how often the entries of a word set occur in
     every document.  No thresholds here: build a mask from the columns (Gopher's stop words: distinct_groups >= 2; C4's bad words:
@@ -729,6 +757,32 @@ class Tokenizer:
             return WordMatches(*hip.word_matches(word_set, buf, np.asarray(offsets, dtype=np.int64)))
         except _capi.TokenDaggerHipError as ex:
             raise TokenDaggerError(f"Word matches failed: {ex}")
+
+    def bag_model(self, words, input_matrix, output_matrix, *, bucket: int, minn: int = 0, maxn: int = 0, word_ngrams: int = 1,
+                  loss: str = "softmax", label_counts=None, labels=None) -> "_capi.BagModel":
+        """A fastText-style model -> a bag model on this tokenizer's device, for classify.  words: the dictionary (str or bytes) in index
+        order; input_matrix [len(words) + bucket, dim] and output_matrix [n_labels, dim] ([n_labels - 1, dim] for loss "hs") fp32;
+        loss "softmax", "ova" or "hs" (hierarchical softmax: label_counts, non-increasing, builds the tree); labels: names for
+        BagResult.mask."""
+        hip = _capi.HipTokenizer.borrow(self._core_bpe.handle())
+        entries = [w.encode("utf-8") if isinstance(w, str) else bytes(w) for w in words]
+        try:
+            spec = _capi.BagSpec(entries, input_matrix, output_matrix, bucket=bucket, minn=minn, maxn=maxn, word_ngrams=word_ngrams,
+                                 loss={"softmax": _capi.TD_BAG_SOFTMAX, "ova": _capi.TD_BAG_OVA, "hs": _capi.TD_BAG_HS}[loss], label_counts=label_counts)
+            return hip.bag_model(spec, labels)
+        except (_capi.TokenDaggerHipError, ValueError) as ex:
+            raise TokenDaggerError(f"Bag model failed: {ex}")
+
+    def classify(self, text: np.ndarray | bytes, offsets: np.ndarray, model: "_capi.BagModel", *, probs: bool = False, hidden: bool = False,
+                 eos: bool = True) -> BagResult:
+        """Concatenated bytes + int64 document offsets + a bag model -> BagResult, on the GPU.  eos: "</s>" follows every document, as
+        fastText's predict does."""
+        hip = _capi.HipTokenizer.borrow(self._core_bpe.handle())
+        buf = np.frombuffer(text, dtype=np.uint8) if isinstance(text, (bytes, bytearray)) else text
+        try:
+            return BagResult(model, hip.bag_classify(model, buf, np.asarray(offsets, dtype=np.int64), _capi.TD_BAG_EOS if eos else 0, probs, hidden))
+        except _capi.TokenDaggerHipError as ex:
+            raise TokenDaggerError(f"Classify failed: {ex}")
 
     def repetition_stats(self, text: np.ndarray | bytes, offsets: np.ndarray, groups: str = "all") -> RepetitionStats:
         """Concatenated bytes + int64 document offsets -> RepetitionStats (duplicate lines and paragraphs per document), on the GPU."""

@@ -38,6 +38,10 @@ g++ $F $H $S/mask_asan.cpp -o /tmp/td_mask_asan
 # td_word_set_create are), the same way.
 g++ $F $H $S/wordlist_asan.cpp -o /tmp/td_wordlist_asan
 /tmp/td_wordlist_asan
+# The bag models' statement and the model's builder (bag_host, bag_build_dict and bag_build_tree of td_bag_args.h, which
+# td_bag_classify_host and td_bag_model_create are), the same way.
+g++ $F $H $S/bag_asan.cpp -o /tmp/td_bag_asan
+/tmp/td_bag_asan
 # The code the DEVICE shares with the host (td_common.h: scanners, exact-key probes, merge rounds; td_regex.h: the matcher) runs
 # in the CPU twin; under the sanitizers (round 3: the twin tests, the generic-pattern tests and 30 000 fuzz documents, no report):
 #   g++ -std=c++17 -O1 -g -fPIC -shared -fsanitize=address,undefined tests/twin/td_twin.cpp $C/td_tables.cpp $C/td_regex.cpp \
